@@ -2,25 +2,36 @@
 """Benchmark of the hot path on BASELINE.json's workload: GCUPS of the banded semi-global DP on
 synthetic 50 kb x 50 kb contig pairs (5 % divergence, band 512; generator of SURVEY.md 8d).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--scaling strong|weak] [--full] [--dump-outputs DIR]
 
 One "step" = one gamdp_align_batch call over this rank's pairs (fill + end-cell search + traceback summary for
 every pair), sequences already packed and resident in HBM.  N > 1 = one process per GPU (the driver starts them
 with torch.distributed.run; `python bench.py --gpus N` on its own spawns the same thing as a child process).
 
+A plain run only sets up, warms up, times the K steps and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, plus the roofline and launch_info of those same steps).  Everything that
+takes runs of its own -- the CPU baseline and the verification against it, the weak-scaling record of an N > 1
+strong run, band150, strong8/4_proxy, mixed150 and l1 below -- runs only with --full (the --no-* options still
+drop single records there).
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the last step returned for its pairs: one float64
+                      DIR/<field>.npy per field of gamdp_result (status, begin_a, ..., homology) and pair_index.npy
+                      (the generator's pair id of every row).  Inputs are the seeded generator's, so two builds can
+                      be compared file for file; above 64 MB in all, a fixed, evenly spread sample of the pairs.
+
   --scaling strong (default)  BASELINE config 5 as written: ONE fixed list of P pairs (100 000), dealt over the N
                               GPUs by the library's partitioner (gamdp_partition_lpt on predicted cells: equal
                               weights -> round-robin); value = P pairs' cells / max-over-ranks time.
   --scaling weak              every rank aligns its own P pairs; value = N*P pairs' cells / max-over-ranks time.
-With N > 1 the strong-scaling line also carries a short weak-scaling measurement ("weak": {...}).
+With N > 1 and --full the strong-scaling line also carries a short weak-scaling measurement ("weak": {...}).
 There is no data-path collective in either mode; RCCL only carries the barrier and three timing scalars.
 BENCH_SHARE_GPU=1 (tests/test_gpu_bench_ranks.py): all ranks on GPU 0 over gloo, a bounded scratch arena per rank (--arena-gb) -- the
-N > 1 path on a one-GPU box, not a multi-GPU measurement.  With N > 1 rank 0 compares --verify-pairs pairs of ITS share with the CPU
-path (verified_pairs); cpu_baseline itself, a timing of the host cores, stays an N = 1 record.
+N > 1 path on a one-GPU box, not a multi-GPU measurement.  With N > 1 and --full rank 0 compares --verify-pairs pairs of ITS share
+with the CPU path (verified_pairs); cpu_baseline itself, a timing of the host cores, stays an N = 1 record.
 
 The printed JSON line also carries
   roofline        algorithmic HBM bytes (0.2507 B per cell update) of one kernel launch divided by
                   that launch's HIP-event duration (the library's own stream), against the 8 TB/s HBM peak;
+and, with --full,
   cpu_baseline    the reference's own find_alignment (oracle/_ref, kind "reference") or, where that build is
                   absent, our C restatement (oracle/, kind "port"), timed on this box's host cores on a bounded
                   sample of the same pairs (rank 0, N = 1 only);
@@ -237,6 +248,26 @@ def strided_sample(n_total, n_sample):
     return sorted({round(j * (n_total - 1) / max(1, n - 1)) for j in range(n)}) if n_total else []
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, P, first, stride):
+    """--dump-outputs: the gamdp_result fields of the pairs of the last step, one float64 array per field (every value
+    is an integer below 2^53 or already a double, so the conversion is exact), and pair_index (the generator's id of
+    each row).  When all rows would exceed DUMP_MAX_BYTES, a fixed, evenly spread sample of rows is written."""
+    import numpy as np
+    from gam_ngs_amd import lib as L
+    names = [f for f, _ in L.Result._fields_ if f != "pad_"]
+    rec = np.ctypeslib.as_array(out)[:P]        # a structured view of the caller's result array
+    cap = DUMP_MAX_BYTES // (8 * (len(names) + 1))
+    rows = np.arange(P) if P <= cap else np.array(strided_sample(P, cap), dtype=np.int64)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "pair_index.npy"), (first + rows * stride).astype(np.float64))
+    for f in names:
+        np.save(os.path.join(path, f + ".npy"), rec[f][rows].astype(np.float64))
+    return len(rows)
+
+
 def strong_proxy_record(ctx, n_gpus, pairs_total, length, band, value, steps=2, warmup=1, verify=128):
     """Rank 0's share of the fixed list in a strong-scaling run over n_gpus GPUs (pairs 0, n_gpus, 2 n_gpus, ...: what
     gamdp_partition_lpt deals it on equal weights), timed on this GPU."""
@@ -450,7 +481,14 @@ def main():
     ap.add_argument("--verify-pairs", type=int, default=128,
                     help="N > 1: pairs of rank 0's share compared with the CPU path (0 = none); N = 1 verifies the cpu_baseline sample")
     ap.add_argument("--no-mixed150", action="store_true", help="skip the mixed150 record (a driver-shaped batch of 100 000 band-150 calls)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: cpu_baseline + verification, weak (N > 1), band150, proxies, "
+                         "mixed150, l1 (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's results of the last timed step as float64 DIR/<field>.npy (at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args))
@@ -550,8 +588,10 @@ def main():
         return m
 
     m = measure(args.scaling, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["_keep"][2], m["P"], m["first"], m["stride"])
     weak = None
-    if world > 1 and args.scaling == "strong":
+    if args.full and world > 1 and args.scaling == "strong":
         w = measure("weak", 1, 1)
         weak = {"value": w["gcups"], "unit": "GCUPS", "pairs_per_gpu_per_step": w["P"], "steps": 1,
                 "ms_per_step": w["dt_max"] * 1e3}
@@ -606,7 +646,7 @@ def main():
             line["results_unusable"] = True
             print("bench.py: WARNING: %d pairs came back without an alignment (GAMDP_BENCH_IGNORE_FAILED): NOT a valid measurement"
                   % int(m["bad_all"]), file=sys.stderr)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             n_cpu = min(args.cpu_pairs or 512, m["P"])   # ~26 G cell updates: 10 - 15 s of the reference on this box's cores
             # the sample is spread over the whole list (the list order is also the order in which a launch pairs tasks
             # up); only the oracle's own bench entry ("port", no reference build on this box) needs a contiguous range
@@ -625,7 +665,7 @@ def main():
                                  % (ids[k], rec["kind"], gpu_keys[k], cpu_keys[k], len(diff), len(pos)))
             line["verified_pairs"] = len(pos)   # status, begin, score, #matches, length, first/last match, identity
             line["verified_sample"] = "every %d-th pair of the list" % max(1, (m["P"] - 1) // max(1, len(pos) - 1))
-        if world > 1 and args.verify_pairs and not args.no_cpu_baseline:
+        if args.full and world > 1 and args.verify_pairs and not args.no_cpu_baseline:
             # N > 1: the line is certified too -- a sample spread over RANK 0's share against the CPU path (the baseline
             # itself, a timing of the host cores, stays an N = 1 record: N ranks would time the same cores N times)
             pos = strided_sample(m["P"], min(args.verify_pairs, m["P"]))
@@ -645,17 +685,17 @@ def main():
             line["config"]["arena_bytes_per_rank"] = arena_bytes
         if share_gpu and world > 1:
             line["config"]["note"] = "BENCH_SHARE_GPU=1: %d ranks on ONE GPU over gloo -- a test of the N > 1 path, not a multi-GPU measurement" % world
-        if not args.no_band150 and world == 1 and band == 512 and "_keep" in m:
+        if args.full and not args.no_band150 and world == 1 and band == 512 and "_keep" in m:
             line["band150"] = band150_record(ctx, m, length, verify=0 if args.no_cpu_baseline else 128)
-        if not args.no_proxy and world == 1 and band == 512 and args.scaling == "strong" and args.pairs >= 64:
+        if args.full and not args.no_proxy and world == 1 and band == 512 and args.scaling == "strong" and args.pairs >= 64:
             if "_keep" in m:
                 m["_keep"][0].close()   # the headline's sequences: make room
             for ng in (8, 4):
                 line["strong%d_proxy" % ng] = strong_proxy_record(ctx, ng, args.pairs, length, band, m["gcups"],
                                                                   verify=0 if args.no_cpu_baseline else 128)
-        if not args.no_mixed150 and world == 1 and band == 512:
+        if args.full and not args.no_mixed150 and world == 1 and band == 512:
             line["mixed150"] = mixed150_record(ctx, verify=0 if args.no_cpu_baseline else 256)
-        if not args.no_l1 and world == 1:
+        if args.full and not args.no_l1 and world == 1:
             import bench_l1
             line["l1"] = bench_l1.run(ctx, genome=args.l1_genome, cpu=not args.no_cpu_baseline)
         print(json.dumps(line), flush=True)

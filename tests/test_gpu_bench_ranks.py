@@ -22,7 +22,7 @@ def run_bench(*flags, ranks=2, timeout=900):
     env = dict(os.environ, BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "GAMDP_LIB", "GAMDP_QUAD_MIN"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--full",
            "--no-l1", "--no-mixed150", "--no-proxy", "--no-band150", "--arena-gb", "4"] + list(flags)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2500:] + r.stderr[-2500:]

@@ -35,6 +35,64 @@ def test_bridge_compiles_against_the_c_abi_alone(tmp_path):
         assert hasattr(lib, name), name
 
 
+def patch_files():
+    """The patch read on its own: {path: [(old_start, old_len, new_start, new_len, lines)]}, the hunk counts checked."""
+    files, cur, hunk = {}, None, None
+    for line in open(PATCH).read().split("\n")[:-1]:
+        if line.startswith("diff "):
+            cur, hunk = None, None
+        elif line.startswith("+++ ") and hunk is None:
+            cur = line[4:].split("\t")[0][2:]
+            files[cur] = []
+        elif line.startswith("--- ") and hunk is None:
+            pass
+        elif line.startswith("@@ "):
+            old, new = line.split()[1:3]
+            o = [int(x) for x in (old[1:] + ",1").split(",")[:2]]
+            n = [int(x) for x in (new[1:] + ",1").split(",")[:2]]
+            hunk = (o[0], o[1], n[0], n[1], [])
+            files[cur].append(hunk)
+        else:
+            assert hunk is not None and line[:1] in (" ", "+", "-"), line
+            hunk[4].append(line)
+    for path, hunks in files.items():
+        for o0, o1, n0, n1, lines in hunks:
+            assert sum(l[0] != "+" for l in lines) == o1 and sum(l[0] != "-" for l in lines) == n1, (path, o0, n0)
+    return files
+
+
+def post_image(hunks):
+    return "\n".join(l[1:] for h in hunks for l in h[4] if l[0] != "-") + "\n"
+
+
+def test_patch_adds_the_master_copies_and_keeps_the_seams():
+    """What the patch says on its own, without the reference tree: well-formed hunks, the new files it adds are the master
+    copies under integration/, and the seam and the three-phase run are in what it leaves in the patched files."""
+    files = patch_files()
+    for rel, master in (("lib/include/pctg/GamdpBridge.hpp", "GamdpBridge.hpp"), ("lib/src/pctg/GamdpBridge.cc", "GamdpBridge.cc")):
+        assert [(h[0], h[1]) for h in files[rel]] == [(0, 0)], rel    # a new file, one hunk
+        assert post_image(files[rel]) == open(os.path.join(ROOT, "integration", master)).read(), rel
+    bf = post_image(files["lib/src/pctg/BuildPctgFunctions.cc"])
+    assert "builder.alignMergeBlock(graph,*mb);" in bf and "prepareMergeLists" in bf and "finishPctg" in bf
+    tb = post_image(files["lib/src/pctg/ThreadedBuildPctg.cc"])
+    assert "ThreadedBuildPctg::runOnGpu()" in tb and "if( gamdp_bridge::ready() ) return this->runOnGpu();" in tb
+    assert "gamdp_bridge::init( masterCodes, slaveCodes );" in post_image(files["src/Merge.cc"])
+    assert "GamdpBridge.cc" in post_image(files["CMakeLists.txt"])
+
+
+def test_stub_library_refuses_every_call(tmp_path):
+    """integration/gamdp_stub.c, the stand-in library of make_l1_dump.sh for hosts without hipcc: it refuses, so the bridge
+    leaves gam-merge on its CPU path."""
+    so = tmp_path / "stub.so"
+    assert subprocess.run(["gcc", "-shared", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-o", str(so),
+                           os.path.join(ROOT, "integration", "gamdp_stub.c")]).returncode == 0
+    import ctypes
+    stub = ctypes.CDLL(str(so))
+    h = ctypes.c_void_p()
+    dev = (ctypes.c_int * 1)(0)
+    assert stub.gamdp_multi_create(dev, 1, ctypes.byref(h)) != 0 and not h.value
+
+
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "lib", "src", "pctg")), reason="reference tree not present")
 def test_patch_applies_cleanly_to_the_reference(tmp_path):
     tree = tmp_path / "gam-ngs"

@@ -1,90 +1,65 @@
-"""Pins oracle/gamdp_oracle.c against the reference's own code (oracle/_ref/libgamref.so).
+"""Pins oracle/gamdp_oracle.c against the reference's own code.
 
-Skipped where the reference build is unavailable (e.g. the GPU box); there the oracle is pinned
-by tests/test_oracle_golden.py against the committed vectors generated from the same reference.
+Every test feeds the oracle seeded inputs and compares its answers with what the reference returned for exactly those
+inputs, stored in tests/golden/oracle_vs_ref.json.gz (written by tests/golden/make_golden_vs_ref.py through
+oracle/_ref/libgamref.so), so the tests stand on the repository alone.  Where the reference build is present, its live
+answers are compared with the stored ones as well.
 """
+import ctypes
+import gzip
+import hashlib
+import json
+import os
 import random
+import zlib
 
 import pytest
 
 import _cases
 import _oracle as O
 
-pytestmark = pytest.mark.skipif(O.ref() is None, reason="oracle/_ref not built (no /root/reference)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_ref.json.gz")
+_golden = None
 
 
-def check_case(c):
-    a, b = O.encode(c["a"]), O.encode(c["b"])
-    args = (c["band"], c["begin_a"], c["end_a"], c["begin_b"], c["end_b"], c["fs"], c["fe"])
-    r, ops = O.oracle_align(a, b, *args)
-    if r.status == O.INVALID:
-        return "invalid"
-    rr, rops = O.ref_align(c["a"], c["b"], *args)
-    assert r.key() == O.ref_key(rr), (c, r.key(), O.ref_key(rr))
-    assert ops == rops, c
-    return r.status
+# ---- the inputs (tests/golden/make_golden_vs_ref.py records the reference's answers to exactly these) ----
+
+def random_cases(seed):
+    return _cases.cases(1000 + seed, 700)
 
 
-@pytest.mark.parametrize("seed", range(8))
-def test_random_cases_match_reference(seed):
-    stats = {}
-    for c in _cases.cases(1000 + seed, 700):
-        s = check_case(c)
-        stats[s] = stats.get(s, 0) + 1
-    assert stats.get(O.OK, 0) > 300
-    assert stats.get("invalid", 0) == 0
+def out_of_range_cases():
+    return _cases.cases(77, 3000, max_len=80, bands=(0, 1, 2, 5, 8))
 
 
-def test_out_of_range_cases_exist_and_match():
-    n_oor = 0
-    for c in _cases.cases(77, 3000, max_len=80, bands=(0, 1, 2, 5, 8)):
-        if check_case(c) == O.OUT_OF_RANGE:
-            n_oor += 1
-    assert n_oor >= 5
+def beyond_cases():
+    return _cases.beyond_cases(31, 1500)
 
 
-def test_begin_a_at_or_past_the_end_of_a_matches_reference():
-    """begin_a >= |a| (up to far past it): the reference's row bound wraps; outcomes are EMPTY / OUT_OF_RANGE only"""
-    stats = {}
-    for c in _cases.beyond_cases(31, 1500):
-        s = check_case(c)
-        stats[s] = stats.get(s, 0) + 1
-    assert stats.get(O.OUT_OF_RANGE, 0) > 100 and stats.get(O.EMPTY, 0) > 100, stats
-
-
-def test_medium_pairs_band150_and_512():
+def medium_cases():
     rng = random.Random(5)
+    out = []
     for n, band in ((3000, 150), (2500, 512), (4000, 20)):
         a, b = _cases.related_pair(rng, n, n_frac=0.01)
-        c = dict(a=a.encode(), b=b.encode(), band=band, begin_a=0, end_a=len(a) - 1, begin_b=0,
-                 end_b=len(b) - 1, fs=False, fe=False)
-        assert check_case(c) == O.OK
+        out.append(dict(a=a.encode(), b=b.encode(), band=band, begin_a=0, end_a=len(a) - 1, begin_b=0,
+                        end_b=len(b) - 1, fs=False, fe=False))
+    return out
 
 
-def test_iupac_and_lowercase_normalise_like_reference():
-    s = b"acgtnACGTNRYKMxX-*"
-    import ctypes
-    buf = ctypes.create_string_buffer(s, len(s))
-    O.ref().gamref_normalise(buf, len(s))
-    assert O.decode(O.encode(s)).encode() == buf.raw[:len(s)]
+ALIGN_GROUPS = dict([("random_%d" % s, (lambda s=s: random_cases(s))) for s in range(8)] +
+                    [("out_of_range", out_of_range_cases), ("beyond", beyond_cases), ("medium", medium_cases)])
+
+NORMALISE_INPUT = b"acgtnACGTNRYKMxX-*"
 
 
-def test_reverse_complement_matches_reference():
-    import ctypes
+def revcomp_inputs():
     rng = random.Random(3)
-    for n in (0, 1, 2, 3, 59, 60, 61, 120, 1001):
-        s = _cases.rand_seq(rng, n, 0.05).encode()
-        buf = ctypes.create_string_buffer(s, max(1, n))
-        O.ref().gamref_reverse_complement(buf, n)
-        codes = ctypes.create_string_buffer(O.encode(s), max(1, n))
-        O.oracle().gamdp_oracle_revcomp(codes, n)
-        assert O.decode(codes.raw[:n]).encode() == buf.raw[:n]
+    return [_cases.rand_seq(rng, n, 0.05).encode() for n in (0, 1, 2, 3, 59, 60, 61, 120, 1001)]
 
 
-@pytest.mark.parametrize("seed", range(3))
-def test_find_hits_matches_reference(seed):
+def find_hits_inputs(seed):
     rng = random.Random(4000 + seed)
-    n_nonempty = 0
+    out = []
     for _ in range(400):
         word = rng.choice([4, 8, 12, 20])
         la, lb = rng.randint(0, 200), rng.randint(0, 200)
@@ -101,8 +76,126 @@ def test_find_hits_matches_reference(seed):
         a, b = a.encode(), b.encode()
         a_s, a_e = rng.randint(0, max(0, len(a) // 3)), rng.randint(0, len(a) + 5)
         b_s, b_e = rng.randint(0, max(0, len(b) // 3)), rng.randint(0, len(b) + 5)
+        out.append((a, a_s, a_e, b, b_s, b_e, word))
+    return out
+
+
+def digest(items):
+    """sha256 of the inputs, stored next to the answers: a changed generator fails loudly instead of comparing
+    answers to other questions."""
+    h = hashlib.sha256()
+    for x in items:
+        h.update(repr(sorted(x.items()) if isinstance(x, dict) else x).encode())
+    return h.hexdigest()[:16]
+
+
+ALIGN_ARGS = ("band", "begin_a", "end_a", "begin_b", "end_b", "fs", "fe")
+
+
+def ref_answer(c):
+    """What the reference returns for one case: (key, crc32 of the edit string)."""
+    rr, rops = O.ref_align(c["a"], c["b"], *[c[k] for k in ALIGN_ARGS])
+    return list(O.ref_key(rr)), zlib.crc32(rops.encode())
+
+
+# ---- the stored answers ----
+
+def golden():
+    global _golden
+    if _golden is None:
+        with gzip.open(GOLDEN, "rt") as f:
+            _golden = json.load(f)
+    return _golden
+
+
+def stored(group, inputs):
+    g = golden()[group]
+    assert g["inputs_sha"] == digest(inputs), "the inputs of %s changed: regenerate %s" % (group, GOLDEN)
+    return g["answers"]
+
+
+def check_case(c, want):
+    a, b = O.encode(c["a"]), O.encode(c["b"])
+    r, ops = O.oracle_align(a, b, *[c[k] for k in ALIGN_ARGS])
+    if r.status == O.INVALID:
+        return "invalid"
+    key, crc = want
+    assert r.key() == tuple(key), (c, r.key(), key)
+    assert zlib.crc32(ops.encode()) == crc, c
+    if O.ref() is not None:
+        rr, rops = O.ref_align(c["a"], c["b"], *[c[k] for k in ALIGN_ARGS])
+        assert O.ref_key(rr) == tuple(key) and ops == rops, (c, O.ref_key(rr), key)
+    return r.status
+
+
+def check_group(group):
+    cases = ALIGN_GROUPS[group]()
+    return [check_case(c, w) for c, w in zip(cases, stored(group, cases))]
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_random_cases_match_reference(seed):
+    stats = {}
+    for s in check_group("random_%d" % seed):
+        stats[s] = stats.get(s, 0) + 1
+    assert stats.get(O.OK, 0) > 300
+    assert stats.get("invalid", 0) == 0
+
+
+def test_out_of_range_cases_exist_and_match():
+    assert sum(1 for s in check_group("out_of_range") if s == O.OUT_OF_RANGE) >= 5
+
+
+def test_begin_a_at_or_past_the_end_of_a_matches_reference():
+    """begin_a >= |a| (up to far past it): the reference's row bound wraps; outcomes are EMPTY / OUT_OF_RANGE only"""
+    stats = {}
+    for s in check_group("beyond"):
+        stats[s] = stats.get(s, 0) + 1
+    assert stats.get(O.OUT_OF_RANGE, 0) > 100 and stats.get(O.EMPTY, 0) > 100, stats
+
+
+def test_medium_pairs_band150_and_512():
+    assert check_group("medium") == [O.OK] * 3
+
+
+def ref_normalise(s):
+    buf = ctypes.create_string_buffer(s, len(s))
+    O.ref().gamref_normalise(buf, len(s))
+    return buf.raw[:len(s)].decode()
+
+
+def ref_revcomp(s):
+    buf = ctypes.create_string_buffer(s, max(1, len(s)))
+    O.ref().gamref_reverse_complement(buf, len(s))
+    return buf.raw[:len(s)].decode()
+
+
+def test_iupac_and_lowercase_normalise_like_reference():
+    want = stored("normalise", [NORMALISE_INPUT])[0]
+    if O.ref() is not None:
+        assert ref_normalise(NORMALISE_INPUT) == want
+    assert O.decode(O.encode(NORMALISE_INPUT)) == want
+
+
+def test_reverse_complement_matches_reference():
+    inputs = revcomp_inputs()
+    for s, want in zip(inputs, stored("revcomp", inputs)):
+        if O.ref() is not None:
+            assert ref_revcomp(s) == want
+        n = len(s)
+        codes = ctypes.create_string_buffer(O.encode(s), max(1, n))
+        O.oracle().gamdp_oracle_revcomp(codes, n)
+        assert O.decode(codes.raw[:n]) == want
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_find_hits_matches_reference(seed):
+    inputs = find_hits_inputs(seed)
+    n_nonempty = 0
+    for (a, a_s, a_e, b, b_s, b_e, word), want in zip(inputs, stored("find_hits_%d" % seed, inputs)):
+        if O.ref() is not None:
+            assert O.ref_find_hits(a, a_s, a_e, b, b_s, b_e, word) == want
         got = O.oracle_find_hits(O.encode(a), a_s, a_e, O.encode(b), b_s, b_e, word)
-        want = O.ref_find_hits(a, a_s, a_e, b, b_s, b_e, word)
         assert got == want, (a, b, a_s, a_e, b_s, b_e, word)
         n_nonempty += bool(want)
     assert n_nonempty > 50

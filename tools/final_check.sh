@@ -1,9 +1,9 @@
 #!/bin/bash
-# The round's closing check on the GPU box (from the repo root): the whole -m gpu suite, then the default bench line with its records.
+# The round's closing check on the GPU box (from the repo root): the whole -m gpu suite, then the bench line with all its records (--full).
 set -u
 OUT=gpurun_out/${1:-final}; mkdir -p $OUT
 (time python -m pytest tests -m gpu -x -q) > $OUT/gputests.log 2>&1; tail -4 $OUT/gputests.log
-python bench.py > $OUT/bench.log 2> $OUT/bench.err; tail -c 600 $OUT/bench.err
+python bench.py --full > $OUT/bench.log 2> $OUT/bench.err; tail -c 600 $OUT/bench.err
 python - $OUT/bench.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
