@@ -93,9 +93,6 @@ constexpr u32 LP_WALK_SIDE_BY_SIDE = 1;
 // the packed kernels keep the int32 tagged code for their top blocks (cells with pos <= 0), as before round 4: GAMDP_NO_PACKED_TOP=1 (A/B,
 // and a second way through every test)
 constexpr u32 LP_NO_PACKED_TOP = 2;
-// the strips of the direction-free ranges begin at multiples of the strip width, as before round 4 (Tk::sshift = 0): GAMDP_NO_STRIP_SHIFT=1
-// (A/B, and a second way through the tests)
-constexpr u32 LP_NO_STRIP_SHIFT = 4;
 // the packed top blocks only for wavefronts whose calls share begin_a and hold no force_start call, as in round 4 (the others keep the
 // int32 code): GAMDP_NO_PACKED_TOP_MIXED=1 (A/B, and a second way through the tests)
 constexpr u32 LP_NO_PACKED_TOP_MIXED = 16;
@@ -210,7 +207,7 @@ GAMDP_HD inline bool call_touches_n(const u32* pre_a, int64_t alen, bool a_rc, u
            npre_window_has_n(pre_b, blen, b_rc, b_off, begin_b - margin, begin_b + X - 1 + margin);
 }
 
-// ---- the main chain of a merge block on the device (k_chain, gamdp_kernel.hip) -----------------------------------------
+// ---- the main chain of a merge block on the device (k_chain2, gamdp_kernel.hip) -----------------------------------------
 // One wavefront takes a merge block through alignBlocks' serial chain (PctgBuilder.cc:1617-1708: block k starts where block
 // k-1's last match ended, plus the gap between the blocks) and the orientation retry of findBestAlignment (:1420-1509)
 // without returning to the host: the next window, the pre-checks, is_good(vector) (:1711-1724) are integer arithmetic.  Every
@@ -268,27 +265,33 @@ struct ChainParams {
     ChainWin* host_win;
     u32 skew_call;                 // diagnostics build only (GAMDP_DIAG_CHAIN_SKEW=k): the device starts call k of every first attempt one base late on the slave; ~0u = off
     int32_t n_margin;              // bases added on either side of a call's window when it is tested for N (64; the diagnostics build can shrink it below zero: GAMDP_DIAG_N_WINDOW_SHRINK, the replay must notice)
-    u32 n_by_contig;               // 1: every call of a chain whose contigs hold N runs the N-aware cells (GAMDP_N_BY_CONTIG=1, GAMDP_DIAG_FORCE_N)
-    u32 two_waves;                 // k_chain2: a workgroup of one filling and several walking wavefronts with chain_slots_per_workgroup() scratch slots of slot_words each
+    u32 n_by_contig;               // 1: every call of a chain whose contigs hold N runs the N-aware cells (diagnostics build: GAMDP_DIAG_FORCE_N)
 };
 int launch_chain(const ChainParams& p, bool has_n, unsigned n_workgroups, void* stream);   // returns hipError_t as int
 int chain_slots_per_workgroup();   // scratch slots a k_chain2 workgroup goes round (1 + its walker wavefronts)
 
-int kernel_cols(int kid);
-const char* kernel_name(int kid);      // the instantiation as rocprofv3 prints it, e.g. "k_align_o<19,15>"
-bool kernel_n_aware(int kid);
-bool kernel_dirfree(int kid);          // its fast blocks can run without directions (when the launch provides ckpt_off / bnd_off)
-int kernel_dir_block_words(int kid);  // words per block (16 row-times) of a task's direction image
+// What the host needs to know of a kernel variant: one row per KernelId (kernel_info, gamdp_kernel.hip, next to the layout
+// constants the rows are built from).
+struct KernelInfo {
+    KernelId id;
+    const char* name;        // the instantiation as rocprofv3 prints it, e.g. "k_align_o<19,15>"
+    int cols;                // band columns per lane (K_WIDE: 0)
+    u32 band;                // the one band a tuned kernel takes (pick_kernel): 512 or 150; 0 = any band
+    int tasks_per_wave;      // each task has its own side buffers in a slot
+    int waves_per_cu;        // occupancy: resident waves (K_WIDE: workgroups) per CU
+    bool n_aware;
+    bool dirfree;            // its fast blocks can run without directions (when the launch provides ckpt_off / bnd_off)
+    bool two_dir_images;     // a slot holds two direction images (the pairs of tasks / of quads)
+    int dir_block_words;     // words per block (16 row-times) of a task's direction image
+    int ckpt_words;          // words per group (4 blocks) of the live-row store of the direction-free kernels
+    int bnd_words;           // boundary words per block of the direction-free kernels
+    void (*kernel)(LaunchParams);   // nullptr for K_WIDE (launch_wide)
+};
+extern const KernelInfo kernel_info[K_COUNT];
+
 // launches on `stream`; returns hipError_t as int
 int launch_align(int kid, const LaunchParams& p, unsigned n_slots, unsigned dyn_lds, void* stream);
 int launch_wide(const LaunchParams& p, unsigned n_slots, void* stream);   // K_WIDE (gamdp_wide.hip): n_slots workgroups
-unsigned wide_static_lds();
 constexpr int WIDE_WORKGROUPS_PER_CU = 8;
-unsigned kernel_static_lds(int kid);  // static LDS bytes of a variant
-// occupancy hint: resident waves per CU for this variant
-int kernel_waves_per_cu(int kid);
-int kernel_bnd_words(int kid);  // boundary words per block of the direction-free kernels
-int kernel_ckpt_words(int kid);      // words per group (4 blocks) of the live-row store of the direction-free kernels
-int kernel_tasks_per_wave(int kid);
 
 }  // namespace gamdp

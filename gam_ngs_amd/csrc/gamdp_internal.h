@@ -19,12 +19,42 @@ constexpr int64_t FORCE_MAXGAP_ = 10;  // FORCE_MAXGAP_LEN, banded_smith_waterma
 
 struct Ctx;
 
-// diagnostics switches (gamdp_host.cpp): all false in the product build except `timing`
+// Diagnostics switches (environment, read once per process: gamdp_host.cpp).  The product build reads GAMDP_DIAG_TIMING alone;
+// everything else keeps its default there.
 struct Diag {
-    bool build = false;  // compiled with -DGAMDP_DIAG
-    bool timing = false, skip_traceback = false, no_dirfree = false, count_mat = false, force_n = false;
+    bool build = false;            // compiled with -DGAMDP_DIAG
+    bool timing = false;           // GAMDP_DIAG_TIMING: host-side timing lines on stderr (results untouched)
+    bool skip_traceback = false;   // GAMDP_DIAG_SKIP_TRACEBACK: no walk (results invalid)
+    bool no_dirfree = false;       // GAMDP_DIAG_NO_DIRFREE: a direction per cell everywhere
+    bool count_mat = false;        // GAMDP_DIAG_COUNT_MAT: n_match := number of materialise() calls (results invalid)
+    bool force_n = false;          // GAMDP_DIAG_FORCE_N: N-free input through the N-aware kernels
+    int64_t n_window_shrink = 0;   // GAMDP_DIAG_N_WINDOW_SHRINK=k: the N windows k bases too small on either side (fault injection)
+    u32 chain_skew = ~0u;          // GAMDP_DIAG_CHAIN_SKEW=k: the device chains start call k one slave base late (fault injection)
 };
 const Diag& diag();
+
+// Product-library switches (environment, read once per process: gamdp_host.cpp).  None changes a result: each takes the planner
+// to the other side of a threshold that real inputs also reach (A/B measurements, and a second way through the tests).
+struct Tuning {
+    bool no_merge_n = false;            // GAMDP_NO_MERGE_N (or GAMDP_QUAD_MIN set): a small batch keeps its N-free and N-aware band-150 launches apart
+    long quad_min = -1;                 // GAMDP_QUAD_MIN=n: band-150 groups of n tasks or more take the multi-task kernels (-1: by the chip's wave slots)
+    size_t octo_min_rows = 0;           // GAMDP_OCTO_MIN_ROWS=r (0..500 000): the eight-task kernel only for tasks of r rows or more on average
+    bool no_pair = false;               // GAMDP_NO_PAIR: neither the two-task (band 512) nor the eight-task (band 150) kernel
+    bool no_aux_launch = false;         // GAMDP_NO_AUX_LAUNCH: a batch's small launch after its big one instead of beside it
+    u64 side_walk_rounds = 2;           // GAMDP_SIDE_WALK_ROUNDS=r (0..1 000 000): two-task launches of up to r rounds walk side by side
+    bool no_packed_top = false;         // GAMDP_NO_PACKED_TOP: int32 top blocks everywhere
+    bool no_packed_top_mixed = false;   // GAMDP_NO_PACKED_TOP_MIXED: int32 top blocks for wavefronts whose calls differ in begin_a or force their start
+    int walk_prio = -1;                 // GAMDP_WALK_PRIO=0..3 (& 3): issue priority of the walk phase (-1: by the launch's rounds)
+    bool no_prio = false;               // GAMDP_NO_PRIO: no longest-remaining-first priority
+    long chunk_min = -1;                // GAMDP_CHUNK_MIN=n: batches of n calls or more go in pieces, whatever their size (-1: by the batch's shape)
+    double chunk_min_rounds = -1;       // GAMDP_CHUNK_MIN_ROUNDS=r (0..1000): rounds a piece must keep the chip busy (-1: 3 or 2.5)
+    size_t chunk_first_div = 8;         // GAMDP_CHUNK_FIRST_DIV=d (4..1024): the first piece is 1/d of the batch
+    bool l1_rounds = false;             // GAMDP_L1_ROUNDS: every merge-block call through the round loop (no device chains)
+    bool l1_no_twins = false;           // GAMDP_L1_NO_TWINS: no twin workgroups for the device chains
+    int l1_cohorts = 0;                 // GAMDP_L1_COHORTS=k (1..16): cohorts of a merge-block call (0: by its size)
+    size_t l1_cohort_min = 48;          // GAMDP_L1_COHORT_MIN=m (1 or more): merge blocks per cohort at least
+};
+const Tuning& tuning();
 
 // banded_smith_waterman.cc:90-132 on plain numbers: GAMDP_ST_OK = has to run on the GPU, else the final status
 int preflight(u64 alen, u64 blen, u64 band, u64 begin_a, u64 end_a, u64 begin_b, u64 end_b, bool fs, bool fe,
@@ -103,6 +133,25 @@ struct Prepared {
     u64 dir_words;
 };
 
+// One launch of a batch call, as the planner lays it out (Ctx::align_plan)
+struct Launch {
+    int kid;
+    u32 first, count;             // its tasks in the staged task list (count: padded to whole wavefronts)
+    u64 slot_words, dir_words;
+    u32 ypad, n_slots, dyn_lds;
+    u64 ckpt_off, bnd_off;
+    u32 band_max;
+    u64 scratch_off = 0;          // where its slots begin in the scratch arena
+    bool aux = false;             // runs beside the other launch, on aux_stream
+};
+// The launches of a batch call, the tasks of each (in launch order) and the padded task count of all
+struct Plan {
+    std::vector<Launch> launches;
+    std::vector<std::vector<u32>> items;
+    u64 n_host_tasks = 0;
+};
+struct AlignCall;   // one align() call under way (gamdp_host.cpp)
+
 struct Ctx {
     int device = -1;
     int n_cu = 0;
@@ -162,6 +211,7 @@ struct Ctx {
     std::vector<u32> w_rows;     // ... and its rows
     std::vector<std::vector<u32>> w_groups;            // the tasks of the batch under way by kernel
     std::vector<u32> w_sort_tmp; std::vector<size_t> w_sort_count;   // scratch of the planner's sort
+    Plan w_plan;                                       // the launches of the batch under way
 
     // buffers of the merge-block chain kernel (gamdp_l1.cpp), kept between calls
     void* d_chain = nullptr; u64 cap_chain = 0;    // device: DevMB[] | DevBlk[] | DevResult audit[] | ChainOut[] | cursor
@@ -186,6 +236,15 @@ struct Ctx {
     u32 chain_epoch = 0;
 
     int align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_ops* ops);
+    // the steps of align(), in the order they run (gamdp_host.cpp)
+    int align_check(const TaskSrc& tasks, size_t n);
+    void align_prepare(AlignCall& a);
+    void align_group(AlignCall& a);
+    int align_plan(u64 arena_call);
+    int align_stage(const AlignCall& a);
+    int align_scratch(u64 arena_call);
+    int align_run(AlignCall& a);
+    void align_collect(AlignCall& a);
     int align(const ITask* tasks, size_t n, gamdp_result* out, const gamdp_ops* ops) { TaskSrc s; s.it = tasks; return align(s, n, out, ops); }
     int align(const std::vector<ITask>& tasks, gamdp_result* out, const gamdp_ops* ops) { return align(tasks.data(), tasks.size(), out, ops); }
     ~Ctx();

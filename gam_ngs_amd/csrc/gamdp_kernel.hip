@@ -150,7 +150,7 @@ __device__ __forceinline__ void fill_task(const DevTask& dt, const LaunchParams&
     t.ckpt = (gptr)(slot + p.ckpt_off);
     t.bnd = (gptr)(slot + p.bnd_off);
     t.df_lo = t.df_hi = t.df_top = t.sshift = 0;
-    if constexpr (DIRFREE_OK<CE, C, HASN>) t.sshift = (p.flags & LP_NO_STRIP_SHIFT) ? 0 : strip_shift<C, Strip<64>::SL>(dt.band);
+    if constexpr (DIRFREE_OK<CE, C, HASN>) t.sshift = strip_shift<C, Strip<64>::SL>(dt.band);
     {
         const int64_t rel = t.end_a - t.begin_a + t.band;  // may be negative
         t.eaRel = (int)min(max(rel, (int64_t)-(1 << 30)), (int64_t)(1 << 30));
@@ -416,7 +416,7 @@ __device__ __forceinline__ void run_pair(const LaunchParams& p, const u32 qi, u3
     u32* const sideA = slot + 2 * p.dir_words;
     Tk ta = make_tk(da, p, slot, sideA, slot);
     Tk tb = make_tk(db, p, slot + p.dir_words, sideA + 4u * p.ypad, slot);
-    ta.sshift = tb.sshift = (p.flags & LP_NO_STRIP_SHIFT) ? 0 : strip_shift<C, Strip<64, true>::SL>(max(ta.band, tb.band));
+    ta.sshift = tb.sshift = strip_shift<C, Strip<64, true>::SL>(max(ta.band, tb.band));
     const Plan pa = make_plan<C>(ta), pb = make_plan<C>(tb);
     // the packed range: fast blocks of BOTH tasks, whole groups of 4 blocks, at least one tagged fast block in front of it
     // for either task (what a lane receives at a group start must be its neighbour's plain last column)
@@ -514,7 +514,7 @@ __device__ __forceinline__ void run_quad(const LaunchParams& p, const u32 qi, u3
     t.ckpt = (gptr)(slot + p.ckpt_off);
     t.bnd = (gptr)(slot + p.bnd_off);
     t.df_lo = t.df_hi = t.df_top = 0;
-    t.sshift = (p.flags & LP_NO_STRIP_SHIFT) ? 0 : strip_shift<C, Strip<LPT>::SL>(uni(quad_max(dt.band)));   // one for the wavefront: its lanes share the boundary slots
+    t.sshift = strip_shift<C, Strip<LPT>::SL>(uni(quad_max(dt.band)));   // one for the wavefront: its lanes share the boundary slots
     {
         const int64_t rel = t.end_a - t.begin_a + t.band;  // may be negative
         t.eaRel = (int)min(max(rel, (int64_t)-(1 << 30)), (int64_t)(1 << 30));
@@ -612,7 +612,7 @@ __device__ __forceinline__ void run_octo(const LaunchParams& p, const u32 qi, u3
     u32* const side = slot + 2 * p.dir_words;
     Tk ta = make_tk(da, p, slot, side + (u64)sub * 4u * p.ypad, slot);
     Tk tb = make_tk(db, p, slot + p.dir_words, side + (u64)(4 + sub) * 4u * p.ypad, slot);
-    ta.sshift = tb.sshift = (p.flags & LP_NO_STRIP_SHIFT) ? 0 : strip_shift<C, Strip<QL, true>::SL>(uni(quad_max(max(ta.band, tb.band))));   // one for the wavefront
+    ta.sshift = tb.sshift = strip_shift<C, Strip<QL, true>::SL>(uni(quad_max(max(ta.band, tb.band))));   // one for the wavefront
     const Plan pa = make_plan<C>(ta), pb = make_plan<C>(tb);   // per lane
     const int nA = quad_max(pa.nblk), nB = quad_max(pb.nblk);
     int lo = (quad_max(max(pa.b0, pb.b0)) + 1 + 3) & ~3, mid = quad_min(min(pa.b1, pb.b1)) & ~3, hi = quad_min(min(pa.b2, pb.b2)) & ~3;
@@ -699,160 +699,10 @@ __global__ __launch_bounds__(64, GAMDP_WAVES_PER_SIMD) void k_align_q(const Laun
     }
 }
 
-// ---- the main chain of a merge block, one wavefront per merge block (structures and rationale: gamdp_dev.h) --------------
-// Band 150 only (gam-merge's live band): the one-task kernel shape k_align<5, 0, HASN> run call after call by the same
-// wavefront.  Everything but the DP itself is wave-uniform integer arithmetic that restates gamdp_l1.cpp's Machine for the
-// MAIN phase (PctgBuilder.cc:1420-1509, 1617-1724); the host replays that machine over the audit list afterwards.
-template <bool HASN>
-__device__ __forceinline__ void run_chain(const ChainParams& cp, const LaunchParams& p, const u32 mi, u32* slot, const int lane)
-{
-    const u32 t_begin = diag_clock();
-    const u32 hw_me = diag_hw_id(), hw_other = 0, te0 = 0, te1 = 0, tb2 = 0;   // XCC_ID | HW_ID (timing diagnostics)
-    const DevMB* mb = unip(cp.mbs + mi);
-    const u64 mlen = (u64)uni64((int64_t)mb->mlen), slen = (u64)uni64((int64_t)mb->slen);
-    const u64 m_start = (u64)uni64((int64_t)mb->m_start), s_start = (u64)uni64((int64_t)mb->s_start), s_end = (u64)uni64((int64_t)mb->s_end);
-    const u64 align_thr = (u64)uni64((int64_t)mb->align_thr);
-    const u32 first_blk = (u32)uni((int)mb->first_blk), n = (u32)uni((int)mb->n_blocks), audit_first = (u32)uni((int)mb->audit_first);
-    const u32 band = cp.band, max_x = (u32)uni((int)mb->max_x);
-    bool try_rev = uni((int)mb->try_rev) != 0;
-    auto frame_len = [](const int32_t b, const int32_t e) -> int32_t { return e < b ? 0 : e - b + 1; };   // Frame.cc:124-127
-    u32 n_dp = 0, state = 1;
-    for (int attempt = 0;; ) {
-        int64_t cur_ms = (int64_t)m_start;
-        int64_t cur_ss = (int64_t)(try_rev ? slen - s_end - 1 : s_start);   // reverse_complement maps (start,end) -> (|s|-end-1, |s|-start-1), :1446-1448
-        u64 last_a = 0, last_b = 0, sumlen = 0;
-        bool all_good = true, thrown = false, overflow = false;
-        int rows_left = uni((int)mb->rows);
-        for (u32 k = 0; k < n; ++k) {
-            const DevBlk* bk = unip(cp.blks + first_blk + k);
-            const int32_t cm_b = uni(bk->m_begin), cm_e = uni(bk->m_end), cs_b = uni(bk->s_begin), cs_e = uni(bk->s_end);
-            const int32_t ml = frame_len(cm_b, cm_e), sl = frame_len(cs_b, cs_e);
-            if (k > 0) {  // :1660-1667
-                const int32_t pm_b = uni(bk[-1].m_begin), pm_e = uni(bk[-1].m_end), ps_b = uni(bk[-1].s_begin), ps_e = uni(bk[-1].s_end);
-                const int32_t mgap = pm_b <= cm_b ? (cm_b - pm_e - 1) : (pm_b - cm_e - 1);
-                const int32_t sgap = ps_b <= cs_b ? (cs_b - ps_e - 1) : (ps_b - cs_e - 1);
-                cur_ms = (int64_t)(last_a + (u64)(int64_t)mgap); if (cur_ms < 0) cur_ms = 0;
-                cur_ss = (int64_t)(last_b + (u64)(int64_t)sgap); if (cur_ss < 0) cur_ss = 0;
-            }
-#ifdef GAMDP_DIAG
-            if (attempt == 0 && k == cp.skew_call) ++cur_ss;   // fault injection (GAMDP_DIAG_CHAIN_SKEW): the host's replay must notice
-#endif
-            const u64 begin_a = (u64)cur_ms, end_a = (u64)(cur_ms + ml - 1), begin_b = (u64)cur_ss, end_b = (u64)(cur_ss + sl - 1);
-            // the call ends when its longest chain does: wavefronts that share a SIMD yield to the one with the most rows left
-            set_prio_by_remaining(rows_left, (int)cp.max_rows);
-            rows_left -= sl;
-            u64 X = 0, cells = 0;
-            const int st = preflight_hd(mlen, slen, band, begin_a, end_a, begin_b, end_b, false, false, &X, &cells);
-            const u32 idx = audit_first + n_dp;
-            if (st == 0 && X > (u64)max_x) { overflow = true; break; }   // (the host sized the slot for the chain's longest slave frame: never, unless its arithmetic and this one differ)
-            // N by window: the cell of THIS call (HASN: one of the chain's contigs holds an N somewhere)
-            bool call_n = false;
-            if constexpr (HASN)
-                call_n = st == 0 && (cp.n_by_contig != 0 || call_touches_n(unip(mb->npre_a), (int64_t)mlen, false, 0, unip(mb->npre_b), (int64_t)slen, try_rev, 0, (int64_t)band,
-                                                                            (int64_t)begin_a, (int64_t)begin_b, (int64_t)X, (int64_t)cp.n_margin));
-            if (lane == 0) { ChainWin w; w.begin_a = begin_a; w.end_a = end_a; w.begin_b = begin_b; w.end_b = end_b; w.X = (u32)X; w.info = (try_rev ? 1u : 0u) | (call_n ? 2u : 0u) | ((u32)st << 8); cp.win[idx] = w; }
-#ifdef GAMDP_DIAG
-            if (lane == 0) { ChainOut o; o.n_dp = n_dp; o.state = 0x1000u | ((u32)st << 16) | (k << 20); cp.out[mi] = o; }   // progress marker (overwritten at the end)
-#endif
-            DevResult r;
-            if (st != 0) {   // settled without a DP, exactly as the host settles it (Ctx::align)
-                r.begin_a = r.begin_b = r.score = 0; r.n_match = r.length = 0;
-                r.first_a = r.first_b = r.last_a = r.last_b = 0;
-                r.flags = (u32)st << 8;
-                if (lane == 0) cp.audit[idx] = r;
-            } else {
-                DevTask dt;
-                dt.a2 = mb->a2; dt.an = mb->an;
-                dt.b2 = try_rev ? mb->b2rc : mb->b2; dt.bn = try_rev ? mb->bnrc : mb->bn;
-                dt.a_base = 0; dt.b_base = 0;
-                dt.end_a = (int64_t)(end_a < (1ull << 40) ? end_a : (1ull << 40));
-                dt.alen = (int32_t)mlen; dt.blen = (int32_t)slen;
-                dt.begin_a = (int32_t)begin_a; dt.begin_b = (int32_t)begin_b;
-                dt.X = (int32_t)X; dt.band = (int32_t)band;
-                dt.flags = 0; dt.res_idx = idx; dt.ops_off = 0; dt.ops_cap = 0;
-                if constexpr (HASN) {
-                    if (call_n) run_task<5, 0, true>(dt, p, slot, lane, false);
-                    else run_task<5, 0, false>(dt, p, slot, lane, false);
-                } else run_task<5, 0, false>(dt, p, slot, lane, false);
-#ifdef GAMDP_DIAG
-                if (lane == 0) { ChainOut o; o.n_dp = n_dp; o.state = 0x2000u | (k << 20); cp.out[mi] = o; }
-#endif
-                // the record lane 0 just wrote: wait until L2 has it, drop this CU's L1 lines, read it back (wave-uniform)
-                __builtin_amdgcn_s_waitcnt(0);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                const DevResult* rp = cp.audit + idx;
-                r.flags = (u32)uni((int)rp->flags); r.n_match = (u32)uni((int)rp->n_match); r.length = (u32)uni((int)rp->length);
-                r.last_a = uni(rp->last_a); r.last_b = uni(rp->last_b);
-            }
-            ++n_dp;
-#ifdef GAMDP_DIAG
-            if (lane == 0) { ChainOut o; o.n_dp = n_dp; o.state = 0x3000u | (k << 20) | (r.flags & 0xf00u); cp.out[mi] = o; }
-#endif
-            const u32 status = r.flags >> 8;
-            if (status == ST_OUT_OF_RANGE || status == 3u) { thrown = true; break; }   // the reference throws / undefined: the machine stops (finish_bad)
-            if (status == ST_OK) {
-                // homology >= 95 <=> n_match * 100 >= 95 * length (the quotient the host compares is correctly rounded and the
-                // distance of n_match * 100 / length from 95 is either 0 or at least 1 / length: no rounding across 95)
-                if (r.length == 0 || (u64)r.n_match * 100u < 95ull * (u64)r.length) all_good = false;
-                sumlen += r.length;
-                last_a = (u64)(int64_t)r.last_a; last_b = (u64)(int64_t)r.last_b;
-            } else {   // EMPTY: MyAlignment(), homology 0, last match (0, 0)
-                all_good = false;
-                last_a = last_b = 0;
-            }
-        }
-#ifdef GAMDP_DIAG
-        if (lane == 0) { ChainOut o; o.n_dp = n_dp; o.state = 0x4000u | (all_good ? 1u : 0u) | (thrown ? 2u : 0u) | ((sumlen >= align_thr) ? 4u : 0u); cp.out[mi] = o; }
-#endif
-        if (overflow) { state = 3; break; }
-        if (thrown) { state = 2; break; }
-        if (all_good && sumlen >= align_thr) { state = try_rev ? 0x100u : 0u; break; }   // is_good(vector), :1711-1724
-        if (++attempt == 2) { state = 1; break; }                                          // :1512
-        try_rev = !try_rev;
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    if (lane == 0) { ChainOut o; o.n_dp = n_dp; o.state = state; o.t_begin = t_begin; o.t_end = diag_clock(); o.hw = hw_me; o.hw_twin = hw_other; o.t_end_att[0] = te0; o.t_end_att[1] = te1; o.t_begin2 = tb2; o.pad = 0; cp.out[mi] = o; }
-    // hand the chain to the host: records and ChainOut into its pinned mirror, then the flag
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    {
-        const u32* src = reinterpret_cast<const u32*>(cp.audit + audit_first);
-        u32* dst = reinterpret_cast<u32*>(cp.host_audit + audit_first);
-        const u32 nw = n_dp * (u32)(sizeof(DevResult) / sizeof(u32));
-        for (u32 w = (u32)lane; w < nw; w += 64) dst[w] = src[w];
-        const u32* wsrc = reinterpret_cast<const u32*>(cp.win + audit_first);
-        u32* wdst = reinterpret_cast<u32*>(cp.host_win + audit_first);
-        const u32 nww = n_dp * (u32)(sizeof(ChainWin) / sizeof(u32));
-        for (u32 w = (u32)lane; w < nww; w += 64) wdst[w] = wsrc[w];
-        if (lane == 0) { ChainOut o; o.n_dp = n_dp; o.state = state; o.t_begin = t_begin; o.t_end = diag_clock(); o.hw = hw_me; o.hw_twin = hw_other; o.t_end_att[0] = te0; o.t_end_att[1] = te1; o.t_begin2 = tb2; o.pad = 0; cp.host_out[mi] = o; }
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope: every lane's stores above are out before the flag
-    if (lane == 0) __hip_atomic_store(cp.host_done + mi, cp.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// One workgroup (= one wavefront) per merge block, no work queue: the grid is the list (longest chains first), every workgroup
-// owns the scratch slot of its index.  (A persistent-wavefront version with an atomic cursor hung on the device after the last
-// call of every chain -- its loop exit had been compiled lane-wise; not pursued: a merge-block call has far fewer merge blocks
-// than the scratch arena has room for slots, and the host launches in pieces when it does not.)
-// HASN = false: a launch in which no contig holds an N; true: every chain picks its cells by its own two contigs.
-template <bool HASN>
-__global__ __launch_bounds__(64, GAMDP_WAVES_PER_SIMD) void k_chain(const ChainParams cp)
-{
-    const int lane = threadIdx.x;
-    const u32 mi = cp.first_mb + blockIdx.x;
-    const DevMB* const mbp = unip(cp.mbs + mi);
-    u32* slot = cp.scratch + (u64)uni64((int64_t)mbp->slot_off[0]);
-    LaunchParams p;
-    p.tasks = nullptr; p.n_tasks = 0; p.cursor = nullptr; p.results = cp.audit; p.ops_buf = nullptr;
-    p.scratch = cp.scratch; p.slot_words = (u64)uni64((int64_t)mbp->slot_words); p.dir_words = (u64)uni64((int64_t)mbp->dir_words); p.ypad = cp.ypad;
-    p.ckpt_off = (u64)uni64((int64_t)mbp->ckpt_off); p.bnd_off = (u64)uni64((int64_t)mbp->bnd_off); p.flags = 0; p.prio_R = 0; p.prio_from = 0; p.stats = nullptr;
-    if constexpr (HASN) {
-        if (uni((int)cp.mbs[mi].has_n) != 0) run_chain<true>(cp, p, mi, slot, lane);
-        else run_chain<false>(cp, p, mi, slot, lane);
-    } else run_chain<false>(cp, p, mi, slot, lane);
-}
-
-// ---- the same chain by two wavefronts: one fills, one walks ------------------------------------------------------------------
+// ---- the main chain of a merge block, one filling and CH_NW walking wavefronts (structures and rationale: gamdp_dev.h) ------
+// Band 150 only (gam-merge's live band): the one-task kernel shape k_align<5, 0, HASN> run call after call.  Everything but the DP
+// itself is wave-uniform integer arithmetic that restates gamdp_l1.cpp's Machine for the MAIN phase (PctgBuilder.cc:1420-1509,
+// 1617-1724); the host replays that machine over the audit list afterwards.
 // A lone wavefront issues one instruction every ~5 cycles whatever it does, and a fifth of a chain's instructions are the end-cell
 // search and the walk (measured, tools/lab_r03/r03_probe8.sh: 50 kb band-150 calls one per CU, 3.81 ms fill + 1.00 ms walk).  The next
 // call of a chain needs one thing from the walk of this one: the last match (PctgBuilder.cc:1660-1667), which is the FIRST match
@@ -1076,139 +926,55 @@ int launch_chain(const ChainParams& p, bool has_n, unsigned n_slots, void* strea
 {
     ChainParams cp = p;
     void* args[] = {&cp};
-    if (cp.two_waves) {
-        const void* f = has_n ? (const void*)k_chain2<true> : (const void*)k_chain2<false>;
-        return (int)hipLaunchKernel(f, dim3(n_slots), dim3(64 * (1 + CH_NW)), args, 0, static_cast<hipStream_t>(stream));
-    }
-    const void* f = has_n ? (const void*)k_chain<true> : (const void*)k_chain<false>;
-    return (int)hipLaunchKernel(f, dim3(n_slots), dim3(64), args, 0, static_cast<hipStream_t>(stream));
+    const void* f = has_n ? (const void*)k_chain2<true> : (const void*)k_chain2<false>;
+    return (int)hipLaunchKernel(f, dim3(n_slots), dim3(64 * (1 + CH_NW)), args, 0, static_cast<hipStream_t>(stream));
 }
 
-int kernel_cols(int kid)
-{
-    switch (kid) {
-    case K_C17_CE4: case K_C17_CE4_N: case K_GEN_C17: return 17;
-    case K_C5_CE0: case K_C5_CE0_N: case K_GEN_C5: return 5;
-    case K_Q19_CE15: case K_Q19_CE15_N: return 19;
-    case K_P17_CE4: return 17;
-    case K_O19_CE15: return 19;
-    case K_GEN_C2: return 2;
-    case K_GEN_C3: return 3;
-    case K_GEN_C9: return 9;
-    default: return 0;
-    }
-}
-
-const char* kernel_name(int kid)
-{
-    switch (kid) {
-    case K_C17_CE4:    return "k_align<17,4,false>";
-    case K_C17_CE4_N:  return "k_align<17,4,true>";
-    case K_C5_CE0:     return "k_align<5,0,false>";
-    case K_C5_CE0_N:   return "k_align<5,0,true>";
-    case K_P17_CE4:    return "k_align_p<17,4>";
-    case K_O19_CE15:   return "k_align_o<19,15>";
-    case K_Q19_CE15:   return "k_align_q<19,15,false>";
-    case K_Q19_CE15_N: return "k_align_q<19,15,true>";
-    case K_GEN_C2:     return "k_align<2,-1,true>";
-    case K_GEN_C3:     return "k_align<3,-1,true>";
-    case K_GEN_C5:     return "k_align<5,-1,true>";
-    case K_GEN_C9:     return "k_align<9,-1,true>";
-    case K_GEN_C17:    return "k_align<17,-1,true>";
-    case K_WIDE:       return "k_align_w";
-    default:           return "?";
-    }
-}
-bool kernel_n_aware(int kid)
-{
-    switch (kid) {
-    case K_C17_CE4: case K_C5_CE0: case K_P17_CE4: case K_O19_CE15: case K_Q19_CE15: return false;
-    default: return true;
-    }
-}
-
-int kernel_waves_per_cu(int kid) { return kid == K_WIDE ? WIDE_WORKGROUPS_PER_CU : 4 * ((kid == K_P17_CE4 || kid == K_O19_CE15) ? GAMDP_PAIR_WAVES_PER_SIMD : GAMDP_WAVES_PER_SIMD); }
-int kernel_tasks_per_wave(int kid) { return (kid == K_Q19_CE15 || kid == K_Q19_CE15_N) ? QT : (kid == K_P17_CE4 ? 2 : (kid == K_O19_CE15 ? 2 * QT : 1)); }
-// words per block of the direction image: lane major (LANE_WORDS per lane) in the direction-free kernels
-static_assert(DIRFREE_OK<4, 17, false> && DIRFREE_OK<4, 17, true> && DIRFREE_OK<15, 19, false> && DIRFREE_OK<15, 19, true> &&
-                  !DIRFREE_OK<0, 5, false> && !DIRFREE_OK<0, 5, true> && DIRFREE_OK<-1, 17, true> && DIRFREE_OK<-1, 9, true> && !DIRFREE_OK<-1, 5, true> && !DIRFREE_OK<-1, 3, true>,
-              "kernel_dir_block_words() below lists the direction-free kernels by id: keep it in step with DIRFREE_OK");
-int kernel_dir_block_words(int kid)
-{
-    switch (kid) {
-    case K_C17_CE4: case K_C17_CE4_N: case K_P17_CE4: return IMG_WORDS<17, true>;
-    case K_Q19_CE15: case K_Q19_CE15_N: case K_O19_CE15: return IMG_WORDS<19, true>;
-    case K_GEN_C17: return IMG_WORDS<17, true>;
-    case K_GEN_C9: return IMG_WORDS<9, true>;
-    case K_WIDE: return 1;   // (no direction image: the slot holds the band matrix itself, sized by the host)
-    default: return kernel_cols(kid) * 64;
-    }
-}
-int kernel_ckpt_words(int kid)
-{
-    if (kid == K_P17_CE4) return (int)PairFmt<17, 64>::CK_WORDS;
-    if (kid == K_O19_CE15) return (int)PairFmt<19, QL>::CK_WORDS;
-    return kernel_dir_block_words(kid);
-}
-
-bool kernel_dirfree(int kid)
-{
-    switch (kid) {
-    case K_C17_CE4: case K_C17_CE4_N: case K_P17_CE4: case K_O19_CE15: case K_Q19_CE15: case K_Q19_CE15_N: case K_GEN_C9: case K_GEN_C17: return true;
-    default: return false;
-    }
-}
-
-int kernel_bnd_words(int kid)
-{
-    if (kid == K_P17_CE4) return (int)PairFmt<17, 64>::BND_WORDS;
-    if (kid == K_O19_CE15) return (int)PairFmt<19, QL>::BND_WORDS;
-    return kernel_tasks_per_wave(kid) > 1 ? (int)Strip<QL>::BND_WORDS : (int)Strip<64>::BND_WORDS;
-}
-
+// One row per kernel variant.  Waves per CU: what the kernels are register-budgeted for (K_WIDE: workgroups).  Direction-block
+// words: lane major (LANE_WORDS per lane) in the direction-free kernels, C*64 in the others; K_WIDE keeps no direction image (its
+// slot holds the band matrix itself, sized by the host).  Checkpoint words: the live-row store per group of 4 blocks, boundary
+// words: per block (the pair formats keep their own; the others one direction block and one Strip per unit).
 namespace {
-// the kernel behind a variant id, as a host-side function pointer
-const void* kernel_ptr(int kid)
-{
-    switch (kid) {
-    case K_C17_CE4:    return (const void*)k_align<17, 4, false>;
-    case K_C17_CE4_N:  return (const void*)k_align<17, 4, true>;
-    case K_C5_CE0:     return (const void*)k_align<5, 0, false>;
-    case K_C5_CE0_N:   return (const void*)k_align<5, 0, true>;
-    case K_P17_CE4:    return (const void*)k_align_p<17, 4>;
-    case K_O19_CE15:   return (const void*)k_align_o<19, 15>;
-    case K_Q19_CE15:   return (const void*)k_align_q<19, 15, false>;
-    case K_Q19_CE15_N: return (const void*)k_align_q<19, 15, true>;
-    case K_GEN_C2:     return (const void*)k_align<2, -1, true>;
-    case K_GEN_C3:     return (const void*)k_align<3, -1, true>;
-    case K_GEN_C5:     return (const void*)k_align<5, -1, true>;
-    case K_GEN_C9:     return (const void*)k_align<9, -1, true>;
-    case K_GEN_C17:    return (const void*)k_align<17, -1, true>;
-    default:           return nullptr;
-    }
-}
+constexpr int W1 = 4 * GAMDP_WAVES_PER_SIMD, W2 = 4 * GAMDP_PAIR_WAVES_PER_SIMD;
+constexpr int I17 = IMG_WORDS<17, true>, I19 = IMG_WORDS<19, true>, I9 = IMG_WORDS<9, true>;
+constexpr int B1 = (int)Strip<64>::BND_WORDS, BQ = (int)Strip<QL>::BND_WORDS;
+constexpr int P17_CK = (int)PairFmt<17, 64>::CK_WORDS, P17_BND = (int)PairFmt<17, 64>::BND_WORDS;
+constexpr int O19_CK = (int)PairFmt<19, QL>::CK_WORDS, O19_BND = (int)PairFmt<19, QL>::BND_WORDS;
 }  // namespace
-
-// static LDS bytes of a variant (0 if unknown)
-unsigned kernel_static_lds(int kid)
-{
-    static unsigned cache[K_COUNT] = {0};
-    if (kid < 0 || kid >= K_COUNT) return 0;
-    if (kid == K_WIDE) return wide_static_lds();
-    if (cache[kid] == 0) {
-        hipFuncAttributes a;
-        const void* f = kernel_ptr(kid);
-        if (f && hipFuncGetAttributes(&a, f) == hipSuccess) cache[kid] = (unsigned)a.sharedSizeBytes;
-    }
-    return cache[kid];
-}
+//                      id            name                      C   band  tasks     waves  N-aware dirfree two-img dir-block ckpt    bnd      kernel
+constexpr KernelInfo kernel_info[K_COUNT] = {
+    {K_C17_CE4,    "k_align<17,4,false>",    17, 512, 1,      W1, false, true,  false, I17,    I17,    B1,      k_align<17, 4, false>},
+    {K_C17_CE4_N,  "k_align<17,4,true>",     17, 512, 1,      W1, true,  true,  false, I17,    I17,    B1,      k_align<17, 4, true>},
+    {K_C5_CE0,     "k_align<5,0,false>",      5, 150, 1,      W1, false, false, false, 5 * 64, 5 * 64, B1,      k_align<5, 0, false>},
+    {K_C5_CE0_N,   "k_align<5,0,true>",       5, 150, 1,      W1, true,  false, false, 5 * 64, 5 * 64, B1,      k_align<5, 0, true>},
+    {K_P17_CE4,    "k_align_p<17,4>",        17, 512, 2,      W2, false, true,  true,  I17,    P17_CK, P17_BND, k_align_p<17, 4>},
+    {K_O19_CE15,   "k_align_o<19,15>",       19, 150, 2 * QT, W2, false, true,  true,  I19,    O19_CK, O19_BND, k_align_o<19, 15>},
+    {K_Q19_CE15,   "k_align_q<19,15,false>", 19, 150, QT,     W1, false, true,  false, I19,    I19,    BQ,      k_align_q<19, 15, false>},
+    {K_Q19_CE15_N, "k_align_q<19,15,true>",  19, 150, QT,     W1, true,  true,  false, I19,    I19,    BQ,      k_align_q<19, 15, true>},
+    {K_GEN_C2,     "k_align<2,-1,true>",      2,   0, 1,      W1, true,  false, false, 2 * 64, 2 * 64, B1,      k_align<2, -1, true>},
+    {K_GEN_C3,     "k_align<3,-1,true>",      3,   0, 1,      W1, true,  false, false, 3 * 64, 3 * 64, B1,      k_align<3, -1, true>},
+    {K_GEN_C5,     "k_align<5,-1,true>",      5,   0, 1,      W1, true,  false, false, 5 * 64, 5 * 64, B1,      k_align<5, -1, true>},
+    {K_GEN_C9,     "k_align<9,-1,true>",      9,   0, 1,      W1, true,  true,  false, I9,     I9,     B1,      k_align<9, -1, true>},
+    {K_GEN_C17,    "k_align<17,-1,true>",    17,   0, 1,      W1, true,  true,  false, I17,    I17,    B1,      k_align<17, -1, true>},
+    {K_WIDE,       "k_align_w",               0,   0, 1,      WIDE_WORKGROUPS_PER_CU, true, false, false, 1, 1, B1, nullptr},
+};
+static_assert([] { for (int k = 0; k < K_COUNT; k++) if (kernel_info[k].id != k) return false; return true; }(),
+              "kernel_info: one row per KernelId, in KernelId order");
+static_assert(kernel_info[K_C17_CE4].dirfree == DIRFREE_OK<4, 17, false> && kernel_info[K_C17_CE4_N].dirfree == DIRFREE_OK<4, 17, true> &&
+                  kernel_info[K_C5_CE0].dirfree == DIRFREE_OK<0, 5, false> && kernel_info[K_C5_CE0_N].dirfree == DIRFREE_OK<0, 5, true> &&
+                  kernel_info[K_P17_CE4].dirfree == DIRFREE_OK<4, 17, false> && kernel_info[K_O19_CE15].dirfree == DIRFREE_OK<15, 19, false> &&
+                  kernel_info[K_Q19_CE15].dirfree == DIRFREE_OK<15, 19, false> && kernel_info[K_Q19_CE15_N].dirfree == DIRFREE_OK<15, 19, true> &&
+                  kernel_info[K_GEN_C2].dirfree == DIRFREE_OK<-1, 2, true> && kernel_info[K_GEN_C3].dirfree == DIRFREE_OK<-1, 3, true> &&
+                  kernel_info[K_GEN_C5].dirfree == DIRFREE_OK<-1, 5, true> && kernel_info[K_GEN_C9].dirfree == DIRFREE_OK<-1, 9, true> &&
+                  kernel_info[K_GEN_C17].dirfree == DIRFREE_OK<-1, 17, true>,
+              "kernel_info: the dirfree column must agree with DIRFREE_OK");
 
 // dyn_lds: unused dynamic LDS that only limits how many workgroups share a CU (see the launch planner in gamdp_host.cpp)
 int launch_align(int kid, const LaunchParams& p, unsigned n_slots, unsigned dyn_lds, void* stream)
 {
     if (kid == K_WIDE) return launch_wide(p, n_slots, stream);
-    const void* f = kernel_ptr(kid);
-    if (!f) return (int)hipErrorInvalidValue;
+    if (kid < 0 || kid >= K_COUNT) return (int)hipErrorInvalidValue;
+    const void* f = (const void*)kernel_info[kid].kernel;
     LaunchParams lp = p;
     void* args[] = {&lp};
     return (int)hipLaunchKernel(f, dim3(n_slots), dim3(64), args, dyn_lds, static_cast<hipStream_t>(stream));

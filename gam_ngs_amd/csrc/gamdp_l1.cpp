@@ -29,8 +29,6 @@
 #include "gamdp_internal.h"
 
 namespace gamdp {
-static bool chain_n_by_contig() { static const bool v = std::getenv("GAMDP_N_BY_CONTIG") != nullptr; return v; }
-
 
 // ---- ABlast::findHits ---------------------------------------------------------------------------
 void find_hits(const uint8_t* a, u64 alen, u64 a_start, u64 a_end, const uint8_t* b, u64 blen, u64 b_start, u64 b_end,
@@ -350,7 +348,7 @@ using namespace gamdp;
 namespace gamdp {
 namespace {
 
-// ---- the main chains on the device (k_chain, gamdp_dev.h) ------------------------------------------------------------
+// ---- the main chains on the device (k_chain2, gamdp_dev.h) -----------------------------------------------------------
 // One launch takes every merge block through alignBlocks' chain and the orientation retry.  It runs on its own stream beside
 // the round loop: a chain that ends copies its result records into a pinned mirror and raises a flag; the cohort that owns the
 // merge block then replays its own machine over those records (so every decision is taken twice: a difference is an internal
@@ -447,8 +445,7 @@ struct ChainRun {
 int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const SeqSet* ss, const u32 band, const u64 arena, ChainRun& run)
 {
     run.launched = false;
-    static const bool rounds_only = std::getenv("GAMDP_L1_ROUNDS") != nullptr;
-    if (rounds_only || band != 150) return 0;
+    if (tuning().l1_rounds || band != 150) return 0;
     // A merge block with an empty slave frame (s_end < s_begin) stays with the round loop: the call of such a block that
     // starts at slave base 0 has end_b = begin_b - 1 wrapped around (the reference computes it in unsigned long,
     // PctgBuilder.cc:1669-1677), so its rows are bounded by the contig, not by the frame the scratch slots below are sized for.
@@ -488,10 +485,9 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
     auto up = [](u64 v) { return (v + 255) & ~255ull; };
     // the longest chains get a twin workgroup for their second orientation (ChainSync, gamdp_dev.h): those within 1/8 of the
     // longest, at most 256 of them; GAMDP_L1_NO_TWINS=1: none
-    static const bool no_twins = std::getenv("GAMDP_L1_NO_TWINS") != nullptr;
     u64 n_tw = 0;
     const u64 tw_cap = n_mb < 256 ? std::max<u64>(16, 256 - n_mb) : 256;   // (a small call: one workgroup per CU as long as that leaves room for a few)
-    if (!no_twins)
+    if (!tuning().l1_no_twins)
         while (n_tw < n_mb && n_tw < tw_cap && w[order[n_tw]] * 8 >= w[order[0]] && w[order[n_tw]] >= 1024) n_tw++;
     const u64 off_mb = 0, off_blk = up(off_mb + n_mb * sizeof(DevMB)), off_sync = up(off_blk + n_blk * sizeof(DevBlk)), off_out = up(off_sync + (n_tw + 1) * sizeof(ChainSync)),
               off_aud = up(off_out + n_mb * sizeof(ChainOut)), off_win = up(off_aud + n_audit * sizeof(DevResult)), total = up(off_win + n_audit * sizeof(ChainWin));
@@ -561,23 +557,23 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
         }
         blk_at += in.n_blocks;
     }
-    // Scratch: every workgroup goes round its own slots (chain_slots_per_workgroup(); one for the one-wavefront kernel), sized
+    // Scratch: every workgroup goes round its own slots (chain_slots_per_workgroup()), sized
     // for the longest call ITS chain can make (x_size <= its longest slave frame) -- a call of a 30 Mb genome has a few chains
     // with frames of 100 kb and two thousand with frames of a few kb.  What does not fit the arena at once goes in pieces, one
     // launch after the other over the same memory; twins only when everything fits at once.
     const u64 Y = 2ull * band + 1, LE = (Y - 1) / 5;
     const u32 ypad = (u32)(((2 * band + 2 + 63) / 64) * 64);
-    const bool df = kernel_dirfree(K_C5_CE0_N);   // (the chain kernels' 5-column shape keeps a direction per cell: no checkpoint / boundary stores)
-    // k_chain2: a filling and two walking wavefronts per merge block; GAMDP_L1_ONE_WAVE=1 keeps the one-wavefront kernel (A/B)
-    static const bool one_wave = std::getenv("GAMDP_L1_ONE_WAVE") != nullptr;
-    const u64 per_wg = one_wave ? 1 : (u64)chain_slots_per_workgroup();
+    const KernelInfo& ki = kernel_info[K_C5_CE0_N];
+    const bool df = ki.dirfree;   // (the chain kernels' 5-column shape keeps a direction per cell: no checkpoint / boundary stores)
+    // k_chain2: a filling and two walking wavefronts per merge block
+    const u64 per_wg = (u64)chain_slots_per_workgroup();
     const u64 arena_words = arena / sizeof(u32);
     u64 words_all = 0, words_twins = 0, slotw_max = 0;
     for (size_t q = 0; q < n_mb; q++) {
         DevMB& x = hmb[q];
         const u64 nblk = ((u64)longest[order[q]] - 1 + LE) / 16 + 1;
-        const u64 dirw = ((nblk * (u64)kernel_dir_block_words(K_C5_CE0_N) + 63) / 64) * 64;
-        const u64 ckptw = df ? (nblk / 4 + 2) * (u64)kernel_ckpt_words(K_C5_CE0_N) : 0, bndw = df ? (nblk + 4) * (u64)kernel_bnd_words(K_C5_CE0_N) : 0;
+        const u64 dirw = ((nblk * (u64)ki.dir_block_words + 63) / 64) * 64;
+        const u64 ckptw = df ? (nblk / 4 + 2) * (u64)ki.ckpt_words : 0, bndw = df ? (nblk + 4) * (u64)ki.bnd_words : 0;
         x.max_x = longest[order[q]];
         x.dir_words = dirw; x.slot_words = dirw + 4ull * ypad + ckptw + bndw;
         x.ckpt_off = df ? dirw + 4ull * ypad : 0; x.bnd_off = x.ckpt_off + ckptw;
@@ -586,7 +582,7 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
         if (q < n_tw) words_twins += per_wg * x.slot_words;
     }
     if (per_wg * slotw_max > arena_words) return 0;   // (a frame too long for the arena: the round loop peels such calls off by itself)
-    if (one_wave || words_all + words_twins > arena_words) { n_tw = 0; words_twins = 0; }
+    if (words_all + words_twins > arena_words) { n_tw = 0; words_twins = 0; }
     // pieces: [first, first + count) of the list, each within the arena; slot offsets are relative to the piece
     std::vector<std::pair<u32, u32>> pieces;
     u64 need_scratch = 0;
@@ -622,13 +618,10 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
     cp.max_rows = (u32)std::min<u64>(std::max<u64>(1, w[order[0]]), 0x7fffffffu);
     cp.host_out = (ChainOut*)(dm + mo_out); cp.host_done = (u32*)(dm + mo_done); cp.host_audit = (DevResult*)(dm + mo_aud); cp.host_win = (ChainWin*)(dm + mo_win);
     cp.epoch = c->chain_epoch;
-    cp.skew_call = ~0u;
-    if (diag().build) { static const char* const e = std::getenv("GAMDP_DIAG_CHAIN_SKEW"); if (e) cp.skew_call = (u32)std::atoi(e); }
-    cp.two_waves = one_wave ? 0u : 1u;
+    cp.skew_call = diag().chain_skew;
     // N by window: the chains pick the cell of every call by the bases it touches (+ 64 on either side, as the batch path does);
-    // GAMDP_N_BY_CONTIG=1 / the diagnostics build's GAMDP_DIAG_FORCE_N: by the contigs' flags, as in rounds 3-4
-    cp.n_margin = 64; cp.n_by_contig = (chain_n_by_contig() || diag().force_n) ? 1u : 0u;
-    if (diag().build) { static const char* const e = std::getenv("GAMDP_DIAG_N_WINDOW_SHRINK"); if (e) cp.n_margin = 64 - std::atoi(e); }
+    // the diagnostics build's GAMDP_DIAG_FORCE_N: by the contigs' flags, as in rounds 3-4
+    cp.n_margin = (int32_t)(64 - diag().n_window_shrink); cp.n_by_contig = diag().force_n ? 1u : 0u;
     run.n_by_contig = cp.n_by_contig != 0;
     if (hipEventCreate(&run.e0) != hipSuccess) { c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
     if (hipEventCreate(&run.e1) != hipSuccess) { (void)hipEventDestroy(run.e0); c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
@@ -841,8 +834,8 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
     // 2 / 4 / 8 / 16).
     // GAMDP_L1_COHORTS=k (<= 16) and GAMDP_L1_COHORT_MIN=m set the cap and the floor by hand.  Results do not depend on the
     // split: every machine only sees its own results.
-    static const int forced_cohorts = [] { const char* e = std::getenv("GAMDP_L1_COHORTS"); return e ? std::min(16, std::max(1, std::atoi(e))) : 0; }();
-    static const size_t cohort_min = [] { const char* e = std::getenv("GAMDP_L1_COHORT_MIN"); const long v = e ? std::atol(e) : 48; return (size_t)std::max(1L, v); }();
+    const int forced_cohorts = tuning().l1_cohorts;
+    const size_t cohort_min = tuning().l1_cohort_min;
     const int K = forced_cohorts ? (int)std::max<size_t>(1, std::min<size_t>((size_t)forced_cohorts, n / cohort_min))
                                  : (int)std::max<size_t>(1, std::max(std::min<size_t>(4, n / cohort_min), std::min<size_t>(16, n / (4 * cohort_min))));
     while ((int)c->helpers.size() < K - 1) {

@@ -239,10 +239,5 @@ int launch_wide(const LaunchParams& p, unsigned n_slots, void* stream)
     void* args[] = {&lp};
     return (int)hipLaunchKernel((const void*)k_align_w, dim3(n_slots), dim3(WT), args, 0, static_cast<hipStream_t>(stream));
 }
-unsigned wide_static_lds()
-{
-    hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, (const void*)k_align_w) == hipSuccess ? (unsigned)a.sharedSizeBytes : 0u;
-}
 
 }  // namespace gamdp

@@ -324,17 +324,6 @@ def test_a_window_too_small_is_noticed():
     assert r.returncode == 0, r.stdout[-2500:] + r.stderr[-1500:]
 
 
-def test_n_by_contig_in_a_fresh_process():
-    """GAMDP_N_BY_CONTIG=1: a call takes the N-aware kernels whenever one of its contigs holds an N (rounds 1-3): same results."""
-    import os, subprocess, sys
-    if os.environ.get("GAMDP_N_BY_CONTIG"):
-        pytest.skip("already inside the child")
-    env = dict(os.environ, GAMDP_N_BY_CONTIG="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.abspath(__file__), "-k",
-                        "one_n_around or window_cases or random_cases or reverse_complement_and"], env=env, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, r.stdout[-2500:] + r.stderr[-2000:]
-
-
 def test_the_limits_that_remain_for_wide_bands():
     """The reference takes any band (banded_smith_waterman.hpp:66); since round 6 so does the library (k_align_w for bands > 543,
     gamdp_wide.hip).  What is left (include/gamdp.h): a band beyond GAMDP_MAX_BAND = 2^20 is refused (GAMDP_ENOTSUP), and a
@@ -771,8 +760,7 @@ def test_paths_in_every_strip():
     """tests/_cases.py displaced_path_cases: alignments that run k columns off the middle of the band, from one band edge to the
     other -- every strip of the direction-free kernels gets a walk, the strips at the two edges of a task (whose outer lanes
     belong to the next task or to nobody since the strips are centred on the band's middle column, Tk::sshift) included.
-    Band 512 here; band 150 reaches the eight-task and the four-task kernels in the GAMDP_QUAD_MIN=1 children; the strips
-    of rounds 1-3 (GAMDP_NO_STRIP_SHIFT=1) in the child below."""
+    Band 512 here; band 150 reaches the eight-task and the four-task kernels in the GAMDP_QUAD_MIN=1 children."""
     band = 150 if _os.environ.get("GAMDP_QUAD_MIN") else 512
     cases = _cases.displaced_path_cases(band)
     n = 0
@@ -784,20 +772,6 @@ def test_paths_in_every_strip():
             assert (not want_ops) or r.ops == ops, (band, k)
             n += o.status == 0
     assert n >= 50
-
-
-def test_strips_at_multiples_of_their_width_in_a_fresh_process():
-    """GAMDP_NO_STRIP_SHIFT=1: the strips of the direction-free ranges begin at multiples of the strip width (rounds 1-3):
-    same results, at band 512 and, through GAMDP_QUAD_MIN=1, in the eight-task kernel."""
-    import os, subprocess, sys
-    if os.environ.get("GAMDP_NO_STRIP_SHIFT"):
-        pytest.skip("already inside the child")
-    for extra in ({}, dict(GAMDP_QUAD_MIN="1")):
-        env = dict(os.environ, GAMDP_NO_STRIP_SHIFT="1", **extra)
-        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.abspath(__file__), "-k",
-                            "paths_in_every_strip or window_cases or golden_large or medium_pairs"],
-                           env=env, capture_output=True, text=True, timeout=1500)
-        assert r.returncode == 0, (extra, r.stdout[-2500:] + r.stderr[-2000:])
 
 
 def test_wavefronts_filled_up_with_copies():

@@ -83,7 +83,7 @@ def _child_main(argv):
 
 def _run_child(genome_len, repeats, seed=7, **env):
     e = dict(os.environ)
-    for k in ("GAMDP_L1_COHORTS", "GAMDP_L1_NO_TWINS", "GAMDP_L1_ROUNDS", "GAMDP_L1_ONE_WAVE", "GAMDP_LIB", "GAMDP_DIAG_CHAIN_SKEW"):
+    for k in ("GAMDP_L1_COHORTS", "GAMDP_L1_NO_TWINS", "GAMDP_L1_ROUNDS", "GAMDP_LIB", "GAMDP_DIAG_CHAIN_SKEW"):
         e.pop(k, None)
     e.update(env)
     r = subprocess.run([sys.executable, os.path.abspath(__file__), str(genome_len), str(repeats), str(seed)], env=e, capture_output=True,
