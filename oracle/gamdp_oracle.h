@@ -6,8 +6,9 @@
  * (oracle/_ref/libgamref.so, built from /root/reference by oracle/Makefile) on randomised and
  * hand-built cases by tests/test_oracle_vs_ref.py (runs only where /root/reference exists), and
  * against the committed golden vectors in tests/golden/ (generated from the reference by
- * tests/golden/make_golden.py) everywhere else.  The L1 driver (merge-block chain logic) has no
- * buildable reference (needs Boost.Graph) and is pinned only through the L0 calls it makes.
+ * tests/golden/make_golden.py) everywhere else.  The L1 driver (gamdp_oracle_align_merge_block) is
+ * checked against the reference's own five PctgBuilder functions (oracle/_ref/libgaml1ref.so,
+ * oracle/ref_l1_shim.cc) through tests/golden/l1_vs_ref.json.gz by tests/test_l1_oracle_vs_ref.py.
  *
  * Base codes follow lib/include/assembly/nucleotide.hpp:35-43: A=0 T=1 C=2 G=3 N=4.
  */

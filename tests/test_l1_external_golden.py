@@ -60,7 +60,7 @@ def check_gpu(d):
     return len(recs), bad
 
 
-@pytest.mark.skipif(not DATASETS, reason="no reference dump under tests/golden/l1_reference_dump/ (L1 parity unpinned)")
+@pytest.mark.skipif(not DATASETS, reason="no reference dump under tests/golden/l1_reference_dump/ (real GAGE dumps: list surgery and buildPctgs stay unpinned)")
 @pytest.mark.parametrize("d", DATASETS or ["-"])
 def test_oracle_against_reference_dump(d):
     n, bad = check_oracle(d)
@@ -68,7 +68,7 @@ def test_oracle_against_reference_dump(d):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not DATASETS, reason="no reference dump under tests/golden/l1_reference_dump/ (L1 parity unpinned)")
+@pytest.mark.skipif(not DATASETS, reason="no reference dump under tests/golden/l1_reference_dump/ (real GAGE dumps: list surgery and buildPctgs stay unpinned)")
 @pytest.mark.parametrize("d", DATASETS or ["-"])
 def test_gpu_against_reference_dump(d):
     n, bad = check_gpu(d)
