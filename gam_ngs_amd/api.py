@@ -344,7 +344,8 @@ class BandedSmithWaterman:
 
 
 class ABlast:
-    """ABlast(word_size).findHits on code arrays (host function of libgamdp)."""
+    """ABlast(word_size).findHits: on code arrays (host function of libgamdp), or find_hits_many for a batch of calls
+    over the views of uploaded sequence sets (gamdp_find_hits_batch, on the GPU)."""
 
     def __init__(self, word_size: int = 20):
         self.word_size = word_size
@@ -359,6 +360,57 @@ class ABlast:
         if n < 0:
             raise L.GamdpError("gamdp_find_hits failed")
         return list(buf[:n])
+
+    def find_hits_many(self, ctx: Context, calls, want_hits=True, caps=None, words=None):
+        """calls: list of (a: Contig, a_start, a_end, b: Contig, b_start, b_end); all a's from one SequenceSet, all b's from
+        one SequenceSet.  Returns one hit list per call (what findHits returns for those views), or, with want_hits=False,
+        (n_hits, first, last, votes) tuples.  caps (one per call) bounds how many hits of each call are returned (the
+        default: all of them); words (one per call) replaces this ABlast's word size call by call."""
+        n = len(calls)
+        if n == 0:
+            return []
+        sa, sb = calls[0][0].seqset, calls[0][3].seqset
+        tasks = (L.HitsTask * n)()
+        m64 = (1 << 64) - 1
+        for i, (a, a_start, a_end, b, b_start, b_end) in enumerate(calls):
+            if a.seqset is not sa or b.seqset is not sb:
+                raise L.GamdpError("all a / all b contigs of one batch must share a SequenceSet")
+            t = tasks[i]
+            t.a_id, t.b_id, t.a_off, t.b_off, t.a_rc, t.b_rc = a.idx, b.idx, a.off, b.off, int(a.rc), int(b.rc)
+            t.word = self.word_size if words is None else words[i]
+            t.a_start, t.a_end, t.b_start, t.b_end = a_start & m64, a_end & m64, b_start & m64, b_end & m64
+
+        def call(tasks, n, caps):
+            out = (L.HitsResult * n)()
+            buf = offs = capc = None
+            offs_l = []
+            if caps is not None:
+                tot = 0
+                for c in caps:
+                    offs_l.append(tot)
+                    tot += c
+                buf = (C.c_uint32 * max(1, tot))()
+                offs = (C.c_uint64 * n)(*offs_l)
+                capc = (C.c_uint64 * n)(*caps)
+            _check(ctx, ctx.lib.gamdp_find_hits_batch(ctx.handle, sa.handle, sb.handle, tasks, n, out, buf, offs, capc),
+                   "gamdp_find_hits_batch")
+            hits = None if caps is None else [list(buf[offs_l[i]:offs_l[i] + min(out[i].n_hits, caps[i])]) for i in range(n)]
+            return out, hits
+
+        if not want_hits:
+            return [(r.n_hits, r.first, r.last, r.votes) for r in call(tasks, n, None)[0]]
+        if caps is not None:
+            return call(tasks, n, list(caps))[1]
+        # all hits: room for a few per call, then the calls with longer lists once more with room for all of theirs
+        first = 64
+        out, hits = call(tasks, n, [first] * n)
+        again = [i for i in range(n) if out[i].n_hits > first]
+        if again:
+            sub = (L.HitsTask * len(again))(*[tasks[i] for i in again])
+            _, more = call(sub, len(again), [out[i].n_hits for i in again])
+            for i, h in zip(again, more):
+                hits[i] = h
+        return hits
 
 
 def load_fasta(path: str):

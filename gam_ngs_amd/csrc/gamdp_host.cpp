@@ -320,6 +320,7 @@ Ctx::~Ctx()
     for (Ctx* h : helpers) delete h;
     if (device >= 0) (void)hipSetDevice(device);
     flush_frees();
+    hits_free(hits);
     if (ref_event) (void)hipEventDestroy(ref_event);
     for (auto& ev : events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (d_scratch) (void)hipFree(d_scratch);

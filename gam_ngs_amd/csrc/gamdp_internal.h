@@ -151,6 +151,8 @@ struct Plan {
     u64 n_host_tasks = 0;
 };
 struct AlignCall;   // one align() call under way (gamdp_host.cpp)
+struct HitsBuffers;  // device buffers of gamdp_find_hits_batch (gamdp_hits.hip)
+void hits_free(HitsBuffers* h);
 
 struct Ctx {
     int device = -1;
@@ -200,6 +202,7 @@ struct Ctx {
     hipEvent_t ref_event = nullptr;
     std::vector<std::pair<float, float>>* interval_sink = nullptr;
     gamdp_l1_stats last_l1{};
+    HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }
     int init(int dev);

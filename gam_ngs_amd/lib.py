@@ -22,6 +22,7 @@ SYMBOLS = [
     "gamdp_multi_seqset_on", "gamdp_multi_align_batch", "gamdp_multi_align_merge_blocks", "gamdp_partition_lpt",
     "gamdp_blocks_open", "gamdp_blocks_close", "gamdp_blocks_count", "gamdp_blocks_data", "gamdp_blocks_write",
     "gamdp_no_blocks_contigs", "gamdp_no_blocks_after_filter", "gamdp_pctgs_not_merged", "gamdp_fasta_write_selected",
+    "gamdp_find_hits_batch",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
@@ -50,6 +51,18 @@ class Result(C.Structure):
         """Same tuple layout as the oracle's / golden vectors' keys."""
         return (self.status, self.begin_a, self.begin_b, self.score, self.n_match, self.length, self.first_a,
                 self.first_b, self.first_found, self.last_a, self.last_b, self.last_found, self.homology)
+
+
+class HitsTask(C.Structure):
+    """gamdp_hits_task: one ABlast(word).findHits call over two sequence views (checked against the header by static_assert)."""
+    _fields_ = [("a_id", C.c_uint32), ("b_id", C.c_uint32), ("a_off", C.c_uint64), ("b_off", C.c_uint64),
+                ("a_rc", C.c_uint8), ("b_rc", C.c_uint8), ("pad_", C.c_uint8 * 2), ("word", C.c_uint32),
+                ("a_start", C.c_uint64), ("a_end", C.c_uint64), ("b_start", C.c_uint64), ("b_end", C.c_uint64)]
+
+
+class HitsResult(C.Structure):
+    _fields_ = [("n_hits", C.c_uint64), ("votes", C.c_uint64), ("first", C.c_uint32), ("last", C.c_uint32),
+                ("status", C.c_uint8), ("pad_", C.c_uint8 * 7)]
 
 
 class Ops(C.Structure):
@@ -187,6 +200,9 @@ def load_library():
     lib.gamdp_partition_lpt.argtypes = [C.POINTER(u64), C.c_size_t, C.c_int, C.POINTER(u32)]
     lib.gamdp_find_hits.argtypes = [C.c_char_p, u64, u64, u64, C.c_char_p, u64, u64, u64, u64, vp, u64]
     lib.gamdp_find_hits.restype = C.c_int64
+    lib.gamdp_find_hits_batch.argtypes = [vp, vp, vp, C.POINTER(HitsTask), C.c_size_t, C.POINTER(HitsResult), C.POINTER(u32),
+                                          C.POINTER(u64), C.POINTER(u64)]
+    lib.gamdp_find_hits_batch.restype = C.c_int
     lib.gamdp_encode.argtypes = [C.c_char_p, u64, vp]
     lib.gamdp_encode.restype = None
     lib.gamdp_decode.argtypes = [vp, u64, vp]

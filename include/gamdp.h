@@ -10,6 +10,8 @@
  *                              first_match_pos / last_match_pos scans of each result
  *                              (lib/src/alignment/my_alignment.cc:167-193, 228-262).
  *   gamdp_find_hits            ABlast(word).findHits(...)    lib/src/alignment/ablast.cc:41-76
+ *   gamdp_find_hits_batch      N independent calls of ABlast(word).findHits(...) on the GPU, over uploaded sequence sets
+ *                              (lib/src/alignment/ablast.cc:41-76, lib/include/alignment/ablast.hpp:53-99).
  *   gamdp_align_merge_blocks   the loop `for list: for mb: builder.alignMergeBlock(graph,*mb)`
  *                              lib/src/pctg/BuildPctgFunctions.cc:82-84, i.e. N calls of
  *                              PctgBuilder::alignMergeBlock  lib/src/pctg/PctgBuilder.cc:726-844
@@ -283,6 +285,36 @@ int gamdp_partition_lpt(const uint64_t* weights, size_t n, int parts, uint32_t* 
 int64_t gamdp_find_hits(const uint8_t* a, uint64_t alen, uint64_t a_start, uint64_t a_end,
                         const uint8_t* b, uint64_t blen, uint64_t b_start, uint64_t b_end,
                         uint64_t word, uint32_t* hits, uint64_t cap);
+
+/* ABlast(word).findHits(a_view, a_start, a_end, b_view, b_start, b_end) (lib/src/alignment/ablast.cc:41-76,
+ * lib/include/alignment/ablast.hpp:53-99) for a batch of queries on the GPU, over the packed sequences of the sets (a packed-only
+ * synthetic set included).  Views as in gamdp_task: *_rc = reverse complement, then *_off = suffix; coordinates are relative to
+ * the view and clamped exactly as ablast.cc:47-53 (word == 0: no hits).  The hits of a query are the positions a_start + i of the
+ * diagonals i that hold the most votes, ascending, as uint32_t (the reference's list<uint32_t>). */
+typedef struct gamdp_hits_task {
+    uint32_t a_id, b_id;
+    uint64_t a_off, b_off;
+    uint8_t a_rc, b_rc, pad_[2];
+    uint32_t word;                  /* ABlast word size (the reference's default: 20) */
+    uint64_t a_start, a_end, b_start, b_end;
+} gamdp_hits_task;
+
+typedef struct gamdp_hits_result {
+    uint64_t n_hits;                /* hitsList.size()                                                        */
+    uint64_t votes;                 /* max_score of ablast.cc:44-73 (0 when there is no hit)                  */
+    uint32_t first, last;           /* hitsList.front() / .back() (what PctgBuilder.cc:1544, 1584 consume); 0 without hits */
+    uint8_t status;                 /* GAMDP_ST_OK, or GAMDP_ST_INVALID: *_off beyond the end of the sequence */
+    uint8_t pad_[7];
+} gamdp_hits_result;
+
+/* The hits of query i go to hits_buf[hits_off[i] .. + min(n_hits, hits_cap[i])); hits_buf == NULL: the summaries only.
+ * GAMDP_EINVAL for NULL ctx / sets / out and for ids out of range or reverse complements of a packed-only set;
+ * GAMDP_ENOMEM when one query alone does not fit the scratch arena (gamdp_ctx_set_arena_bytes; gamdp_last_error names it) --
+ * a batch whose queries fit one by one goes in pieces.  The launches count toward gamdp_ctx_kernel_time; gamdp_ctx_launch_info
+ * keeps describing the last gamdp_align_batch. */
+int gamdp_find_hits_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_hits_task* tasks,
+                          size_t n, gamdp_hits_result* out, uint32_t* hits_buf, const uint64_t* hits_off,
+                          const uint64_t* hits_cap);
 void gamdp_encode(const char* chars, uint64_t n, uint8_t* codes);
 void gamdp_decode(const uint8_t* codes, uint64_t n, char* chars);
 void gamdp_revcomp(uint8_t* codes, uint64_t n);
