@@ -23,9 +23,13 @@ def _mutate(rng, a, sub=0.02, ins=0.005, dele=0.005):
     return b
 
 
-def mixed_batch(seed, n_pairs, calls_per_pair, band=150, len_lo=300, len_hi=20000, n_frac=0.01, force_frac=0.10):
+def mixed_batch(seed, n_pairs, calls_per_pair, band=150, len_lo=300, len_hi=20000, n_frac=0.01, force_frac=0.10, views=0.0):
     """-> (seqs, calls): seqs[2k] = A_k, seqs[2k+1] = B_k as bytes of codes; calls = list of dicts with the gamdp_task fields
-    (a_id, b_id, a_off, begin_a, end_a, begin_b, end_b, fs, fe, band)."""
+    (a_id, b_id, a_off, begin_a, end_a, begin_b, end_b, fs, fe, band).
+    views > 0 (opt-in; 0 leaves the batch bit-identical to what it always was): that share of the contigs is STORED as something else
+    than what its calls see -- reverse-complemented, behind a prefix the calls chop off, or both -- and its calls carry the view that
+    undoes it (a_rc / b_rc, a longer a_off, b_off != 0).  Then -> (seqs, calls, plain_seqs): the calls on the views of `seqs` must
+    give what the same calls, without their view fields except the a_off of the right tails, give on plain_seqs (with_views below)."""
     rng = np.random.default_rng(seed)
     seqs, calls = [], []
     for k in range(n_pairs):
@@ -67,13 +71,41 @@ def mixed_batch(seed, n_pairs, calls_per_pair, band=150, len_lo=300, len_hi=2000
                 ba = max(0, s + int(x * scale) + jitter)
                 c.update(begin_a=ba, end_a=min(la - 1, ba + int(w * scale) - 1), begin_b=x, end_b=min(lb - 1, x + w - 1))
             calls.append(c)
+    if views > 0:
+        return with_views(seed, seqs, calls, views)
     return seqs, calls
+
+
+_VIEW_OFFS = (1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1300)
+_RC = bytes([1, 0, 3, 2, 4]) + bytes(range(5, 256))
+
+
+def with_views(seed, seqs, calls, share):
+    """(stored seqs, calls with view fields, the plain seqs): a generator of its own, so that the plain batch stays what it was."""
+    rng = np.random.default_rng([seed, 0x76696577])
+    stored, view = [], []
+    for k, s in enumerate(seqs):
+        u = rng.random()
+        rc, off = False, 0
+        if u < share:
+            kind = int(rng.integers(0, 3))          # rc, off, rc + off
+            rc = kind != 1
+            if kind != 0:
+                off = _VIEW_OFFS[int(rng.integers(0, len(_VIEW_OFFS)))]
+        x = rng.integers(0, 4, off).astype(np.uint8).tobytes() + s
+        stored.append(x.translate(_RC)[::-1] if rc else x)
+        view.append((rc, off))
+    out = []
+    for c in calls:
+        (arc, aoff), (brc, boff) = view[c["a_id"]], view[c["b_id"]]
+        out.append(dict(c, a_rc=int(arc), b_rc=int(brc), a_off=c["a_off"] + aoff, b_off=boff))
+    return stored, out, seqs
 
 
 def fill_tasks(tasks, calls):
     """calls -> the ctypes gamdp_task array `tasks` (gam_ngs_amd.lib.Task)"""
     for t, c in zip(tasks, calls):
-        t.a_id, t.b_id, t.a_off, t.b_off = c["a_id"], c["b_id"], c["a_off"], 0
-        t.a_rc = t.b_rc = 0
+        t.a_id, t.b_id, t.a_off, t.b_off = c["a_id"], c["b_id"], c["a_off"], c.get("b_off", 0)
+        t.a_rc, t.b_rc = c.get("a_rc", 0), c.get("b_rc", 0)
         t.force_start, t.force_end, t.band = int(c["fs"]), int(c["fe"]), c["band"]
         t.begin_a, t.end_a, t.begin_b, t.end_b = c["begin_a"], c["end_a"], c["begin_b"], c["end_b"]
