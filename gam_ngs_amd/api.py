@@ -47,6 +47,26 @@ class Context:
     def last_error(self):
         return (self.lib.gamdp_last_error(self.handle) or b"").decode()
 
+    def set_l1_hits(self, mode: int):
+        """Where alignMergeBlocks computes the findHits seeds of its tail alignments: L.L1_HITS_HOST (the default) or
+        L.L1_HITS_DEVICE (gamdp_ctx_set_l1_hits).  The results do not depend on it."""
+        _check(self, self.lib.gamdp_ctx_set_l1_hits(self.handle, mode), "gamdp_ctx_set_l1_hits")
+
+    def l1_hits_stats(self):
+        """The findHits calls of the last alignMergeBlocks on this context, as a dict (gamdp_ctx_l1_hits_stats)."""
+        st = L.L1HitsStats()
+        _check(self, self.lib.gamdp_ctx_l1_hits_stats(self.handle, C.byref(st)), "gamdp_ctx_l1_hits_stats")
+        return st.as_dict()
+
+    def l1_tail_calls(self):
+        """The tail alignments of the last alignMergeBlocks on this context and the seed each was given, as
+        (merge_block, right, begin_a, source) tuples ordered by merge block, left before right (gamdp_ctx_l1_tail_calls)."""
+        n = C.c_size_t()
+        _check(self, self.lib.gamdp_ctx_l1_tail_calls(self.handle, None, 0, C.byref(n)), "gamdp_ctx_l1_tail_calls")
+        arr = (L.L1TailCall * max(1, n.value))()
+        _check(self, self.lib.gamdp_ctx_l1_tail_calls(self.handle, arr, n.value, C.byref(n)), "gamdp_ctx_l1_tail_calls")
+        return [(arr[i].merge_block, bool(arr[i].right), arr[i].begin_a, arr[i].source) for i in range(n.value)]
+
     def kernel_time(self, reset=False):
         ms, n = C.c_double(), C.c_uint64()
         self.lib.gamdp_ctx_kernel_time(self.handle, C.byref(ms), C.byref(n), int(reset))
@@ -143,6 +163,22 @@ class MultiContext:
 
     def last_error(self):
         return (self.lib.gamdp_multi_last_error(self.handle) or b"").decode()
+
+    def set_l1_hits(self, mode: int):
+        """Context.set_l1_hits on every context of the handle."""
+        for i in range(len(self.devices)):
+            if self.lib.gamdp_ctx_set_l1_hits(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
+                raise L.GamdpError("gamdp_ctx_set_l1_hits(%r) failed on context %d" % (mode, i))
+
+    def l1_hits_stats(self):
+        """Context.l1_hits_stats of every context of the handle (a list of dicts)."""
+        out = []
+        for i in range(len(self.devices)):
+            st = L.L1HitsStats()
+            if self.lib.gamdp_ctx_l1_hits_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
+                raise L.GamdpError("gamdp_ctx_l1_hits_stats failed on context %d" % i)
+            out.append(st.as_dict())
+        return out
 
     def close(self):
         if getattr(self, "handle", None):

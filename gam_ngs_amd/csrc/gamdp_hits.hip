@@ -9,7 +9,10 @@
 //     the lanes of a wavefront step through their chains together, and a run of neighbouring lanes that vote for the same
 //     diagonal adds once (one atomic of +run per run head) -- a true overlap is one long such run;
 //   * k_hits_collect: one workgroup per query: the maximum vote, then the diagonals holding it compacted in order, in place;
-//   * k_hits_gather: the first hits_cap of each query's list packed for the download.
+//   * k_hits_gather: the first hits_cap of each query's list packed for the download;
+//   * k_hits_summary (instead of the last two when no hit list is wanted -- hits_buf == NULL, and the merge-block driver, which
+//     reads hitsList.empty() / .front() / .back() alone, PctgBuilder.cc:1544-1551, 1584-1591): one workgroup per query, ONE pass
+//     over the votes: maximum, number of diagonals holding it, the lowest and the highest of them.
 // Everything a piece of the batch needs lives in the context's scratch arena; a batch that does not fit goes in pieces.
 #include <hip/hip_runtime.h>
 
@@ -26,6 +29,11 @@ static_assert(sizeof(gamdp_hits_task) == 64 && offsetof(gamdp_hits_task, word) =
               offsetof(gamdp_hits_task, b_end) == 56, "gamdp_hits_task layout");
 static_assert(sizeof(gamdp_hits_result) == 32 && offsetof(gamdp_hits_result, first) == 16 && offsetof(gamdp_hits_result, status) == 24,
               "gamdp_hits_result layout");
+static_assert(sizeof(gamdp_l1_hits_stats) == 64 && offsetof(gamdp_l1_hits_stats, host_queries) == 32 && offsetof(gamdp_l1_hits_stats, hits_launches) == 40 &&
+              offsetof(gamdp_l1_hits_stats, mode) == 44 && offsetof(gamdp_l1_hits_stats, hits_kernel_ms) == 48 && offsetof(gamdp_l1_hits_stats, host_hits_ms) == 56,
+              "gamdp_l1_hits_stats layout");   // (L1HitsStats)
+static_assert(sizeof(gamdp_l1_tail_call) == 16 && offsetof(gamdp_l1_tail_call, merge_block) == 8 && offsetof(gamdp_l1_tail_call, right) == 12 &&
+              offsetof(gamdp_l1_tail_call, source) == 13, "gamdp_l1_tail_call layout");   // (L1TailCall)
 
 namespace gamdp {
 namespace {
@@ -186,6 +194,38 @@ __global__ __launch_bounds__(HT) void k_hits_collect(const HitsQuery* qs, u32* s
     if (t == 0) sums[blockIdx.x] = HitsSum{cnt, m, f[0], f[cnt - 1]};
 }
 
+// (maximum, how many hold it, the lowest and the highest index holding it) of two parts of a vote array, into the first
+__device__ __forceinline__ void h_best_merge(u32& m, u32& cnt, u32& lo, u32& hi, u32 m2, u32 cnt2, u32 lo2, u32 hi2)
+{
+    if (m2 > m) { m = m2; cnt = cnt2; lo = lo2; hi = hi2; }
+    else if (m2 == m) { cnt += cnt2; lo = min(lo, lo2); hi = max(hi, hi2); }
+}
+
+// What k_hits_collect reports, without the list: every lane folds its share of the votes (indices t, t + HT, ...) into one
+// (maximum, count, lowest, highest) record, the 64 records of a wavefront fold across lanes (butterfly: every lane ends with the
+// wavefront's record), the four wavefronts' records meet in LDS.  One read of f, no write to it, one barrier.
+__global__ __launch_bounds__(HT) void k_hits_summary(const HitsQuery* qs, const u32* scratch, HitsSum* sums)
+{
+    __shared__ u32 s_r[HT / 64][4];
+    const HitsQuery& Q = qs[blockIdx.x];
+    const u32* f = scratch + Q.f_off;
+    const u32 nf = Q.nf, t = threadIdx.x, lane = t & 63, w = t / 64;
+    u32 m = 0, cnt = 0, lo = 0xFFFFFFFFu, hi = 0;   // (while m == 0 the other three count zeros: dropped at the end)
+    for (u32 i = t; i < nf; i += HT) {
+        const u32 v = f[i];
+        if (v > m) { m = v; cnt = 1; lo = i; hi = i; }
+        else if (v == m) { cnt++; lo = min(lo, i); hi = i; }
+    }
+    for (int s = 32; s > 0; s >>= 1)
+        h_best_merge(m, cnt, lo, hi, (u32)__shfl_xor(m, s), (u32)__shfl_xor(cnt, s), (u32)__shfl_xor(lo, s), (u32)__shfl_xor(hi, s));
+    if (lane == 0) { s_r[w][0] = m; s_r[w][1] = cnt; s_r[w][2] = lo; s_r[w][3] = hi; }
+    __syncthreads();
+    if (t == 0) {
+        for (u32 k = 1; k < HT / 64; k++) h_best_merge(m, cnt, lo, hi, s_r[k][0], s_r[k][1], s_r[k][2], s_r[k][3]);
+        sums[blockIdx.x] = m ? HitsSum{cnt, m, Q.a_start + lo, Q.a_start + hi} : HitsSum{0, 0, 0, 0};
+    }
+}
+
 __global__ __launch_bounds__(HT) void k_hits_gather(const HitsGather* g, const u32* scratch, u32* out)
 {
     const HitsGather G = g[blockIdx.x];
@@ -227,7 +267,7 @@ template <class T>
 int hgrow(Ctx* c, T*& p, u64& cap, u64 need)
 {
     if (need <= cap) return 0;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+    if (p) { c->free_dev(p); p = nullptr; cap = 0; }   // (beside a chain launch the old buffer waits for the end of the call: Ctx::defer_frees)
     u64 want = need + need / 4;
     if (hipMalloc(&p, want * sizeof(T)) != hipSuccess) {
         if (hipMalloc(&p, need * sizeof(T)) != hipSuccess) {
@@ -273,9 +313,9 @@ HitsPlan plan_query(const gamdp_hits_task& t, u64 alen, u64 blen)
 }  // namespace
 
 // one piece: queries [first, last) of the snapshot, laid out in the scratch arena and run
-static int hits_piece(Ctx* c, HitsBuffers& hb, const SeqSet* sa, const SeqSet* sb, const std::vector<gamdp_hits_task>& tk,
-                      const std::vector<HitsPlan>& plan, const std::vector<u32>& idx, size_t first, size_t last,
-                      gamdp_hits_result* out, uint32_t* hits_buf, const std::vector<u64>& hoff, const std::vector<u64>& hcap)
+static int hits_piece(Ctx* c, HitsBuffers& hb, const std::vector<HitsReq>& tk, const std::vector<HitsPlan>& plan,
+                      const std::vector<u32>& idx, size_t first, size_t last, gamdp_hits_result* out, uint32_t* hits_buf,
+                      const std::vector<u64>& hoff, const std::vector<u64>& hcap, double* kernel_ms, u32* launches)
 {
     const size_t nq = last - first;
     std::vector<HitsQuery> hq(nq);
@@ -286,10 +326,10 @@ static int hits_piece(Ctx* c, HitsBuffers& hb, const SeqSet* sa, const SeqSet* s
     u64 at_key = 0, at_zero = n_keys, at_next = n_keys + n_zero;
     for (size_t k = 0; k < nq; k++) {
         const u32 i = idx[first + k];
-        const gamdp_hits_task& t = tk[i];
+        const gamdp_hits_task& t = tk[i].t;
         const HitsPlan& p = plan[i];
-        const DevSeq& da = t.a_rc ? sa->rc[t.a_id] : sa->fwd[t.a_id];
-        const DevSeq& db = t.b_rc ? sb->rc[t.b_id] : sb->fwd[t.b_id];
+        const DevSeq& da = t.a_rc ? tk[i].sa->rc[t.a_id] : tk[i].sa->fwd[t.a_id];
+        const DevSeq& db = t.b_rc ? tk[i].sb->rc[t.b_id] : tk[i].sb->fwd[t.b_id];
         HitsQuery& Q = hq[k];
         Q.a2 = da.p2; Q.an = da.pn; Q.b2 = db.p2; Q.bn = db.pn;
         Q.a_pos = t.a_off + p.a_start; Q.b_pos = t.b_off + p.b_start;
@@ -326,7 +366,9 @@ static int hits_piece(Ctx* c, HitsBuffers& hb, const SeqSet* sa, const SeqSet* s
     int r;
     if ((r = launch(0, k_hits_insert, tiles_a, (const HitsQuery*)hb.d_q, (u32)nq, c->d_scratch))) return r;
     if ((r = launch(1, k_hits_vote, tiles_b, (const HitsQuery*)hb.d_q, (u32)nq, c->d_scratch))) return r;
-    if ((r = launch(2, k_hits_collect, nq, (const HitsQuery*)hb.d_q, c->d_scratch, hb.d_sum))) return r;
+    if (hits_buf) r = launch(2, k_hits_collect, nq, (const HitsQuery*)hb.d_q, c->d_scratch, hb.d_sum);
+    else r = launch(2, k_hits_summary, nq, (const HitsQuery*)hb.d_q, (const u32*)c->d_scratch, hb.d_sum);
+    if (r) return r;
     std::vector<HitsSum> sums(nq);
     HCHK(c, hipMemcpyAsync(sums.data(), hb.d_sum, nq * sizeof(HitsSum), hipMemcpyDeviceToHost, c->stream));
     HCHK(c, hipStreamSynchronize(c->stream));
@@ -354,7 +396,14 @@ static int hits_piece(Ctx* c, HitsBuffers& hb, const SeqSet* sa, const SeqSet* s
     }
     for (int li = 0; li < n_launch; li++) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, hb.events[li].first, hb.events[li].second) == hipSuccess) { c->kernel_ms += ms; c->kernel_launches++; }
+        if (hipEventElapsedTime(&ms, hb.events[li].first, hb.events[li].second) != hipSuccess) continue;
+        c->kernel_ms += ms; c->kernel_launches++;
+        if (kernel_ms) *kernel_ms += ms;
+        if (launches) ++*launches;
+        if (c->interval_sink && c->ref_event) {   // merge-block calls: where this launch sat on the call's time line (as Ctx::align_collect)
+            float t0 = 0;
+            if (hipEventElapsedTime(&t0, c->ref_event, hb.events[li].first) == hipSuccess) c->interval_sink->push_back({t0, t0 + ms});
+        }
     }
     u64 pk = 0;
     for (size_t k = 0; k < nq; k++) {
@@ -370,51 +419,59 @@ static int hits_piece(Ctx* c, HitsBuffers& hb, const SeqSet* sa, const SeqSet* s
     return 0;
 }
 
-int find_hits_batch(Ctx* c, const SeqSet* sa, const SeqSet* sb, const gamdp_hits_task* tasks, size_t n, gamdp_hits_result* out,
-                    uint32_t* hits_buf, const uint64_t* hits_off, const uint64_t* hits_cap)
+int find_hits_queries(Ctx* c, const HitsReq* q, size_t n, gamdp_hits_result* out, uint32_t* hits_buf, const uint64_t* hits_off,
+                      const uint64_t* hits_cap, uint8_t* how, double* kernel_ms, u32* launches)
 {
     // the caller's arrays are read once, here
-    const std::vector<gamdp_hits_task> tk(tasks, tasks + n);
+    const std::vector<HitsReq> tk(q, q + n);
     std::vector<u64> hoff, hcap;
     if (hits_buf) { hoff.assign(hits_off, hits_off + n); hcap.assign(hits_cap, hits_cap + n); }
-    std::vector<u32> need_a, need_b;
     for (size_t i = 0; i < n; i++) {
-        const gamdp_hits_task& t = tk[i];
-        if (t.a_id >= sa->lens.size() || t.b_id >= sb->lens.size()) {
+        const gamdp_hits_task& t = tk[i].t;
+        if (t.a_id >= tk[i].sa->lens.size() || t.b_id >= tk[i].sb->lens.size()) {
             c->set_error("find_hits query " + std::to_string(i) + ": sequence id out of range");
             return GAMDP_EINVAL;
         }
-        if ((t.a_rc && !sa->has_codes()) || (t.b_rc && !sb->has_codes())) {
+        if ((t.a_rc && !tk[i].sa->has_codes()) || (t.b_rc && !tk[i].sb->has_codes())) {
             c->set_error("find_hits query " + std::to_string(i) + ": reverse complement requested on a packed-only (synthetic) sequence set");
             return GAMDP_EINVAL;
         }
-        if (t.a_rc) need_a.push_back(t.a_id);
-        if (t.b_rc) need_b.push_back(t.b_id);
     }
-    if (c->arena_budget(true) == 0) { c->set_error("hipMemGetInfo failed"); return GAMDP_EHIP; }
     const u64 arena_words = c->arena_call() / sizeof(u32);
     std::vector<HitsPlan> plan(n);
     std::vector<u32> idx;   // the queries that run on the device, in batch order
     for (size_t i = 0; i < n; i++) {
-        const gamdp_hits_task& t = tk[i];
+        const gamdp_hits_task& t = tk[i].t;
         gamdp_hits_result& o = out[i];
         std::memset(&o, 0, sizeof(o));
-        const u64 alen_full = sa->lens[t.a_id], blen_full = sb->lens[t.b_id];
+        if (how) how[i] = HITS_TRIVIAL;
+        const u64 alen_full = tk[i].sa->lens[t.a_id], blen_full = tk[i].sb->lens[t.b_id];
         if (t.a_off > alen_full || t.b_off > blen_full) { o.status = GAMDP_ST_INVALID; continue; }
         o.status = GAMDP_ST_OK;
         plan[i] = plan_query(t, alen_full - t.a_off, blen_full - t.b_off);
         if (!plan[i].work) continue;
         if (plan[i].words > arena_words) {
+            if (how) { how[i] = HITS_UNFIT; continue; }
             c->set_error("find_hits query " + std::to_string(i) + " needs " + std::to_string(plan[i].words * sizeof(u32)) +
                          " bytes of scratch; the arena allows " + std::to_string(arena_words * sizeof(u32)));
             return GAMDP_ENOMEM;
         }
+        if (how) how[i] = HITS_DEVICE;
         idx.push_back((u32)i);
     }
     if (idx.empty()) return 0;
-    if (!need_a.empty()) { int r = sa->ensure_rc(need_a, c); if (r) return r; }
-    if (!need_b.empty()) { int r = sb->ensure_rc(need_b, c); if (r) return r; }
-    if (hipSetDevice(c->device) != hipSuccess) { c->set_error("hipSetDevice failed"); return GAMDP_EHIP; }
+    // the reverse complements the device queries read, set by set (SeqSet::ensure_rc: shared by the cohort threads of a
+    // merge-block call under the set's rc_mu)
+    std::vector<std::pair<const SeqSet*, std::vector<u32>>> need;
+    auto want_rc = [&](const SeqSet* s, u32 id) {
+        for (auto& e : need) if (e.first == s) { e.second.push_back(id); return; }
+        need.push_back({s, {id}});
+    };
+    for (u32 i : idx) {
+        if (tk[i].t.a_rc) want_rc(tk[i].sa, tk[i].t.a_id);
+        if (tk[i].t.b_rc) want_rc(tk[i].sb, tk[i].t.b_id);
+    }
+    for (auto& e : need) { int r = e.first->ensure_rc(e.second, c); if (r) return r; }
     if (!c->hits) c->hits = new HitsBuffers();
     // pieces: consecutive queries while their scratch fits the arena (and the tile counts stay far below 2^31)
     size_t first = 0;
@@ -428,7 +485,7 @@ int find_hits_batch(Ctx* c, const SeqSet* sa, const SeqSet* sb, const gamdp_hits
             words += p.words; tiles += t;
             last++;
         }
-        const int r = hits_piece(c, *c->hits, sa, sb, tk, plan, idx, first, last, out, hits_buf, hoff, hcap);
+        const int r = hits_piece(c, *c->hits, tk, plan, idx, first, last, out, hits_buf, hoff, hcap, kernel_ms, launches);
         if (r) return r;
         first = last;
     }
@@ -445,8 +502,11 @@ extern "C" int gamdp_find_hits_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, 
 {
     if (!ctx || !set_a || !set_b || (n && (!tasks || !out)) || (n && hits_buf && (!hits_off || !hits_cap))) return GAMDP_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    return guarded(c, [&] {
-        return find_hits_batch(c, reinterpret_cast<const SeqSet*>(set_a), reinterpret_cast<const SeqSet*>(set_b), tasks, n, out,
-                               hits_buf, hits_off, hits_cap);
+    return guarded(c, [&]() -> int {
+        if (c->arena_budget(true) == 0) { c->set_error("hipMemGetInfo failed"); return GAMDP_EHIP; }
+        if (hipSetDevice(c->device) != hipSuccess) { c->set_error("hipSetDevice failed"); return GAMDP_EHIP; }
+        std::vector<HitsReq> q(n);
+        for (size_t i = 0; i < n; i++) q[i] = HitsReq{reinterpret_cast<const SeqSet*>(set_a), reinterpret_cast<const SeqSet*>(set_b), tasks[i]};
+        return find_hits_queries(c, q.data(), n, out, hits_buf, hits_off, hits_cap, nullptr);
     });
 }

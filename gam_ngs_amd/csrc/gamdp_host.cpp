@@ -53,6 +53,7 @@ const Diag& diag()
         x.force_n = std::getenv("GAMDP_DIAG_FORCE_N") != nullptr;
         if (const char* e = std::getenv("GAMDP_DIAG_N_WINDOW_SHRINK")) x.n_window_shrink = (int64_t)std::atol(e);
         if (const char* e = std::getenv("GAMDP_DIAG_CHAIN_SKEW")) x.chain_skew = (u32)std::atoi(e);
+        x.hits_drop = std::getenv("GAMDP_DIAG_HITS_DROP") != nullptr;
 #endif
         return x;
     }();
@@ -83,6 +84,7 @@ const Tuning& tuning()
         x.l1_no_twins = set("GAMDP_L1_NO_TWINS");
         if ((e = std::getenv("GAMDP_L1_COHORTS"))) x.l1_cohorts = std::min(16, std::max(1, std::atoi(e)));
         if ((e = std::getenv("GAMDP_L1_COHORT_MIN"))) x.l1_cohort_min = (size_t)std::max(1L, std::atol(e));
+        if ((e = std::getenv("GAMDP_L1_DEVICE_HITS"))) x.l1_device_hits = std::atoi(e) == 1;
         return x;
     }();
     return t;
@@ -300,6 +302,7 @@ int Ctx::init(int dev)
         return GAMDP_ENODEV;
     }
     device = dev;
+    l1_hits_mode = tuning().l1_device_hits ? GAMDP_L1_HITS_DEVICE : GAMDP_L1_HITS_HOST;
     if (hipSetDevice(dev) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("hipGetDeviceProperties failed"); return GAMDP_ENODEV; }

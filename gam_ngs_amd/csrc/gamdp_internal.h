@@ -30,6 +30,7 @@ struct Diag {
     bool force_n = false;          // GAMDP_DIAG_FORCE_N: N-free input through the N-aware kernels
     int64_t n_window_shrink = 0;   // GAMDP_DIAG_N_WINDOW_SHRINK=k: the N windows k bases too small on either side (fault injection)
     u32 chain_skew = ~0u;          // GAMDP_DIAG_CHAIN_SKEW=k: the device chains start call k one slave base late (fault injection)
+    bool hits_drop = false;        // GAMDP_DIAG_HITS_DROP: every device findHits query of the merge-block driver reports no hits (fault injection)
 };
 const Diag& diag();
 
@@ -53,6 +54,7 @@ struct Tuning {
     bool l1_no_twins = false;           // GAMDP_L1_NO_TWINS: no twin workgroups for the device chains
     int l1_cohorts = 0;                 // GAMDP_L1_COHORTS=k (1..16): cohorts of a merge-block call (0: by its size)
     size_t l1_cohort_min = 48;          // GAMDP_L1_COHORT_MIN=m (1 or more): merge blocks per cohort at least
+    bool l1_device_hits = false;        // GAMDP_L1_DEVICE_HITS=1: new contexts start in GAMDP_L1_HITS_DEVICE mode (gamdp_ctx_set_l1_hits)
 };
 const Tuning& tuning();
 
@@ -202,6 +204,11 @@ struct Ctx {
     hipEvent_t ref_event = nullptr;
     std::vector<std::pair<float, float>>* interval_sink = nullptr;
     gamdp_l1_stats last_l1{};
+    // where the merge-block driver computes the findHits seeds of its tail alignments (gamdp_ctx_set_l1_hits), and what the last
+    // call did there
+    int l1_hits_mode = GAMDP_L1_HITS_HOST;
+    gamdp_l1_hits_stats last_l1_hits{};
+    std::vector<gamdp_l1_tail_call> last_l1_tails;   // gamdp_ctx_l1_tail_calls
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }
@@ -291,6 +298,19 @@ void fill_result(const DevResult& r, u64 cells, gamdp_result& o);
 
 // deterministic longest-processing-time-first partition (gamdp_multi.cpp)
 void partition_lpt(const u64* weights, size_t n, int parts, u32* part_of);
+
+// ABlast::findHits (ablast.cc:41-76) on the device with the sequence sets given query by query, as ITask carries them
+// (gamdp_hits.hip).  gamdp_find_hits_batch is this with one pair of sets; the merge-block driver mixes queries whose `a` is the
+// slave with queries whose `a` is the master.  how == nullptr: a query that does not fit the arena fails the call (GAMDP_ENOMEM);
+// otherwise how[i] says what became of query i and a query that does not fit is left to the caller.  No arena refresh, no
+// hipSetDevice: the entry points do that.
+struct HitsReq {
+    const SeqSet *sa, *sb;
+    gamdp_hits_task t;
+};
+enum HitsHow : uint8_t { HITS_DEVICE = 0, HITS_TRIVIAL = 1, HITS_UNFIT = 2 };   // ran on the device / no work after the clamps / too big
+int find_hits_queries(Ctx* c, const HitsReq* q, size_t n, gamdp_hits_result* out, uint32_t* hits_buf, const uint64_t* hits_off,
+                      const uint64_t* hits_cap, uint8_t* how, double* kernel_ms = nullptr, u32* launches = nullptr);
 
 // ABlast::findHits (ablast.cc:41-76) on code arrays
 void find_hits(const uint8_t* a, u64 alen, u64 a_start, u64 a_end, const uint8_t* b, u64 blen, u64 b_start, u64 b_end,

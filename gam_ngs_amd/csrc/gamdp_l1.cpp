@@ -204,6 +204,40 @@ struct Machine {
             t.begin_b = (u64)cur_ss; t.end_b = (u64)(cur_ss + sl - 1);
             return;
         }
+        // a tail alignment: its seed is a findHits query (tail_query), answered here on the host
+        HitsReq q;
+        tail_query(q);
+        std::vector<uint32_t> hits;
+        host_tail_hits(q, rc_cache, rc_mu, hits);
+        tail_task(t, hits.size(), hits.empty() ? 0 : hits.front(), hits.empty() ? 0 : hits.back());
+    }
+
+    // LEFT / RIGHT, step 1: the ABlast(20).findHits call that seeds the tail alignment (PctgBuilder.cc:1544, 1554 left; :1584,
+    // 1597 right), as a query over views of the two sets: the reversed slave is the *_rc view, the chop_begin copy the *_off
+    // view.  The windows are the reference's own numbers (sa - 1 / sb - 1 wrap when a threshold is 0); the clamps of
+    // ablast.cc:47-53 are applied by whoever answers the query (find_hits on the host, plan_query on the device).
+    void tail_query(HitsReq& q) const
+    {
+        q = HitsReq{};
+        gamdp_hits_task& h = q.t;
+        h.word = 20;
+        const bool a_slave = phase == LEFT ? i1 < j1 : i2 < j2;
+        q.sa = a_slave ? ss : ms; q.sb = a_slave ? ms : ss;
+        h.a_id = (u32)(a_slave ? in->s_id : in->m_id); h.b_id = (u32)(a_slave ? in->m_id : in->s_id);
+        h.a_rc = a_slave && rev; h.b_rc = !a_slave && rev;
+        if (phase == LEFT) {
+            h.a_start = 0; h.a_end = (a_slave ? sb : sa) - 1; h.b_start = 0; h.b_end = (a_slave ? sa : sb) - 1;
+        } else {
+            h.a_off = (a_slave ? eb : ea) + 1;
+            const u64 tl = (a_slave ? slen : mlen) - h.a_off;
+            h.a_start = 0; h.a_end = tl - 1; h.b_start = (a_slave ? ea : eb) + 1; h.b_end = (a_slave ? mlen : slen) - 1;
+        }
+    }
+
+    // the query on the host's codes (the reversed slave from the call's cache, built on first use)
+    void host_tail_hits(const HitsReq& q, std::unordered_map<u32, std::vector<uint8_t>>& rc_cache, std::mutex& rc_mu,
+                        std::vector<uint32_t>& hits) const
+    {
         const uint8_t* mc = ms->codes[in->m_id].data();
         const uint8_t* sc;
         if (rev) {
@@ -216,35 +250,34 @@ struct Machine {
             }
             sc = it->second.data();
         } else sc = ss->codes[in->s_id].data();
-        std::vector<uint32_t> hits;
-        if (phase == LEFT) {  // :1535-1569, force_end
+        const bool a_slave = phase == LEFT ? i1 < j1 : i2 < j2;
+        const gamdp_hits_task& h = q.t;
+        find_hits((a_slave ? sc : mc) + h.a_off, (a_slave ? slen : mlen) - h.a_off, h.a_start, h.a_end, a_slave ? mc : sc,
+                  a_slave ? mlen : slen, h.b_start, h.b_end, h.word, hits);
+    }
+
+    // LEFT / RIGHT, step 2: the find_alignment call, given what the driver reads of the hits list: hitsList.empty(), .back()
+    // for the left tail (:1544-1551, 1554-1561, force_end), .front() for the right one (:1584-1591, 1597-1604, force_start)
+    void tail_task(ITask& t, const u64 n_hits, const u32 first, const u32 last)
+    {
+        t = ITask{};
+        t.band = band;
+        const bool a_slave = phase == LEFT ? i1 < j1 : i2 < j2;
+        t.sa = a_slave ? ss : ms; t.sb = a_slave ? ms : ss;
+        t.a_id = (u32)(a_slave ? in->s_id : in->m_id); t.b_id = (u32)(a_slave ? in->m_id : in->s_id);
+        t.a_rc = a_slave && rev; t.b_rc = !a_slave && rev;
+        if (phase == LEFT) {
             t.force_end = true;
-            if (i1 < j1) {
-                find_hits(sc, slen, 0, sb - 1, mc, mlen, 0, sa - 1, 20, hits);
-                t.sa = ss; t.a_id = (u32)in->s_id; t.a_rc = rev; t.sb = ms; t.b_id = (u32)in->m_id;
-                t.begin_a = hits.empty() ? sb - sa : hits.back(); t.end_a = sb - 1; t.begin_b = 0; t.end_b = sa - 1;
-                left_rev = true;
-            } else {
-                find_hits(mc, mlen, 0, sa - 1, sc, slen, 0, sb - 1, 20, hits);
-                t.sa = ms; t.a_id = (u32)in->m_id; t.sb = ss; t.b_id = (u32)in->s_id; t.b_rc = rev;
-                t.begin_a = hits.empty() ? sa - sb : hits.back(); t.end_a = sa - 1; t.begin_b = 0; t.end_b = sb - 1;
-                left_rev = false;
-            }
-        } else {  // RIGHT :1573-1611, force_start; the chop_begin copy becomes a suffix view
+            const u64 xa = a_slave ? sb : sa, xb = a_slave ? sa : sb;
+            t.begin_a = n_hits == 0 ? xa - xb : last; t.end_a = xa - 1; t.begin_b = 0; t.end_b = xb - 1;
+            left_rev = a_slave;
+        } else {  // the chop_begin copy becomes a suffix view
             t.force_start = true;
-            if (i2 < j2) {
-                const u64 tl = slen - (eb + 1);
-                find_hits(sc + eb + 1, tl, 0, tl - 1, mc, mlen, ea + 1, mlen - 1, 20, hits);
-                t.sa = ss; t.a_id = (u32)in->s_id; t.a_rc = rev; t.a_off = eb + 1; t.sb = ms; t.b_id = (u32)in->m_id;
-                t.begin_a = hits.empty() ? 0 : hits.front(); t.end_a = tl - 1; t.begin_b = ea + 1; t.end_b = mlen - 1;
-                right_rev = true;
-            } else {
-                const u64 tl = mlen - (ea + 1);
-                find_hits(mc + ea + 1, tl, 0, tl - 1, sc, slen, eb + 1, slen - 1, 20, hits);
-                t.sa = ms; t.a_id = (u32)in->m_id; t.a_off = ea + 1; t.sb = ss; t.b_id = (u32)in->s_id; t.b_rc = rev;
-                t.begin_a = hits.empty() ? 0 : hits.front(); t.end_a = tl - 1; t.begin_b = eb + 1; t.end_b = slen - 1;
-                right_rev = false;
-            }
+            t.a_off = (a_slave ? eb : ea) + 1;
+            const u64 tl = (a_slave ? slen : mlen) - t.a_off;
+            t.begin_a = n_hits == 0 ? 0 : first; t.end_a = tl - 1;
+            t.begin_b = (a_slave ? ea : eb) + 1; t.end_b = (a_slave ? mlen : slen) - 1;
+            right_rev = a_slave;
         }
     }
 
@@ -701,7 +734,11 @@ int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi)
     return 0;
 }
 
-struct CohortStats { int rounds = 0; double pending_ms = 0, align_ms = 0, feed_ms = 0; int rc = 0; };
+struct CohortStats {
+    int rounds = 0; double pending_ms = 0, align_ms = 0, feed_ms = 0; int rc = 0;
+    gamdp_l1_hits_stats hits{};   // the findHits calls of this cohort
+    std::vector<gamdp_l1_tail_call> tails;   // ... and the seed each gave its tail call
+};
 
 // The round loop over one cohort of merge blocks on one context (= one host thread + one stream): every round collects the
 // pending find_alignment calls of its machines into ONE L0 batch, feeds the results back and advances the machines.  A
@@ -709,14 +746,50 @@ struct CohortStats { int rounds = 0; double pending_ms = 0, align_ms = 0, feed_m
 // rounds go on without it -- so the tails of the short chains are aligned while the long chains run, and a round is whatever
 // became ready while the last one was in flight.  Cohorts run concurrently: while one waits for its kernel, another builds
 // pending calls (findHits over contig tails, descriptor preparation) or feeds results -- host work hides behind GPU work.
+//
+// The tail alignments are seeded by findHits.  GAMDP_L1_HITS_HOST: inside Machine::pending, query by query.
+// GAMDP_L1_HITS_DEVICE (`hits_mode`, the owner context's: its helpers inherit it): a round first describes the queries of all
+// its machines (Machine::tail_query), runs them as ONE batch of the hits kernels on this cohort's context and stream
+// (find_hits_queries, summaries only), then builds the calls from (n_hits, first, last) (Machine::tail_task).  A query whose
+// scratch does not fit this cohort's share of the arena is answered by the host's find_hits; it never fails the call.
 void run_cohort(Ctx* c, std::vector<Machine>& M, const std::vector<u32>& ids, std::unordered_map<u32, std::vector<uint8_t>>& rc_cache,
-                std::mutex& rc_mu, CohortStats& st, const ChainRun* run)
+                std::mutex& rc_mu, CohortStats& st, const ChainRun* run, const int hits_mode)
 {
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto msec = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::vector<ITask> tasks;
     std::vector<u32> owner, first, waiting;
     std::vector<gamdp_result> res;
+    const bool device_hits = hits_mode == GAMDP_L1_HITS_DEVICE;
+    std::vector<HitsReq> hq;             // device mode: the round's findHits queries ...
+    std::vector<u32> hq_task;            // ... and the call each of them seeds
+    std::vector<Machine::Phase> hq_phase;
+    std::vector<gamdp_hits_result> hres;
+    std::vector<uint8_t> hhow;
+    std::vector<uint32_t> host_hits;
+    // a call of machine m in the phase it is in: a main-chain call, or a tail call (host mode: seeded at once; device mode: its
+    // query goes to the round's batch)
+    auto note_tail = [&](u32 mi, Machine::Phase ph, const ITask& t, int source) {
+        st.tails.push_back(gamdp_l1_tail_call{t.begin_a, mi, (uint8_t)(ph == Machine::RIGHT), (uint8_t)source, {0, 0}});
+    };
+    auto next_call = [&](u32 mi) {
+        Machine& m = M[mi];
+        tasks.push_back(ITask{});
+        if (m.phase == Machine::MAIN) { m.pending(tasks.back(), rc_cache, rc_mu); return; }
+        st.hits.tail_queries++;
+        if (!device_hits) {
+            const auto h0 = now();
+            m.pending(tasks.back(), rc_cache, rc_mu);
+            st.hits.host_hits_ms += msec(h0, now());
+            st.hits.host_queries++;
+            note_tail(mi, m.phase, tasks.back(), GAMDP_L1_SEED_HOST);
+            return;
+        }
+        hq.push_back(HitsReq{});
+        m.tail_query(hq.back());
+        hq_task.push_back((u32)tasks.size() - 1);
+        hq_phase.push_back(m.phase);
+    };
     const bool chained = run && run->launched;
     if (chained)
         for (u32 i : ids)
@@ -758,17 +831,50 @@ void run_cohort(Ctx* c, std::vector<Machine>& M, const std::vector<u32>& ids, st
         }
         // one call per machine -- two for a machine whose left AND right tails are due (independent of each other)
         tasks.clear();
+        hq.clear(); hq_task.clear(); hq_phase.clear();
+        std::vector<u32> hq_owner;
         first.assign(owner.size(), 0);
         for (size_t q = 0; q < owner.size(); q++) {
             Machine& m = M[owner[q]];
             first[q] = (u32)tasks.size();
-            tasks.push_back(ITask{});
-            m.pending(tasks.back(), rc_cache, rc_mu);
+            const size_t hq0 = hq.size();
+            next_call(owner[q]);
             if (m.phase == Machine::LEFT && m.right_follows_left()) {
                 m.phase = Machine::RIGHT;          // (pending() looks at the phase and the main chain's end points only)
-                tasks.push_back(ITask{});
-                m.pending(tasks.back(), rc_cache, rc_mu);
+                next_call(owner[q]);
                 m.phase = Machine::LEFT;
+            }
+            hq_owner.resize(hq_owner.size() + (hq.size() - hq0), owner[q]);
+        }
+        if (!hq.empty()) {
+            hres.assign(hq.size(), gamdp_hits_result{});
+            hhow.assign(hq.size(), 0);
+            u32 n_launch = 0;
+            st.rc = find_hits_queries(c, hq.data(), hq.size(), hres.data(), nullptr, nullptr, nullptr, hhow.data(), &st.hits.hits_kernel_ms, &n_launch);
+            if (st.rc) return;
+            st.hits.hits_launches += n_launch;
+            for (size_t k = 0; k < hq.size(); k++) {
+                Machine& m = M[hq_owner[k]];
+                const Machine::Phase was = m.phase;
+                m.phase = hq_phase[k];
+                u64 n_hits = hres[k].n_hits; u32 h_first = hres[k].first, h_last = hres[k].last;
+                const int source = hhow[k] == HITS_UNFIT ? GAMDP_L1_SEED_FALLBACK : hhow[k] == HITS_TRIVIAL ? GAMDP_L1_SEED_TRIVIAL : GAMDP_L1_SEED_DEVICE;
+                if (hhow[k] == HITS_UNFIT) {
+                    const auto h0 = now();
+                    m.host_tail_hits(hq[k], rc_cache, rc_mu, host_hits);
+                    st.hits.host_hits_ms += msec(h0, now());
+                    st.hits.host_fallback++;
+                    n_hits = host_hits.size(); h_first = host_hits.empty() ? 0 : host_hits.front(); h_last = host_hits.empty() ? 0 : host_hits.back();
+                } else if (hhow[k] == HITS_TRIVIAL) {
+                    if (hres[k].status != GAMDP_ST_OK) { c->set_error("internal: a tail's findHits view starts beyond its contig"); st.rc = GAMDP_EHIP; return; }
+                    st.hits.trivial_queries++;
+                } else {
+                    st.hits.device_queries++;
+                    if (diag().hits_drop) { n_hits = 0; h_first = h_last = 0; }   // diagnostics build: a wrong seed the tests must notice
+                }
+                m.tail_task(tasks[hq_task[k]], n_hits, h_first, h_last);
+                note_tail(hq_owner[k], hq_phase[k], tasks[hq_task[k]], source);
+                m.phase = was;
             }
         }
         const auto t1 = now();
@@ -831,7 +937,8 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
     // through this loop: 192 merge blocks 12.5 / 11.5 / 8.8 / 13.1 ms with 1 / 2 / 4 / 8 cohorts, 1 967 merge blocks 103 / 77 /
     // 60 / 54 / 63 ms with 1 / 2 / 4 / 8 / 12; with the main chains on the device only the tails are left, two rounds bound by
     // findHits on the host: 192 merge blocks 7.4 / 7.2 / 7.0 / 7.1 ms with 1 / 2 / 4 / 8, 1 967: 56 / 46 / 38 / 37 ms with
-    // 2 / 4 / 8 / 16).
+    // 2 / 4 / 8 / 16).  GAMDP_L1_HITS_DEVICE moves those findHits calls to the device, a round's as one batch: DESIGN.md section 6
+    // has both modes side by side.
     // GAMDP_L1_COHORTS=k (<= 16) and GAMDP_L1_COHORT_MIN=m set the cap and the floor by hand.  Results do not depend on the
     // split: every machine only sees its own results.
     const int forced_cohorts = tuning().l1_cohorts;
@@ -898,7 +1005,7 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
         cc->interval_sink = &intervals[(size_t)k];
         const int rc_k = guarded(cc, [&]() -> int {
             if (hipSetDevice(cc->device) != hipSuccess) { cc->set_error("hipSetDevice failed"); return GAMDP_EHIP; }
-            run_cohort(cc, M, ids[(size_t)k], rc_cache, rc_mu, cst[(size_t)k], &run);
+            run_cohort(cc, M, ids[(size_t)k], rc_cache, rc_mu, cst[(size_t)k], &run, c->l1_hits_mode);
             return 0;
         });
         if (rc_k && !cst[(size_t)k].rc) cst[(size_t)k].rc = rc_k;
@@ -923,8 +1030,20 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
     for (int k = 1; k < K; k++) { c->kernel_ms += c->helpers[(size_t)k - 1]->kernel_ms; c->kernel_launches += c->helpers[(size_t)k - 1]->kernel_launches; }
     S.merge_blocks = n; S.cohorts = (uint32_t)K;
     for (size_t i = 0; i < n; i++) { S.dp_calls += out[i].n_dp; S.cells += out[i].cells; }
+    gamdp_l1_hits_stats& H = c->last_l1_hits;
+    H = gamdp_l1_hits_stats{};
+    H.mode = (uint32_t)c->l1_hits_mode;
+    c->last_l1_tails.clear();
+    for (int k = 0; k < K; k++) c->last_l1_tails.insert(c->last_l1_tails.end(), cst[(size_t)k].tails.begin(), cst[(size_t)k].tails.end());
+    std::sort(c->last_l1_tails.begin(), c->last_l1_tails.end(), [](const gamdp_l1_tail_call& x, const gamdp_l1_tail_call& y) {
+        return x.merge_block != y.merge_block ? x.merge_block < y.merge_block : x.right < y.right;
+    });
     std::vector<std::pair<float, float>> all;
     for (int k = 0; k < K; k++) {
+        const gamdp_l1_hits_stats& h = cst[(size_t)k].hits;
+        H.tail_queries += h.tail_queries; H.device_queries += h.device_queries; H.trivial_queries += h.trivial_queries;
+        H.host_fallback += h.host_fallback; H.host_queries += h.host_queries; H.hits_launches += h.hits_launches;
+        H.hits_kernel_ms += h.hits_kernel_ms; H.host_hits_ms += h.host_hits_ms;
         S.rounds = std::max<uint32_t>(S.rounds, (uint32_t)cst[(size_t)k].rounds + (chained ? 1u : 0u));
         S.host_pending_ms += cst[(size_t)k].pending_ms; S.host_feed_ms += cst[(size_t)k].feed_ms;
         all.insert(all.end(), intervals[(size_t)k].begin(), intervals[(size_t)k].end());
@@ -946,6 +1065,29 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
                      n, K, S.rounds, S.launches, S.wall_ms, S.gpu_busy_ms, S.kernel_sum_ms, S.host_pending_ms, S.host_feed_ms);
     return 0;
     });
+}
+
+extern "C" int gamdp_ctx_set_l1_hits(gamdp_ctx* ctx, int mode)
+{
+    if (!ctx || (mode != GAMDP_L1_HITS_HOST && mode != GAMDP_L1_HITS_DEVICE)) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->l1_hits_mode = mode;
+    return 0;
+}
+
+extern "C" int gamdp_ctx_l1_hits_stats(const gamdp_ctx* ctx, gamdp_l1_hits_stats* out)
+{
+    if (!ctx || !out) return GAMDP_EINVAL;
+    *out = reinterpret_cast<const Ctx*>(ctx)->last_l1_hits;
+    return 0;
+}
+
+extern "C" int gamdp_ctx_l1_tail_calls(const gamdp_ctx* ctx, gamdp_l1_tail_call* out, size_t cap, size_t* n)
+{
+    if (!ctx || (cap && !out)) return GAMDP_EINVAL;
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    if (n) *n = c->last_l1_tails.size();
+    for (size_t i = 0; i < c->last_l1_tails.size() && i < cap; i++) out[i] = c->last_l1_tails[i];
+    return 0;
 }
 
 extern "C" int gamdp_ctx_l1_stats(const gamdp_ctx* ctx, gamdp_l1_stats* out)

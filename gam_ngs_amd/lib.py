@@ -22,11 +22,13 @@ SYMBOLS = [
     "gamdp_multi_seqset_on", "gamdp_multi_align_batch", "gamdp_multi_align_merge_blocks", "gamdp_partition_lpt",
     "gamdp_blocks_open", "gamdp_blocks_close", "gamdp_blocks_count", "gamdp_blocks_data", "gamdp_blocks_write",
     "gamdp_no_blocks_contigs", "gamdp_no_blocks_after_filter", "gamdp_pctgs_not_merged", "gamdp_fasta_write_selected",
-    "gamdp_find_hits_batch",
+    "gamdp_find_hits_batch", "gamdp_ctx_set_l1_hits", "gamdp_ctx_l1_hits_stats",
+    "gamdp_ctx_l1_tail_calls",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
 ST_OK, ST_EMPTY, ST_OUT_OF_RANGE, ST_INVALID = 0, 1, 2, 3
+L1_HITS_HOST, L1_HITS_DEVICE = 0, 1   # gamdp_ctx_set_l1_hits
 ST_DIAG_RANGE = 9   # diagnostics build only: a packed-f16 block left the exact range (never expected)
 
 
@@ -91,6 +93,22 @@ class L1Stats(C.Structure):
                 ("cohorts", C.c_uint32), ("launches", C.c_uint32), ("pad_", C.c_uint32), ("wall_ms", C.c_double),
                 ("gpu_busy_ms", C.c_double), ("kernel_sum_ms", C.c_double), ("host_pending_ms", C.c_double),
                 ("host_feed_ms", C.c_double)]
+
+
+class L1HitsStats(C.Structure):
+    """gamdp_l1_hits_stats: the findHits calls of the last gamdp_align_merge_blocks (checked against the header by static_assert)."""
+    _fields_ = [("tail_queries", C.c_uint64), ("device_queries", C.c_uint64), ("trivial_queries", C.c_uint64),
+                ("host_fallback", C.c_uint64), ("host_queries", C.c_uint64), ("hits_launches", C.c_uint32), ("mode", C.c_uint32),
+                ("hits_kernel_ms", C.c_double), ("host_hits_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class L1TailCall(C.Structure):
+    """gamdp_l1_tail_call: the seed of one tail alignment of the last gamdp_align_merge_blocks (static_assert in gamdp_hits.hip)."""
+    _fields_ = [("begin_a", C.c_uint64), ("merge_block", C.c_uint32), ("right", C.c_uint8), ("source", C.c_uint8),
+                ("pad_", C.c_uint8 * 2)]
 
 
 class LaunchInfo(C.Structure):
@@ -178,6 +196,12 @@ def load_library():
                                              C.POINTER(Result), u32]
     lib.gamdp_task_preflight.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int, C.POINTER(u64)]
     lib.gamdp_ctx_l1_stats.argtypes = [vp, C.POINTER(L1Stats)]
+    lib.gamdp_ctx_set_l1_hits.argtypes = [vp, C.c_int]
+    lib.gamdp_ctx_set_l1_hits.restype = C.c_int
+    lib.gamdp_ctx_l1_hits_stats.argtypes = [vp, C.POINTER(L1HitsStats)]
+    lib.gamdp_ctx_l1_hits_stats.restype = C.c_int
+    lib.gamdp_ctx_l1_tail_calls.argtypes = [vp, C.POINTER(L1TailCall), C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gamdp_ctx_l1_tail_calls.restype = C.c_int
     lib.gamdp_build_info.argtypes = []
     lib.gamdp_build_info.restype = C.c_uint
     lib.gamdp_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]

@@ -250,6 +250,48 @@ typedef struct gamdp_l1_stats {
 } gamdp_l1_stats;
 int gamdp_ctx_l1_stats(const gamdp_ctx* ctx, gamdp_l1_stats* out);
 
+/* Where gamdp_align_merge_blocks computes the seeds of its tail alignments: after the main chain each merge block makes up to two
+ * more find_alignment calls (PctgBuilder.cc:1535-1569 left, :1573-1611 right), each seeded by ABlast(20).findHits
+ * (lib/src/alignment/ablast.cc:41-76; the driver reads hitsList.empty(), .back() at PctgBuilder.cc:1544-1551 and .front() at
+ * :1584-1591).  HOST: one query at a time on the host's 1 byte/base codes.  DEVICE: the queries of a round as one batch of the
+ * gamdp_find_hits_batch kernels (summaries only: n_hits, first, last) on the cohort's stream, beside the chain launch; a query
+ * whose scratch does not fit the cohort's share of the arena is answered on the host.  Results, n_dp, cells and the audit trail
+ * do not depend on the mode.  A property of the context (gamdp_multi_align_merge_blocks honours what each gamdp_multi_ctx(m, i)
+ * was set to); GAMDP_L1_DEVICE_HITS=1 in the environment (read once per process) makes DEVICE the mode of new contexts. */
+#define GAMDP_L1_HITS_HOST   0   /* default */
+#define GAMDP_L1_HITS_DEVICE 1
+int gamdp_ctx_set_l1_hits(gamdp_ctx* ctx, int mode);      /* GAMDP_EINVAL for NULL / unknown mode */
+/* The findHits calls (ablast.cc:41-76) of the last gamdp_align_merge_blocks on this context. */
+typedef struct gamdp_l1_hits_stats {
+    uint64_t tail_queries;    /* findHits calls the last gamdp_align_merge_blocks made = device + trivial + host_fallback + host */
+    uint64_t device_queries;  /* answered by the hits kernels */
+    uint64_t trivial_queries; /* device mode, no work after the clamps of ablast.cc:47-53 (no launch) */
+    uint64_t host_fallback;   /* device mode, did not fit the arena share */
+    uint64_t host_queries;    /* host mode */
+    uint32_t hits_launches;   /* kernel launches of the hits batches (part of gamdp_l1_stats.launches) */
+    uint32_t mode;            /* GAMDP_L1_HITS_* the call ran in */
+    double hits_kernel_ms;    /* sum of those kernels' durations (part of gamdp_l1_stats.kernel_sum_ms) */
+    double host_hits_ms;      /* inside the host findHits, summed over cohort threads */
+} gamdp_l1_hits_stats;
+int gamdp_ctx_l1_hits_stats(const gamdp_ctx* ctx, gamdp_l1_hits_stats* out);
+/* The tail alignments the last gamdp_align_merge_blocks on this context issued, ordered by merge block, left before right: the
+ * seed each was given.  gamdp_result holds what find_alignment returned, not the window it was called with; this is the one
+ * number of that window that findHits decides (begin_a: hitsList.back() / sb - sa, PctgBuilder.cc:1544-1561, hitsList.front() /
+ * 0, :1584-1604), so that a test can pin the seed itself.  *n = how many there are; the first cap are written (as
+ * gamdp_ctx_launch_info). */
+#define GAMDP_L1_SEED_HOST     0   /* host mode                           */
+#define GAMDP_L1_SEED_DEVICE   1   /* the hits kernels                    */
+#define GAMDP_L1_SEED_TRIVIAL  2   /* device mode, no work after the clamps */
+#define GAMDP_L1_SEED_FALLBACK 3   /* device mode, host fallback          */
+typedef struct gamdp_l1_tail_call {
+    uint64_t begin_a;         /* of the find_alignment call                          */
+    uint32_t merge_block;     /* index in the call's `in` array                      */
+    uint8_t right;            /* 0: left tail (force_end), 1: right tail (force_start) */
+    uint8_t source;           /* GAMDP_L1_SEED_*                                     */
+    uint8_t pad_[2];
+} gamdp_l1_tail_call;
+int gamdp_ctx_l1_tail_calls(const gamdp_ctx* ctx, gamdp_l1_tail_call* out, size_t cap, size_t* n);
+
 /* ---- several GPUs of one node ------------------------------------------------------------- */
 /* Replaces gam-merge's worker pool (lib/src/pctg/ThreadedBuildPctg.cc:143-197: N pthreads, mutex-guarded cursor
  * :50-74) for this path: one host thread + context + resident copy of the sequences per device; the task / merge-block

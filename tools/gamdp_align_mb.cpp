@@ -3,7 +3,9 @@
 //
 //   gamdp-align-mb <master.fasta> <slave.fasta> <mergeblocks.tsv> <out.tsv> [--band N] [--device D | --devices D0,D1,..]
 //                  [--repeat K] [--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]]
+//                  [--device-hits]
 //
+// --device-hits seeds the tail alignments with findHits on the GPU (gamdp_ctx_set_l1_hits; the output does not change).
 // --devices runs the step on several GPUs of the node (gamdp_multi_*: merge blocks partitioned statically by predicted
 // cells, one host thread + context per device, no collective); a device may be listed twice.  The output is the same
 // whatever the device list -- unlike gam-merge --threads N, whose paired-contig order depends on thread timing.
@@ -49,12 +51,15 @@ static int region_vote(void*, int32_t, int32_t, int32_t, int32_t, int32_t, int32
 int main(int argc, char** argv)
 {
     if (argc < 5) die("usage: gamdp-align-mb <master.fasta> <slave.fasta> <mergeblocks.tsv> <out.tsv> [--band N] [--device D] [--repeat K] "
-                      "[--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]]");
+                      "[--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]] [--device-hits]");
     unsigned band = GAMDP_DEFAULT_BAND;
     int device = 0, repeat = 1;
     std::vector<int> devices;
     std::string pctg_prefix, blocks_path, filtered_path;
-    for (int i = 5; i + 1 < argc; i += 2) {
+    bool device_hits = false;
+    for (int i = 5; i < argc; i += 2) {
+        if (!std::strcmp(argv[i], "--device-hits")) { device_hits = true; i--; continue; }   // (a flag: no value follows)
+        if (i + 1 >= argc) die(std::string("option ") + argv[i] + " needs a value");
         if (!std::strcmp(argv[i], "--band")) band = (unsigned)std::atoi(argv[i + 1]);
         else if (!std::strcmp(argv[i], "--device")) device = std::atoi(argv[i + 1]);
         else if (!std::strcmp(argv[i], "--devices")) {
@@ -135,6 +140,11 @@ int main(int argc, char** argv)
     } else {
         if (gamdp_multi_create(devices.data(), (int)devices.size(), &multi)) die("cannot open the listed gfx950 GPUs (libgamdp has no CPU fallback)");
         if (gamdp_multi_seqset_create_from_fasta(multi, fm, &mmaster) || gamdp_multi_seqset_create_from_fasta(multi, fs, &mslave)) die(gamdp_multi_last_error(multi));
+    }
+    if (device_hits) {   // the findHits seeds of the tail alignments on the GPU (identical results)
+        if (ctx && gamdp_ctx_set_l1_hits(ctx, GAMDP_L1_HITS_DEVICE)) die("gamdp_ctx_set_l1_hits failed");
+        for (int d = 0; multi && d < gamdp_multi_size(multi); d++)
+            if (gamdp_ctx_set_l1_hits(gamdp_multi_ctx(multi, d), GAMDP_L1_HITS_DEVICE)) die("gamdp_ctx_set_l1_hits failed");
     }
 
     std::vector<gamdp_mb_out> out(in.size());
