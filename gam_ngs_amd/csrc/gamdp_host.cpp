@@ -366,23 +366,6 @@ void Ctx::trim_scratch()
     }
 }
 
-template <class T>
-static int grow(Ctx* ctx, T*& ptr, u64& cap, u64 need)
-{
-    if (need <= cap) return 0;
-    if (ptr) { ctx->free_dev(ptr); ptr = nullptr; cap = 0; }
-    u64 want = need + (ctx->defer_frees ? need + 1024 : need / 4);   // (a round loop beside a chain launch: see the scratch arena in Ctx::align)
-    if (hipMalloc(&ptr, want * sizeof(T)) != hipSuccess) {
-        if (hipMalloc(&ptr, need * sizeof(T)) != hipSuccess) {
-            ctx->set_error("hipMalloc of " + std::to_string(need * sizeof(T)) + " bytes failed");
-            return GAMDP_ENOMEM;
-        }
-        want = need;
-    }
-    cap = want;
-    return 0;
-}
-
 // ---- task validation (same order as banded_smith_waterman.cc:90-132) -------------------------------
 
 // words of a task's direction image in a slot of kernel `kid` (K_WIDE: the band matrix itself).  The multi-task kernels keep

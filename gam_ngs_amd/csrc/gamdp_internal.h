@@ -224,10 +224,10 @@ struct Ctx {
     Plan w_plan;                                       // the launches of the batch under way
 
     // buffers of the merge-block chain kernel (gamdp_l1.cpp), kept between calls
-    void* d_chain = nullptr; u64 cap_chain = 0;    // device: DevMB[] | DevBlk[] | DevResult audit[] | ChainOut[] | cursor
-    void* h_chain = nullptr; u64 cap_hchain = 0;   // pinned: what is uploaded (DevMB[] | DevBlk[])
+    uint8_t* d_chain = nullptr; u64 cap_chain = 0;    // device, bytes: laid out by ChainLayout (gamdp_l1.cpp)
+    uint8_t* h_chain = nullptr; u64 cap_hchain = 0;   // pinned: the part of it that is uploaded
     // the chain launch runs beside the round loop's launches: own stream, own scratch slots, and a pinned coherent mirror
-    // (ChainOut[] | done flags | DevResult audit[]) the chains write when they end
+    // (ChainLayout's second half) the chains write when they end
     hipStream_t chain_stream = nullptr;
     // hipFree / hipHostFree wait for the whole device; while the chain launch runs, a round loop that regrows a buffer keeps
     // the old one until the call is over (flush_frees) instead of waiting for the launch to end
@@ -242,7 +242,7 @@ struct Ctx {
         deferred_dev.clear(); deferred_host.clear();
     }
     u32* d_chain_scratch = nullptr; u64 cap_chain_scratch = 0;   // u32 words
-    void* h_mirror = nullptr; u64 cap_mirror = 0;
+    uint8_t* h_mirror = nullptr; u64 cap_mirror = 0;
     u32 chain_epoch = 0;
 
     int align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_ops* ops);
@@ -292,6 +292,41 @@ struct Threads {
     void join() { for (auto& t : th) if (t.joinable()) t.join(); }
     ~Threads() { join(); }
 };
+
+// Regrows a device buffer that is kept between calls: `need` elements or more, with a quarter to spare (`exact`: none), or just
+// `need` when that much can not be had.  The old buffer goes through Ctx::free_dev: beside a chain launch it waits for the end of
+// the call, and a round loop there asks for twice the size instead (see the scratch arena in Ctx::align).
+template <class T>
+int grow(Ctx* ctx, T*& ptr, u64& cap, u64 need, bool exact = false)
+{
+    if (need <= cap) return 0;
+    if (ptr) { ctx->free_dev(ptr); ptr = nullptr; cap = 0; }
+    u64 want = exact ? need : need + (ctx->defer_frees ? need + 1024 : need / 4);
+    if (hipMalloc(&ptr, want * sizeof(T)) != hipSuccess) {
+        if (hipMalloc(&ptr, need * sizeof(T)) != hipSuccess) {
+            ctx->set_error("hipMalloc of " + std::to_string(need * sizeof(T)) + " bytes failed");
+            return GAMDP_ENOMEM;
+        }
+        want = need;
+    }
+    cap = want;
+    return 0;
+}
+
+// ... and a pinned one, in bytes (no second try: the merge-block driver's upload buffer and mirror are small)
+inline int grow_pinned(Ctx* ctx, uint8_t*& ptr, u64& cap, u64 need, unsigned flags)
+{
+    if (need <= cap) return 0;
+    if (ptr) { ctx->free_host(ptr); ptr = nullptr; cap = 0; }
+    const u64 want = need + need / 4;
+    if (hipHostMalloc(&ptr, want, flags) != hipSuccess) {
+        ptr = nullptr;
+        ctx->set_error("hipHostMalloc of " + std::to_string(want) + " bytes failed");
+        return GAMDP_ENOMEM;
+    }
+    cap = want;
+    return 0;
+}
 
 // DevResult record + the cell count of its call -> the C ABI's result (gamdp_host.cpp)
 void fill_result(const DevResult& r, u64 cells, gamdp_result& o);

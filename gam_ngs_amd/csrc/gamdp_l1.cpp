@@ -14,7 +14,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -101,8 +100,23 @@ constexpr double MIN_HOMOLOGY = 95.0;  // PctgBuilder.hpp:63
 inline int32_t frame_len(int32_t b, int32_t e) { return e < b ? 0 : e - b + 1; }  // Frame.cc:124-127
 inline u64 umin(u64 x, u64 y) { return x < y ? x : y; }
 
+// The host's 1 B/base reverse complements of the slave contigs of one call, built on first use, shared by its cohort threads
+struct RcCache {
+    std::unordered_map<u32, std::vector<uint8_t>> map;
+    std::mutex mu;
+    const uint8_t* get(const SeqSet* ss, u32 id)
+    {
+        std::lock_guard<std::mutex> g(mu);  // node-based map: the data pointer stays valid after unlock
+        auto it = map.find(id);
+        if (it != map.end()) return it->second.data();
+        std::vector<uint8_t> r = ss->codes[id];
+        gamdp_revcomp(r.data(), r.size());
+        return map.emplace(id, std::move(r)).first->second.data();
+    }
+};
+
 struct Machine {
-    enum Phase { MAIN, LEFT, RIGHT, DONE };
+    enum Phase { MAIN, LEFT, RIGHT, DONE };   // LEFT / RIGHT also name the side of a tail alignment
     const gamdp_mb_in* in = nullptr;
     gamdp_mb_out* out = nullptr;
     const SeqSet *ms = nullptr, *ss = nullptr;
@@ -184,100 +198,90 @@ struct Machine {
         last_a = last_b = 0;
     }
 
-    // the next find_alignment call of this merge block
-    void pending(ITask& t, std::unordered_map<u32, std::vector<uint8_t>>& rc_cache, std::mutex& rc_mu)
+    // MAIN: the next find_alignment call of the chain (alignBlocks, :1652-1677)
+    void pending(ITask& t)
     {
         t = ITask{};
         t.band = band;
-        if (phase == MAIN) {
-            const gamdp_block& cur = blk(k);
-            const int32_t ml = frame_len(cur.m_begin, cur.m_end), sl = frame_len(cur.s_begin, cur.s_end);
-            if (k > 0) {  // :1660-1667
-                const gamdp_block& prev = blk(k - 1);
-                const int32_t mgap = prev.m_begin <= cur.m_begin ? (cur.m_begin - prev.m_end - 1) : (prev.m_begin - cur.m_end - 1);
-                const int32_t sgap = prev.s_begin <= cur.s_begin ? (cur.s_begin - prev.s_end - 1) : (prev.s_begin - cur.s_end - 1);
-                cur_ms = (int64_t)(last_a + (u64)(int64_t)mgap); if (cur_ms < 0) cur_ms = 0;
-                cur_ss = (int64_t)(last_b + (u64)(int64_t)sgap); if (cur_ss < 0) cur_ss = 0;
-            }
-            t.sa = ms; t.a_id = (u32)in->m_id; t.sb = ss; t.b_id = (u32)in->s_id; t.b_rc = try_rev;
-            t.begin_a = (u64)cur_ms; t.end_a = (u64)(cur_ms + ml - 1);
-            t.begin_b = (u64)cur_ss; t.end_b = (u64)(cur_ss + sl - 1);
-            return;
+        const gamdp_block& cur = blk(k);
+        const int32_t ml = frame_len(cur.m_begin, cur.m_end), sl = frame_len(cur.s_begin, cur.s_end);
+        if (k > 0) {  // :1660-1667
+            const gamdp_block& prev = blk(k - 1);
+            const int32_t mgap = prev.m_begin <= cur.m_begin ? (cur.m_begin - prev.m_end - 1) : (prev.m_begin - cur.m_end - 1);
+            const int32_t sgap = prev.s_begin <= cur.s_begin ? (cur.s_begin - prev.s_end - 1) : (prev.s_begin - cur.s_end - 1);
+            cur_ms = (int64_t)(last_a + (u64)(int64_t)mgap); if (cur_ms < 0) cur_ms = 0;
+            cur_ss = (int64_t)(last_b + (u64)(int64_t)sgap); if (cur_ss < 0) cur_ss = 0;
         }
-        // a tail alignment: its seed is a findHits query (tail_query), answered here on the host
-        HitsReq q;
-        tail_query(q);
-        std::vector<uint32_t> hits;
-        host_tail_hits(q, rc_cache, rc_mu, hits);
-        tail_task(t, hits.size(), hits.empty() ? 0 : hits.front(), hits.empty() ? 0 : hits.back());
+        t.sa = ms; t.a_id = (u32)in->m_id; t.sb = ss; t.b_id = (u32)in->s_id; t.b_rc = try_rev;
+        t.begin_a = (u64)cur_ms; t.end_a = (u64)(cur_ms + ml - 1);
+        t.begin_b = (u64)cur_ss; t.end_b = (u64)(cur_ss + sl - 1);
     }
 
-    // LEFT / RIGHT, step 1: the ABlast(20).findHits call that seeds the tail alignment (PctgBuilder.cc:1544, 1554 left; :1584,
-    // 1597 right), as a query over views of the two sets: the reversed slave is the *_rc view, the chop_begin copy the *_off
-    // view.  The windows are the reference's own numbers (sa - 1 / sb - 1 wrap when a threshold is 0); the clamps of
-    // ablast.cc:47-53 are applied by whoever answers the query (find_hits on the host, plan_query on the device).
-    void tail_query(HitsReq& q) const
+    // How the tail alignment of one side, and the findHits call that seeds it, see the two contigs (PctgBuilder.cc:1535-1611):
+    // the contig with less left over on that side is the `a` sequence, the reversed slave is an *_rc view, the right tail's
+    // chop_begin copy of `a` a suffix view.  Valid once the main chain is good (after_main_good).
+    struct TailView {
+        bool a_slave, a_rc, b_rc;  // the slave contig is `a`; the views are reversed
+        const SeqSet *sa, *sb;
+        u32 a_id, b_id;
+        u64 alen, blen;            // the whole contigs
+        u64 xa, xb;                // where the main alignment ends on this side, in a and in b: its first match (LEFT), its last (RIGHT)
+        u64 a_off;                 // RIGHT: the suffix view of `a` starts behind xa;  LEFT: 0
+    };
+    TailView tail_view(Phase side) const
     {
+        TailView v;
+        const bool s = v.a_slave = side == LEFT ? i1 < j1 : i2 < j2;
+        v.sa = s ? ss : ms; v.sb = s ? ms : ss;
+        v.a_id = (u32)(s ? in->s_id : in->m_id); v.b_id = (u32)(s ? in->m_id : in->s_id);
+        v.a_rc = s && rev; v.b_rc = !s && rev;
+        v.alen = s ? slen : mlen; v.blen = s ? mlen : slen;
+        const u64 xm = side == LEFT ? sa : ea, xs = side == LEFT ? sb : eb;
+        v.xa = s ? xs : xm; v.xb = s ? xm : xs;
+        v.a_off = side == LEFT ? 0 : v.xa + 1;
+        return v;
+    }
+
+    // A tail, step 1: the ABlast(20).findHits call that seeds the alignment (PctgBuilder.cc:1544, 1554 left; :1584, 1597 right),
+    // as a query over the views.  The windows are the reference's own numbers (xa - 1 / xb - 1 wrap when a threshold is 0); the
+    // clamps of ablast.cc:47-53 are applied by whoever answers the query (find_hits on the host, plan_query on the device).
+    void tail_query(Phase side, HitsReq& q) const
+    {
+        const TailView v = tail_view(side);
         q = HitsReq{};
+        q.sa = v.sa; q.sb = v.sb;
         gamdp_hits_task& h = q.t;
         h.word = 20;
-        const bool a_slave = phase == LEFT ? i1 < j1 : i2 < j2;
-        q.sa = a_slave ? ss : ms; q.sb = a_slave ? ms : ss;
-        h.a_id = (u32)(a_slave ? in->s_id : in->m_id); h.b_id = (u32)(a_slave ? in->m_id : in->s_id);
-        h.a_rc = a_slave && rev; h.b_rc = !a_slave && rev;
-        if (phase == LEFT) {
-            h.a_start = 0; h.a_end = (a_slave ? sb : sa) - 1; h.b_start = 0; h.b_end = (a_slave ? sa : sb) - 1;
-        } else {
-            h.a_off = (a_slave ? eb : ea) + 1;
-            const u64 tl = (a_slave ? slen : mlen) - h.a_off;
-            h.a_start = 0; h.a_end = tl - 1; h.b_start = (a_slave ? ea : eb) + 1; h.b_end = (a_slave ? mlen : slen) - 1;
-        }
+        h.a_id = v.a_id; h.b_id = v.b_id; h.a_rc = v.a_rc; h.b_rc = v.b_rc; h.a_off = v.a_off;
+        if (side == LEFT) { h.a_start = 0; h.a_end = v.xa - 1; h.b_start = 0; h.b_end = v.xb - 1; }
+        else { h.a_start = 0; h.a_end = v.alen - v.a_off - 1; h.b_start = v.xb + 1; h.b_end = v.blen - 1; }
     }
 
-    // the query on the host's codes (the reversed slave from the call's cache, built on first use)
-    void host_tail_hits(const HitsReq& q, std::unordered_map<u32, std::vector<uint8_t>>& rc_cache, std::mutex& rc_mu,
-                        std::vector<uint32_t>& hits) const
+    // ... answered on the host's codes (the reversed slave from the call's cache)
+    void host_tail_hits(Phase side, const HitsReq& q, RcCache& rc, std::vector<uint32_t>& hits) const
     {
+        const TailView v = tail_view(side);
         const uint8_t* mc = ms->codes[in->m_id].data();
-        const uint8_t* sc;
-        if (rev) {
-            std::lock_guard<std::mutex> g(rc_mu);  // node-based map: the data pointer stays valid after unlock
-            auto it = rc_cache.find((u32)in->s_id);
-            if (it == rc_cache.end()) {
-                std::vector<uint8_t> r = ss->codes[in->s_id];
-                gamdp_revcomp(r.data(), r.size());
-                it = rc_cache.emplace((u32)in->s_id, std::move(r)).first;
-            }
-            sc = it->second.data();
-        } else sc = ss->codes[in->s_id].data();
-        const bool a_slave = phase == LEFT ? i1 < j1 : i2 < j2;
+        const uint8_t* sc = rev ? rc.get(ss, (u32)in->s_id) : ss->codes[in->s_id].data();
         const gamdp_hits_task& h = q.t;
-        find_hits((a_slave ? sc : mc) + h.a_off, (a_slave ? slen : mlen) - h.a_off, h.a_start, h.a_end, a_slave ? mc : sc,
-                  a_slave ? mlen : slen, h.b_start, h.b_end, h.word, hits);
+        find_hits((v.a_slave ? sc : mc) + h.a_off, v.alen - h.a_off, h.a_start, h.a_end, v.a_slave ? mc : sc, v.blen, h.b_start,
+                  h.b_end, h.word, hits);
     }
 
-    // LEFT / RIGHT, step 2: the find_alignment call, given what the driver reads of the hits list: hitsList.empty(), .back()
-    // for the left tail (:1544-1551, 1554-1561, force_end), .front() for the right one (:1584-1591, 1597-1604, force_start)
-    void tail_task(ITask& t, const u64 n_hits, const u32 first, const u32 last)
+    // A tail, step 2: the find_alignment call, given what the driver reads of the hits list: hitsList.empty(), .back() for the
+    // left tail (:1544-1551, 1554-1561, force_end), .front() for the right one (:1584-1591, 1597-1604, force_start)
+    void tail_task(Phase side, ITask& t, const u64 n_hits, const u32 first, const u32 last) const
     {
+        const TailView v = tail_view(side);
         t = ITask{};
         t.band = band;
-        const bool a_slave = phase == LEFT ? i1 < j1 : i2 < j2;
-        t.sa = a_slave ? ss : ms; t.sb = a_slave ? ms : ss;
-        t.a_id = (u32)(a_slave ? in->s_id : in->m_id); t.b_id = (u32)(a_slave ? in->m_id : in->s_id);
-        t.a_rc = a_slave && rev; t.b_rc = !a_slave && rev;
-        if (phase == LEFT) {
+        t.sa = v.sa; t.sb = v.sb; t.a_id = v.a_id; t.b_id = v.b_id; t.a_rc = v.a_rc; t.b_rc = v.b_rc; t.a_off = v.a_off;
+        if (side == LEFT) {
             t.force_end = true;
-            const u64 xa = a_slave ? sb : sa, xb = a_slave ? sa : sb;
-            t.begin_a = n_hits == 0 ? xa - xb : last; t.end_a = xa - 1; t.begin_b = 0; t.end_b = xb - 1;
-            left_rev = a_slave;
-        } else {  // the chop_begin copy becomes a suffix view
+            t.begin_a = n_hits == 0 ? v.xa - v.xb : last; t.end_a = v.xa - 1; t.begin_b = 0; t.end_b = v.xb - 1;
+        } else {
             t.force_start = true;
-            t.a_off = (a_slave ? eb : ea) + 1;
-            const u64 tl = (a_slave ? slen : mlen) - t.a_off;
-            t.begin_a = n_hits == 0 ? 0 : first; t.end_a = tl - 1;
-            t.begin_b = (a_slave ? ea : eb) + 1; t.end_b = (a_slave ? mlen : slen) - 1;
-            right_rev = a_slave;
+            t.begin_a = n_hits == 0 ? 0 : first; t.end_a = v.alen - v.a_off - 1; t.begin_b = v.xb + 1; t.end_b = v.blen - 1;
         }
     }
 
@@ -320,6 +324,9 @@ struct Machine {
         else enter_right_or_finalize();
     }
 
+    // left_rev / right_rev ("the slave was `a`") are set here, with the result they describe, not where the call is built: a
+    // tail that is skipped is never fed and keeps the `false` of after_main_good, and finalize() -- their only reader -- runs
+    // after every call that was built has been fed (or not at all: a failed call ends the machine in finish_bad).
     void feed(const gamdp_result& r)
     {
         if (audit && out->n_dp < audit_cap) audit[out->n_dp] = r;
@@ -335,10 +342,10 @@ struct Machine {
             try_rev = !try_rev;
             start_attempt();
         } else if (phase == LEFT) {
-            left = r;
+            left = r; left_rev = tail_view(LEFT).a_slave;
             enter_right_or_finalize();
         } else if (phase == RIGHT) {
-            right = r;
+            right = r; right_rev = tail_view(RIGHT).a_slave;
             finalize();
         }
     }
@@ -409,11 +416,17 @@ struct ChainRun {
     ChainRun() = default;
     ChainRun(const ChainRun&) = delete;
     ChainRun& operator=(const ChainRun&) = delete;
+    // the one place the events of a launch end: after finish(), or with the object (a launch that failed half-way included)
+    void drop_events()
+    {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        e0 = e1 = nullptr;
+    }
     ~ChainRun()
-    {   // (only on a path that skipped finish(): an exception between the launch and the join)
-        if (!launched) return;
-        (void)hipStreamSynchronize(stream);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    {
+        if (launched) (void)hipStreamSynchronize(stream);   // (only on a path that skipped finish(): an exception between the launch and the join)
+        drop_events();
     }
 
     bool ended(u32 q) const
@@ -430,7 +443,7 @@ struct ChainRun {
         bool ok = hipStreamSynchronize(stream) == hipSuccess;
         float k = 0, f = 0;
         if (ok) ok = hipEventElapsedTime(&k, e0, e1) == hipSuccess && hipEventElapsedTime(&f, c->ref_event, e0) == hipSuccess;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        drop_events();
         if (!ok) { c->set_error(std::string("chain kernel: ") + hipGetErrorString(hipGetLastError())); return GAMDP_EHIP; }
         *ms = k; *from_ref_ms = f;
         c->kernel_ms += k; c->kernel_launches++;
@@ -473,80 +486,76 @@ struct ChainRun {
     }
 };
 
-// Starts the launch (asynchronous).  `arena` = bytes its scratch slots may take.  Returns 0 (run.launched says whether there is
-// one: not for other bands, GAMDP_L1_ROUNDS=1, no merge block with a chain, or a frame too long for the arena) or an error code.
-int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const SeqSet* ss, const u32 band, const u64 arena, ChainRun& run)
+// The launch in steps (launch_main_chains below runs them in this order); steps 1, 2, 4 and 5 are plain host code.
+// 1. Select and order: the machines whose main chain goes to the device, longest chains first.
+//    A merge block with an empty slave frame (s_end < s_begin) stays with the round loop: the call of such a block that starts at
+//    slave base 0 has end_b = begin_b - 1 wrapped around (the reference computes it in unsigned long, PctgBuilder.cc:1669-1677),
+//    so its rows are bounded by the contig, not by the frame the scratch slots are sized for.
+struct ChainPick { u32 mi; u64 rows; u32 longest; };   // a machine, the rows of its chain (the sum of its slave frames), its longest slave frame: no call of the chain has more rows
+struct ChainSel {
+    std::vector<ChainPick> ch;
+    std::vector<u32> need_rc;   // the slave contigs (their reverse complements must be resident)
+    u64 n_blk = 0, n_tw = 0;
+    bool has_n = false;
+};
+ChainSel select_chains(const std::vector<Machine>& M, const SeqSet* ms, const SeqSet* ss)
 {
-    run.launched = false;
-    if (tuning().l1_rounds || band != 150) return 0;
-    // A merge block with an empty slave frame (s_end < s_begin) stays with the round loop: the call of such a block that
-    // starts at slave base 0 has end_b = begin_b - 1 wrapped around (the reference computes it in unsigned long,
-    // PctgBuilder.cc:1669-1677), so its rows are bounded by the contig, not by the frame the scratch slots below are sized for.
-    std::vector<u32> act;
+    ChainSel s;
     for (u32 i = 0; i < (u32)M.size(); i++) {
         if (M[i].phase != Machine::MAIN) continue;
+        const gamdp_mb_in& in = *M[i].in;
+        ChainPick p{i, 0, 1};
         bool empty_frame = false;
-        for (u32 k = 0; k < M[i].in->n_blocks; k++) empty_frame = empty_frame || M[i].in->blocks[k].s_end < M[i].in->blocks[k].s_begin;
-        if (!empty_frame) act.push_back(i);
-    }
-    if (act.empty()) return 0;
-    // longest chains first
-    std::vector<u64> w(act.size(), 0);
-    std::vector<u32> longest(act.size(), 1);   // its longest slave frame: no call of the chain has more rows
-    u64 n_blk = 0;
-    bool has_n = false;
-    std::vector<u32> need_rc;
-    for (size_t q = 0; q < act.size(); q++) {
-        const gamdp_mb_in& in = *M[act[q]].in;
         for (u32 k = 0; k < in.n_blocks; k++) {
             const int32_t sl = frame_len(in.blocks[k].s_begin, in.blocks[k].s_end);
-            w[q] += (u64)sl;
-            longest[q] = std::max<u32>(longest[q], (u32)sl);
+            empty_frame = empty_frame || in.blocks[k].s_end < in.blocks[k].s_begin;
+            p.rows += (u64)sl;
+            p.longest = std::max<u32>(p.longest, (u32)sl);
         }
-        n_blk += in.n_blocks;
-        has_n = has_n || ms->has_n[in.m_id] || ss->has_n[in.s_id];
-        need_rc.push_back((u32)in.s_id);
+        if (empty_frame) continue;
+        s.ch.push_back(p);
+        s.n_blk += in.n_blocks;
+        s.has_n = s.has_n || ms->has_n[in.m_id] || ss->has_n[in.s_id];
+        s.need_rc.push_back((u32)in.s_id);
     }
-    { int rc_ = ss->ensure_rc(need_rc, c); if (rc_) return rc_; }
-    std::vector<u32> order(act.size());
-    for (u32 q = 0; q < order.size(); q++) order[q] = q;
-    std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return w[x] > w[y]; });
-
-    // device: DevMB[] | DevBlk[] | ChainOut[] | DevResult audit[]      (the first two uploaded from h_chain)
-    // mirror: ChainOut[] | done flags | DevResult audit[]               (pinned, coherent; written by the chains as they end)
-    const u64 n_mb = act.size(), n_audit = 2 * n_blk;
-    auto up = [](u64 v) { return (v + 255) & ~255ull; };
+    std::stable_sort(s.ch.begin(), s.ch.end(), [](const ChainPick& x, const ChainPick& y) { return x.rows > y.rows; });
     // the longest chains get a twin workgroup for their second orientation (ChainSync, gamdp_dev.h): those within 1/8 of the
     // longest, at most 256 of them; GAMDP_L1_NO_TWINS=1: none
-    u64 n_tw = 0;
+    const u64 n_mb = s.ch.size();
     const u64 tw_cap = n_mb < 256 ? std::max<u64>(16, 256 - n_mb) : 256;   // (a small call: one workgroup per CU as long as that leaves room for a few)
     if (!tuning().l1_no_twins)
-        while (n_tw < n_mb && n_tw < tw_cap && w[order[n_tw]] * 8 >= w[order[0]] && w[order[n_tw]] >= 1024) n_tw++;
-    const u64 off_mb = 0, off_blk = up(off_mb + n_mb * sizeof(DevMB)), off_sync = up(off_blk + n_blk * sizeof(DevBlk)), off_out = up(off_sync + (n_tw + 1) * sizeof(ChainSync)),
-              off_aud = up(off_out + n_mb * sizeof(ChainOut)), off_win = up(off_aud + n_audit * sizeof(DevResult)), total = up(off_win + n_audit * sizeof(ChainWin));
-    const u64 mo_out = 0, mo_done = up(mo_out + n_mb * sizeof(ChainOut)), mo_aud = up(mo_done + n_mb * sizeof(u32)), mo_win = up(mo_aud + n_audit * sizeof(DevResult)),
-              mtotal = up(mo_win + n_audit * sizeof(ChainWin));
-    if (total > c->cap_chain) {
-        if (c->d_chain) (void)hipFree(c->d_chain);
-        c->d_chain = nullptr; c->cap_chain = 0;
-        if (hipMalloc(&c->d_chain, total + total / 4) != hipSuccess) { c->set_error("hipMalloc of the chain buffers failed"); return GAMDP_ENOMEM; }
-        c->cap_chain = total + total / 4;
+        while (s.n_tw < n_mb && s.n_tw < tw_cap && s.ch[s.n_tw].rows * 8 >= s.ch[0].rows && s.ch[s.n_tw].rows >= 1024) s.n_tw++;
+    return s;
+}
+
+// 2. Layout (byte offsets, each a multiple of 256).
+//    Ctx::d_chain:   DevMB[n_mb] | DevBlk[n_blk] | ChainSync[n_tw + 1] | ChainOut[n_mb] | DevResult audit[2 n_blk] | ChainWin[2 n_blk]
+//                    -- the first three, [0, out), are written on the host (Ctx::h_chain) and uploaded
+//    Ctx::h_mirror:  ChainOut[n_mb] | done flags u32[n_mb] | DevResult audit[2 n_blk] | ChainWin[2 n_blk]
+//                    -- pinned and coherent: written by the chains as they end
+struct ChainLayout {
+    u64 n_mb, n_audit;
+    u64 mb, blk, sync, out, aud, win, total;
+    u64 m_out, m_done, m_aud, m_win, m_total;
+    ChainLayout(const u64 n_mb_, const u64 n_blk, const u64 n_tw) : n_mb(n_mb_), n_audit(2 * n_blk)
+    {
+        auto up = [](u64 v) { return (v + 255) & ~255ull; };
+        mb = 0; blk = up(mb + n_mb * sizeof(DevMB)); sync = up(blk + n_blk * sizeof(DevBlk)); out = up(sync + (n_tw + 1) * sizeof(ChainSync));
+        aud = up(out + n_mb * sizeof(ChainOut)); win = up(aud + n_audit * sizeof(DevResult)); total = up(win + n_audit * sizeof(ChainWin));
+        m_out = 0; m_done = up(m_out + n_mb * sizeof(ChainOut)); m_aud = up(m_done + n_mb * sizeof(u32));
+        m_win = up(m_aud + n_audit * sizeof(DevResult)); m_total = up(m_win + n_audit * sizeof(ChainWin));
     }
-    if (off_out > c->cap_hchain) {
-        if (c->h_chain) (void)hipHostFree(c->h_chain);
-        c->h_chain = nullptr; c->cap_hchain = 0;
-        if (hipHostMalloc(&c->h_chain, off_out + off_out / 4) != hipSuccess) { c->set_error("hipHostMalloc of the chain buffers failed"); return GAMDP_ENOMEM; }
-        c->cap_hchain = off_out + off_out / 4;
-    }
-    if (mtotal > c->cap_mirror) {
-        if (c->h_mirror) (void)hipHostFree(c->h_mirror);
-        c->h_mirror = nullptr; c->cap_mirror = 0;
-        const u64 want = mtotal + mtotal / 4;
-        if (hipHostMalloc(&c->h_mirror, want, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { c->set_error("hipHostMalloc of the chain mirror failed"); return GAMDP_ENOMEM; }
-        c->cap_mirror = want;
-    }
-    void* d_mirror = nullptr;
-    if (hipHostGetDevicePointer(&d_mirror, c->h_mirror, 0) != hipSuccess) { c->set_error("hipHostGetDevicePointer failed"); return GAMDP_EHIP; }
+};
+
+// 3. Buffers: the three allocations of the layout (kept between calls, regrown with a quarter to spare: grow, grow_pinned), the
+//    chain stream, the flags cleared and a new epoch.  (No launch is running: frees are immediate.)
+int chain_buffers(Ctx* c, const ChainLayout& L, uint8_t*& d_mirror)
+{
+    int rc_ = grow(c, c->d_chain, c->cap_chain, L.total);
+    if (!rc_) rc_ = grow_pinned(c, c->h_chain, c->cap_hchain, L.out, hipHostMallocDefault);
+    if (!rc_) rc_ = grow_pinned(c, c->h_mirror, c->cap_mirror, L.m_total, hipHostMallocMapped | hipHostMallocCoherent);
+    if (rc_) return rc_;
+    if (hipHostGetDevicePointer((void**)&d_mirror, c->h_mirror, 0) != hipSuccess) { c->set_error("hipHostGetDevicePointer failed"); return GAMDP_EHIP; }
     if (!c->chain_stream) {
         // A stream of its own priority class: the runtime multiplexes the streams of one class over a few hardware queues, and a
         // round loop whose stream shares the chain launch's queue waits for the whole launch (measured: two of ten cohorts sat
@@ -557,20 +566,21 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
     }
     // the flags: cleared for every launch (the layout moves with the call's sizes, so what lies there may be an earlier call's
     // records), and raised to a value that changes from launch to launch
-    std::memset((uint8_t*)c->h_mirror + mo_done, 0, n_mb * sizeof(u32));
+    std::memset(c->h_mirror + L.m_done, 0, L.n_mb * sizeof(u32));
     if (++c->chain_epoch == 0) c->chain_epoch = 1;
-    uint8_t* const h = (uint8_t*)c->h_chain;
-    uint8_t* const d = (uint8_t*)c->d_chain;
-    uint8_t* const hm = (uint8_t*)c->h_mirror;
-    uint8_t* const dm = (uint8_t*)d_mirror;
-    DevMB* hmb = (DevMB*)(h + off_mb);
-    DevBlk* hbk = (DevBlk*)(h + off_blk);
-    run.q_of.assign(M.size(), ~0u);
+    return 0;
+}
+
+// 4. Describe: DevMB[] and DevBlk[] in the upload buffer, and which place of the launch each machine has
+void describe_chains(const std::vector<Machine>& M, const ChainSel& sel, const SeqSet* ms, const SeqSet* ss, DevMB* hmb, DevBlk* hbk,
+                     std::vector<u32>& q_of)
+{
+    q_of.assign(M.size(), ~0u);
     u32 blk_at = 0;
-    for (size_t q = 0; q < n_mb; q++) {
-        const Machine& m = M[act[order[q]]];
+    for (size_t q = 0; q < sel.ch.size(); q++) {
+        const Machine& m = M[sel.ch[q].mi];
         const gamdp_mb_in& in = *m.in;
-        run.q_of[act[order[q]]] = (u32)q;
+        q_of[sel.ch[q].mi] = (u32)q;
         DevMB& x = hmb[q];
         x.a2 = ms->fwd[in.m_id].p2; x.an = ms->fwd[in.m_id].pn;
         x.b2 = ss->fwd[in.s_id].p2; x.bn = ss->fwd[in.s_id].pn;
@@ -579,7 +589,7 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
         x.m_start = m.m_start; x.s_start = m.s_start; x.s_end = m.s_end;
         x.align_thr = m.align_thr;
         x.first_blk = blk_at; x.n_blocks = in.n_blocks; x.audit_first = 2 * blk_at;
-        x.rows = (u32)std::min<u64>(w[order[q]], 0x7fffffffu);
+        x.rows = (u32)std::min<u64>(sel.ch[q].rows, 0x7fffffffu);
         x.try_rev = m.try_rev ? 1u : 0u;
         x.has_n = (ms->has_n[in.m_id] || ss->has_n[in.s_id] || diag().force_n) ? 1u : 0u;
         x.npre_a = (size_t)in.m_id < ms->dev_npre.size() ? ms->dev_npre[in.m_id] : nullptr;
@@ -590,94 +600,125 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
         }
         blk_at += in.n_blocks;
     }
-    // Scratch: every workgroup goes round its own slots (chain_slots_per_workgroup()), sized
-    // for the longest call ITS chain can make (x_size <= its longest slave frame) -- a call of a 30 Mb genome has a few chains
-    // with frames of 100 kb and two thousand with frames of a few kb.  What does not fit the arena at once goes in pieces, one
-    // launch after the other over the same memory; twins only when everything fits at once.
+}
+
+// 5. Slots and pieces.  Every workgroup goes round its own scratch slots (chain_slots_per_workgroup(): k_chain2 has a filling
+//    and two walking wavefronts per merge block), sized for the longest call ITS chain can make (x_size <= its longest slave
+//    frame) -- a call of a 30 Mb genome has a few chains with frames of 100 kb and two thousand with frames of a few kb.  What
+//    does not fit the arena at once goes in pieces, one launch after the other over the same memory; twins only when everything
+//    fits at once.  Returns false when a frame is too long for the arena: the round loop peels such calls off by itself.
+struct ChainSlots {
+    std::vector<std::pair<u32, u32>> pieces;   // [first, first + count) of the list, each within the arena; slot offsets are relative to the piece
+    u64 need_scratch = 0, slotw_max = 0, n_tw = 0;   // u32 words; the twins that are left
+    u32 ypad = 0;
+};
+bool plan_slots(const ChainSel& sel, DevMB* hmb, const u32 band, const u64 arena, ChainSlots& S)
+{
+    const u64 n_mb = sel.ch.size();
     const u64 Y = 2ull * band + 1, LE = (Y - 1) / 5;
-    const u32 ypad = (u32)(((2 * band + 2 + 63) / 64) * 64);
+    const u32 ypad = S.ypad = (u32)(((2 * band + 2 + 63) / 64) * 64);
     const KernelInfo& ki = kernel_info[K_C5_CE0_N];
     const bool df = ki.dirfree;   // (the chain kernels' 5-column shape keeps a direction per cell: no checkpoint / boundary stores)
-    // k_chain2: a filling and two walking wavefronts per merge block
     const u64 per_wg = (u64)chain_slots_per_workgroup();
     const u64 arena_words = arena / sizeof(u32);
-    u64 words_all = 0, words_twins = 0, slotw_max = 0;
+    S.n_tw = sel.n_tw;
+    u64 words_all = 0, words_twins = 0;
     for (size_t q = 0; q < n_mb; q++) {
         DevMB& x = hmb[q];
-        const u64 nblk = ((u64)longest[order[q]] - 1 + LE) / 16 + 1;
+        const u64 nblk = ((u64)sel.ch[q].longest - 1 + LE) / 16 + 1;
         const u64 dirw = ((nblk * (u64)ki.dir_block_words + 63) / 64) * 64;
         const u64 ckptw = df ? (nblk / 4 + 2) * (u64)ki.ckpt_words : 0, bndw = df ? (nblk + 4) * (u64)ki.bnd_words : 0;
-        x.max_x = longest[order[q]];
+        x.max_x = sel.ch[q].longest;
         x.dir_words = dirw; x.slot_words = dirw + 4ull * ypad + ckptw + bndw;
         x.ckpt_off = df ? dirw + 4ull * ypad : 0; x.bnd_off = x.ckpt_off + ckptw;
-        slotw_max = std::max(slotw_max, x.slot_words);
+        S.slotw_max = std::max(S.slotw_max, x.slot_words);
         words_all += per_wg * x.slot_words;
-        if (q < n_tw) words_twins += per_wg * x.slot_words;
+        if (q < S.n_tw) words_twins += per_wg * x.slot_words;
     }
-    if (per_wg * slotw_max > arena_words) return 0;   // (a frame too long for the arena: the round loop peels such calls off by itself)
-    if (words_all + words_twins > arena_words) { n_tw = 0; words_twins = 0; }
-    // pieces: [first, first + count) of the list, each within the arena; slot offsets are relative to the piece
-    std::vector<std::pair<u32, u32>> pieces;
-    u64 need_scratch = 0;
-    {
-        u64 at = 0;
-        for (size_t q = 0; q < n_tw; q++) { hmb[q].slot_off[1] = at; at += per_wg * hmb[q].slot_words; }   // (the twins' workgroups come first in the grid)
-        u32 first = 0;
-        for (size_t q = 0; q < n_mb; q++) {
-            const u64 mine = per_wg * hmb[q].slot_words;
-            if (at + mine > arena_words) {   // (never with twins: then everything fits)
-                pieces.emplace_back(first, (u32)q - first);
-                need_scratch = std::max(need_scratch, at);
-                first = (u32)q; at = 0;
-            }
-            hmb[q].slot_off[0] = at;
-            if (q >= n_tw) hmb[q].slot_off[1] = 0;
-            at += mine;
+    if (per_wg * S.slotw_max > arena_words) return false;
+    if (words_all + words_twins > arena_words) S.n_tw = 0;
+    u64 at = 0;
+    for (size_t q = 0; q < S.n_tw; q++) { hmb[q].slot_off[1] = at; at += per_wg * hmb[q].slot_words; }   // (the twins' workgroups come first in the grid)
+    u32 first = 0;
+    for (size_t q = 0; q < n_mb; q++) {
+        const u64 mine = per_wg * hmb[q].slot_words;
+        if (at + mine > arena_words) {   // (never with twins: then everything fits)
+            S.pieces.emplace_back(first, (u32)q - first);
+            S.need_scratch = std::max(S.need_scratch, at);
+            first = (u32)q; at = 0;
         }
-        pieces.emplace_back(first, (u32)n_mb - first);
-        need_scratch = std::max(need_scratch, at);
+        hmb[q].slot_off[0] = at;
+        if (q >= S.n_tw) hmb[q].slot_off[1] = 0;
+        at += mine;
     }
-    if (need_scratch > c->cap_chain_scratch) {
-        if (c->d_chain_scratch) { (void)hipFree(c->d_chain_scratch); c->d_chain_scratch = nullptr; c->cap_chain_scratch = 0; }
-        if (hipMalloc(&c->d_chain_scratch, need_scratch * sizeof(u32)) != hipSuccess) { c->d_chain_scratch = nullptr; c->set_error("hipMalloc of the chains' scratch slots failed"); return GAMDP_ENOMEM; }
-        c->cap_chain_scratch = need_scratch;
-    }
+    S.pieces.emplace_back(first, (u32)n_mb - first);
+    S.need_scratch = std::max(S.need_scratch, at);
+    return true;
+}
+
+// 6. Enqueue: the kernel's parameters, what the host keeps of the launch (`run`), upload, the launches, the two events.
+int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const ChainSlots& S, uint8_t* const dm, const u32 band,
+                   const SeqSet* ms, const SeqSet* ss, ChainRun& run)
+{
+    uint8_t *const h = c->h_chain, *const d = c->d_chain, *const hm = c->h_mirror;
     ChainParams cp;
-    cp.mbs = (const DevMB*)(d + off_mb); cp.blks = (const DevBlk*)(d + off_blk); cp.n_mbs = (u32)n_mb;
-    cp.n_twins = (u32)n_tw; cp.sync = (ChainSync*)(d + off_sync);
-    std::memset(h + off_sync, 0, (n_tw + 1) * sizeof(ChainSync));
-    cp.cursor = nullptr; cp.audit = (DevResult*)(d + off_aud); cp.out = (ChainOut*)(d + off_out); cp.win = (ChainWin*)(d + off_win);
-    cp.scratch = c->d_chain_scratch; cp.ypad = ypad; cp.band = band;
-    cp.max_rows = (u32)std::min<u64>(std::max<u64>(1, w[order[0]]), 0x7fffffffu);
-    cp.host_out = (ChainOut*)(dm + mo_out); cp.host_done = (u32*)(dm + mo_done); cp.host_audit = (DevResult*)(dm + mo_aud); cp.host_win = (ChainWin*)(dm + mo_win);
+    cp.mbs = (const DevMB*)(d + L.mb); cp.blks = (const DevBlk*)(d + L.blk); cp.n_mbs = (u32)L.n_mb;
+    cp.n_twins = (u32)S.n_tw; cp.sync = (ChainSync*)(d + L.sync);
+    std::memset(h + L.sync, 0, (S.n_tw + 1) * sizeof(ChainSync));
+    cp.cursor = nullptr; cp.audit = (DevResult*)(d + L.aud); cp.out = (ChainOut*)(d + L.out); cp.win = (ChainWin*)(d + L.win);
+    cp.scratch = c->d_chain_scratch; cp.ypad = S.ypad; cp.band = band;
+    cp.max_rows = (u32)std::min<u64>(std::max<u64>(1, sel.ch[0].rows), 0x7fffffffu);
+    cp.host_out = (ChainOut*)(dm + L.m_out); cp.host_done = (u32*)(dm + L.m_done); cp.host_audit = (DevResult*)(dm + L.m_aud); cp.host_win = (ChainWin*)(dm + L.m_win);
     cp.epoch = c->chain_epoch;
     cp.skew_call = diag().chain_skew;
     // N by window: the chains pick the cell of every call by the bases it touches (+ 64 on either side, as the batch path does);
     // the diagnostics build's GAMDP_DIAG_FORCE_N: by the contigs' flags, as in rounds 3-4
     cp.n_margin = (int32_t)(64 - diag().n_window_shrink); cp.n_by_contig = diag().force_n ? 1u : 0u;
     run.n_by_contig = cp.n_by_contig != 0;
-    if (hipEventCreate(&run.e0) != hipSuccess) { c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
-    if (hipEventCreate(&run.e1) != hipSuccess) { (void)hipEventDestroy(run.e0); c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
-    if (diag().timing) std::fprintf(stderr, "gamdp chain: %zu merge blocks, %llu blocks, %zu piece(s), %.1f MB of scratch (slots of up to %llu words), %llu twins, has_n %d\n", (size_t)n_mb, (unsigned long long)n_blk, pieces.size(), need_scratch * 4e-6, (unsigned long long)slotw_max, (unsigned long long)n_tw, (int)has_n);
-    run.n_mb = n_mb; run.band = band; run.hmb = hmb; run.ms = ms; run.ss = ss;
-    run.hout = (const ChainOut*)(hm + mo_out); run.done = (const volatile u32*)(hm + mo_done); run.haud = (const DevResult*)(hm + mo_aud); run.hwin = (const ChainWin*)(hm + mo_win);
+    // (the events belong to `run` from here on: every path out leaves them to it)
+    if (hipEventCreate(&run.e0) != hipSuccess || hipEventCreate(&run.e1) != hipSuccess) { c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
+    if (diag().timing) std::fprintf(stderr, "gamdp chain: %zu merge blocks, %llu blocks, %zu piece(s), %.1f MB of scratch (slots of up to %llu words), %llu twins, has_n %d\n", (size_t)L.n_mb, (unsigned long long)sel.n_blk, S.pieces.size(), S.need_scratch * 4e-6, (unsigned long long)S.slotw_max, (unsigned long long)S.n_tw, (int)sel.has_n);
+    run.n_mb = L.n_mb; run.band = band; run.hmb = (const DevMB*)(h + L.mb); run.ms = ms; run.ss = ss;
+    run.hout = (const ChainOut*)(hm + L.m_out); run.done = (const volatile u32*)(hm + L.m_done); run.haud = (const DevResult*)(hm + L.m_aud); run.hwin = (const ChainWin*)(hm + L.m_win);
     run.epoch = cp.epoch; run.stream = c->chain_stream; run.dout = cp.out;
     run.t_launch = std::chrono::steady_clock::now();
-    bool ok = hipMemcpyAsync(d, h, off_out, hipMemcpyHostToDevice, c->chain_stream) == hipSuccess;
+    bool ok = hipMemcpyAsync(d, h, L.out, hipMemcpyHostToDevice, c->chain_stream) == hipSuccess;
     ok = ok && hipEventRecord(run.e0, c->chain_stream) == hipSuccess;
-    for (size_t pc = 0; ok && pc < pieces.size(); pc++) {   // (one launch unless the arena is too small for all the slots at once)
-        cp.first_mb = pieces[pc].first;
-        ok = launch_chain(cp, has_n || diag().force_n, (unsigned)(pieces[pc].second + n_tw), c->chain_stream) == 0;
+    for (size_t pc = 0; ok && pc < S.pieces.size(); pc++) {   // (one launch unless the arena is too small for all the slots at once)
+        cp.first_mb = S.pieces[pc].first;
+        ok = launch_chain(cp, sel.has_n || diag().force_n, (unsigned)(S.pieces[pc].second + S.n_tw), c->chain_stream) == 0;
     }
     ok = ok && hipEventRecord(run.e1, c->chain_stream) == hipSuccess;
     if (!ok) {
         (void)hipStreamSynchronize(c->chain_stream);
-        (void)hipEventDestroy(run.e0); (void)hipEventDestroy(run.e1);
         c->set_error(std::string("chain launch: ") + hipGetErrorString(hipGetLastError()));
         return GAMDP_EHIP;
     }
     run.launched = true;
-    for (u32 i : act) M[i].on_device = true;
+    return 0;
+}
+
+// Starts the launch (asynchronous).  `arena` = bytes its scratch slots may take.  Returns 0 (run.launched says whether there is
+// one: not for other bands, GAMDP_L1_ROUNDS=1, no merge block with a chain, or a frame too long for the arena) or an error code.
+int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const SeqSet* ss, const u32 band, const u64 arena, ChainRun& run)
+{
+    run.launched = false;
+    if (tuning().l1_rounds || band != 150) return 0;
+    const ChainSel sel = select_chains(M, ms, ss);
+    if (sel.ch.empty()) return 0;
+    int rc_ = ss->ensure_rc(sel.need_rc, c);
+    if (rc_) return rc_;
+    const ChainLayout L(sel.ch.size(), sel.n_blk, sel.n_tw);
+    uint8_t* d_mirror = nullptr;
+    if ((rc_ = chain_buffers(c, L, d_mirror))) return rc_;
+    DevMB* const hmb = (DevMB*)(c->h_chain + L.mb);
+    describe_chains(M, sel, ms, ss, hmb, (DevBlk*)(c->h_chain + L.blk), run.q_of);
+    ChainSlots slots;
+    if (!plan_slots(sel, hmb, band, arena, slots)) return 0;
+    // (the slots themselves: exactly what the pieces need -- the arena is a budget, a quarter to spare would overdraw it)
+    if ((rc_ = grow(c, c->d_chain_scratch, c->cap_chain_scratch, slots.need_scratch, true))) return rc_;
+    if ((rc_ = enqueue_chains(c, sel, L, slots, d_mirror, band, ms, ss, run))) return rc_;
+    for (const ChainPick& p : sel.ch) M[p.mi].on_device = true;
     return 0;
 }
 
@@ -688,8 +729,6 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
 // call: a chain kernel that derived a different window can not hand back a plausible wrong answer.
 int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi)
 {
-    static std::unordered_map<u32, std::vector<uint8_t>> no_cache;   // (never touched: the MAIN phase does not look at the slave's codes)
-    static std::mutex no_mu;
     const u32 q = run.q_of[mi];
     const DevMB& x = run.hmb[q];
     const u32 n_dp = run.hout[q].n_dp;
@@ -706,7 +745,7 @@ int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi)
     while (m.phase == Machine::MAIN) {
         if (used >= n_dp) { cc->set_error("internal: the device's chain of merge block " + std::to_string(mi) + " is shorter than the host's"); return GAMDP_EHIP; }
         ITask t;
-        m.pending(t, no_cache, no_mu);
+        m.pending(t);
         u64 X = 0, cells = 0;
         const int st = preflight(m.mlen, m.slen, run.band, t.begin_a, t.end_a, t.begin_b, t.end_b, false, false, &X, &cells);
         const ChainWin& w = run.hwin[x.audit_first + used];
@@ -740,6 +779,83 @@ struct CohortStats {
     std::vector<gamdp_l1_tail_call> tails;   // ... and the seed each gave its tail call
 };
 
+inline auto now() { return std::chrono::steady_clock::now(); }
+template <class T> double msec(T a, T b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+// A cohort with nothing to align while chains of its merge blocks (`waiting`) still run: waits a little for one of them.
+enum class Wait { NOTHING, AGAIN, FAILED };   // nothing to wait for / look again / the launch failed (error set)
+Wait wait_for_chain(Ctx* c, const ChainRun& run, const std::vector<u32>& waiting, bool& drained)
+{
+    if (waiting.empty()) return Wait::NOTHING;
+    // a launch that is over without every flag up has failed (`drained`: it is known to be over; then one more look at the flags)
+    if (drained) { c->set_error("internal: the chain launch ended without handing over merge block " + std::to_string(waiting[0])); return Wait::FAILED; }
+    const hipError_t qs = hipStreamQuery(run.stream);
+    if (qs == hipSuccess) { drained = true; return Wait::AGAIN; }
+    if (qs != hipErrorNotReady) { c->set_error(std::string("chain kernel: ") + hipGetErrorString(qs)); return Wait::FAILED; }
+    if (diag().timing && diag().build && std::chrono::duration<double>(now() - run.t_launch).count() > 5.0) {
+        run.dump(stderr);   // diagnostics build: a watchdog instead of a blind wait
+        std::_Exit(3);
+    }
+    for (int spin = 0; spin < 256; spin++) {
+        bool any = false;
+        for (u32 i : waiting) any = any || run.done[run.q_of[i]] == run.epoch;
+        if (any) break;
+        std::this_thread::yield();
+    }
+    return Wait::AGAIN;
+}
+
+// A tail alignment of a round: the findHits query that seeds it, and what the driver reads of the answer
+struct TailQuery { u32 mi; Machine::Phase side; u32 task; HitsReq req; };   // the machine, LEFT or RIGHT, the call it seeds in the round's batch
+struct Seed { u64 n_hits; u32 first, last; int source; };                   // source: GAMDP_L1_SEED_*
+inline Seed seed_of(const std::vector<uint32_t>& hits, const int source)
+{
+    return Seed{hits.size(), hits.empty() ? 0 : hits.front(), hits.empty() ? 0 : hits.back(), source};
+}
+
+// Answers the round's queries.  GAMDP_L1_HITS_HOST: find_hits on the host, query by query.  GAMDP_L1_HITS_DEVICE: ONE batch of
+// the hits kernels on this cohort's context and stream (find_hits_queries, summaries only); a query whose scratch does not fit
+// this cohort's share of the arena (HITS_UNFIT) is answered by the host; it never fails the call.
+int answer_tails(Ctx* c, const std::vector<Machine>& M, const std::vector<TailQuery>& tq, const bool device_hits, RcCache& rc_cache,
+                 gamdp_l1_hits_stats& hs, std::vector<Seed>& seeds)
+{
+    std::vector<uint32_t> hits;
+    auto on_host = [&](const TailQuery& q, const int source) {
+        const auto h0 = now();
+        M[q.mi].host_tail_hits(q.side, q.req, rc_cache, hits);
+        hs.host_hits_ms += msec(h0, now());
+        return seed_of(hits, source);
+    };
+    seeds.clear();
+    if (tq.empty()) return 0;
+    if (!device_hits) {
+        for (const TailQuery& q : tq) seeds.push_back(on_host(q, GAMDP_L1_SEED_HOST));
+        hs.host_queries += tq.size();
+        return 0;
+    }
+    std::vector<HitsReq> reqs;
+    for (const TailQuery& q : tq) reqs.push_back(q.req);
+    std::vector<gamdp_hits_result> res(tq.size(), gamdp_hits_result{});
+    std::vector<uint8_t> how(tq.size(), 0);
+    u32 n_launch = 0;
+    const int rc_ = find_hits_queries(c, reqs.data(), reqs.size(), res.data(), nullptr, nullptr, nullptr, how.data(), &hs.hits_kernel_ms, &n_launch);
+    if (rc_) return rc_;
+    hs.hits_launches += n_launch;
+    for (size_t k = 0; k < tq.size(); k++) {
+        if (how[k] == HITS_UNFIT) {
+            seeds.push_back(on_host(tq[k], GAMDP_L1_SEED_FALLBACK));
+            hs.host_fallback++;
+            continue;
+        }
+        const bool trivial = how[k] == HITS_TRIVIAL;
+        if (trivial && res[k].status != GAMDP_ST_OK) { c->set_error("internal: a tail's findHits view starts beyond its contig"); return GAMDP_EHIP; }
+        seeds.push_back(Seed{res[k].n_hits, res[k].first, res[k].last, trivial ? GAMDP_L1_SEED_TRIVIAL : GAMDP_L1_SEED_DEVICE});
+        if (!trivial && diag().hits_drop) seeds.back() = Seed{0, 0, 0, GAMDP_L1_SEED_DEVICE};   // diagnostics build: a wrong seed the tests must notice
+        (trivial ? hs.trivial_queries : hs.device_queries)++;
+    }
+    return 0;
+}
+
 // The round loop over one cohort of merge blocks on one context (= one host thread + one stream): every round collects the
 // pending find_alignment calls of its machines into ONE L0 batch, feeds the results back and advances the machines.  A
 // machine whose main chain is on the device (ChainRun) joins once its chain has ended and been replayed; until then the
@@ -747,50 +863,23 @@ struct CohortStats {
 // became ready while the last one was in flight.  Cohorts run concurrently: while one waits for its kernel, another builds
 // pending calls (findHits over contig tails, descriptor preparation) or feeds results -- host work hides behind GPU work.
 //
-// The tail alignments are seeded by findHits.  GAMDP_L1_HITS_HOST: inside Machine::pending, query by query.
-// GAMDP_L1_HITS_DEVICE (`hits_mode`, the owner context's: its helpers inherit it): a round first describes the queries of all
-// its machines (Machine::tail_query), runs them as ONE batch of the hits kernels on this cohort's context and stream
-// (find_hits_queries, summaries only), then builds the calls from (n_hits, first, last) (Machine::tail_task).  A query whose
-// scratch does not fit this cohort's share of the arena is answered by the host's find_hits; it never fails the call.
-void run_cohort(Ctx* c, std::vector<Machine>& M, const std::vector<u32>& ids, std::unordered_map<u32, std::vector<uint8_t>>& rc_cache,
-                std::mutex& rc_mu, CohortStats& st, const ChainRun* run, const int hits_mode)
+// The tail alignments are seeded by findHits: a round describes the queries of all its machines (Machine::tail_query), has them
+// answered (answer_tails: on the host or, `hits_mode` GAMDP_L1_HITS_DEVICE -- the owner context's, its helpers inherit it -- as
+// one batch on the device), then builds the calls from (n_hits, first, last) (Machine::tail_task).
+void run_cohort(Ctx* c, std::vector<Machine>& M, const std::vector<u32>& ids, RcCache& rc_cache, CohortStats& st, const ChainRun& run,
+                const int hits_mode)
 {
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto msec = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::vector<ITask> tasks;
     std::vector<u32> owner, first, waiting;
     std::vector<gamdp_result> res;
-    const bool device_hits = hits_mode == GAMDP_L1_HITS_DEVICE;
-    std::vector<HitsReq> hq;             // device mode: the round's findHits queries ...
-    std::vector<u32> hq_task;            // ... and the call each of them seeds
-    std::vector<Machine::Phase> hq_phase;
-    std::vector<gamdp_hits_result> hres;
-    std::vector<uint8_t> hhow;
-    std::vector<uint32_t> host_hits;
-    // a call of machine m in the phase it is in: a main-chain call, or a tail call (host mode: seeded at once; device mode: its
-    // query goes to the round's batch)
-    auto note_tail = [&](u32 mi, Machine::Phase ph, const ITask& t, int source) {
-        st.tails.push_back(gamdp_l1_tail_call{t.begin_a, mi, (uint8_t)(ph == Machine::RIGHT), (uint8_t)source, {0, 0}});
-    };
-    auto next_call = [&](u32 mi) {
-        Machine& m = M[mi];
+    std::vector<TailQuery> tq;
+    std::vector<Seed> seeds;
+    auto add_tail = [&](u32 mi, Machine::Phase side) {
+        tq.push_back(TailQuery{mi, side, (u32)tasks.size(), HitsReq{}});
+        M[mi].tail_query(side, tq.back().req);
         tasks.push_back(ITask{});
-        if (m.phase == Machine::MAIN) { m.pending(tasks.back(), rc_cache, rc_mu); return; }
-        st.hits.tail_queries++;
-        if (!device_hits) {
-            const auto h0 = now();
-            m.pending(tasks.back(), rc_cache, rc_mu);
-            st.hits.host_hits_ms += msec(h0, now());
-            st.hits.host_queries++;
-            note_tail(mi, m.phase, tasks.back(), GAMDP_L1_SEED_HOST);
-            return;
-        }
-        hq.push_back(HitsReq{});
-        m.tail_query(hq.back());
-        hq_task.push_back((u32)tasks.size() - 1);
-        hq_phase.push_back(m.phase);
     };
-    const bool chained = run && run->launched;
+    const bool chained = run.launched;
     if (chained)
         for (u32 i : ids)
             if (M[i].phase == Machine::MAIN && M[i].on_device) waiting.push_back(i);
@@ -800,8 +889,8 @@ void run_cohort(Ctx* c, std::vector<Machine>& M, const std::vector<u32>& ids, st
         if (!waiting.empty()) {
             size_t keep = 0;
             for (u32 i : waiting) {
-                if (run->ended(run->q_of[i])) {
-                    st.rc = replay_chain(c, *run, M[i], i);
+                if (run.ended(run.q_of[i])) {
+                    st.rc = replay_chain(c, run, M[i], i);
                     if (st.rc) return;
                 } else waiting[keep++] = i;
             }
@@ -810,72 +899,29 @@ void run_cohort(Ctx* c, std::vector<Machine>& M, const std::vector<u32>& ids, st
         owner.clear();
         for (u32 i : ids)
             if (M[i].phase != Machine::DONE && !(M[i].phase == Machine::MAIN && M[i].on_device)) owner.push_back(i);
-        if (owner.empty()) {
-            if (waiting.empty()) break;
-            // nothing to do until a chain ends; a launch that is over without every flag up has failed
-            if (drained) { c->set_error("internal: the chain launch ended without handing over merge block " + std::to_string(waiting[0])); st.rc = GAMDP_EHIP; return; }
-            const hipError_t qs = hipStreamQuery(run->stream);
-            if (qs == hipSuccess) { drained = true; continue; }
-            if (qs != hipErrorNotReady) { c->set_error(std::string("chain kernel: ") + hipGetErrorString(qs)); st.rc = GAMDP_EHIP; return; }
-            if (diag().timing && diag().build && std::chrono::duration<double>(now() - run->t_launch).count() > 5.0) {
-                run->dump(stderr);   // diagnostics build: a watchdog instead of a blind wait
-                std::_Exit(3);
-            }
-            for (int spin = 0; spin < 256; spin++) {
-                bool any = false;
-                for (u32 i : waiting) any = any || run->done[run->q_of[i]] == run->epoch;
-                if (any) break;
-                std::this_thread::yield();
-            }
+        if (owner.empty()) {   // nothing to do until a chain ends
+            const Wait w = wait_for_chain(c, run, waiting, drained);
+            if (w == Wait::NOTHING) break;
+            if (w == Wait::FAILED) { st.rc = GAMDP_EHIP; return; }
             continue;
         }
         // one call per machine -- two for a machine whose left AND right tails are due (independent of each other)
-        tasks.clear();
-        hq.clear(); hq_task.clear(); hq_phase.clear();
-        std::vector<u32> hq_owner;
+        tasks.clear(); tq.clear();
         first.assign(owner.size(), 0);
         for (size_t q = 0; q < owner.size(); q++) {
             Machine& m = M[owner[q]];
             first[q] = (u32)tasks.size();
-            const size_t hq0 = hq.size();
-            next_call(owner[q]);
-            if (m.phase == Machine::LEFT && m.right_follows_left()) {
-                m.phase = Machine::RIGHT;          // (pending() looks at the phase and the main chain's end points only)
-                next_call(owner[q]);
-                m.phase = Machine::LEFT;
-            }
-            hq_owner.resize(hq_owner.size() + (hq.size() - hq0), owner[q]);
+            if (m.phase == Machine::MAIN) { tasks.push_back(ITask{}); m.pending(tasks.back()); continue; }
+            add_tail(owner[q], m.phase);
+            if (m.phase == Machine::LEFT && m.right_follows_left()) add_tail(owner[q], Machine::RIGHT);
         }
-        if (!hq.empty()) {
-            hres.assign(hq.size(), gamdp_hits_result{});
-            hhow.assign(hq.size(), 0);
-            u32 n_launch = 0;
-            st.rc = find_hits_queries(c, hq.data(), hq.size(), hres.data(), nullptr, nullptr, nullptr, hhow.data(), &st.hits.hits_kernel_ms, &n_launch);
-            if (st.rc) return;
-            st.hits.hits_launches += n_launch;
-            for (size_t k = 0; k < hq.size(); k++) {
-                Machine& m = M[hq_owner[k]];
-                const Machine::Phase was = m.phase;
-                m.phase = hq_phase[k];
-                u64 n_hits = hres[k].n_hits; u32 h_first = hres[k].first, h_last = hres[k].last;
-                const int source = hhow[k] == HITS_UNFIT ? GAMDP_L1_SEED_FALLBACK : hhow[k] == HITS_TRIVIAL ? GAMDP_L1_SEED_TRIVIAL : GAMDP_L1_SEED_DEVICE;
-                if (hhow[k] == HITS_UNFIT) {
-                    const auto h0 = now();
-                    m.host_tail_hits(hq[k], rc_cache, rc_mu, host_hits);
-                    st.hits.host_hits_ms += msec(h0, now());
-                    st.hits.host_fallback++;
-                    n_hits = host_hits.size(); h_first = host_hits.empty() ? 0 : host_hits.front(); h_last = host_hits.empty() ? 0 : host_hits.back();
-                } else if (hhow[k] == HITS_TRIVIAL) {
-                    if (hres[k].status != GAMDP_ST_OK) { c->set_error("internal: a tail's findHits view starts beyond its contig"); st.rc = GAMDP_EHIP; return; }
-                    st.hits.trivial_queries++;
-                } else {
-                    st.hits.device_queries++;
-                    if (diag().hits_drop) { n_hits = 0; h_first = h_last = 0; }   // diagnostics build: a wrong seed the tests must notice
-                }
-                m.tail_task(tasks[hq_task[k]], n_hits, h_first, h_last);
-                note_tail(hq_owner[k], hq_phase[k], tasks[hq_task[k]], source);
-                m.phase = was;
-            }
+        st.hits.tail_queries += tq.size();
+        st.rc = answer_tails(c, M, tq, hits_mode == GAMDP_L1_HITS_DEVICE, rc_cache, st.hits, seeds);
+        if (st.rc) return;
+        for (size_t k = 0; k < tq.size(); k++) {
+            const TailQuery& q = tq[k];
+            M[q.mi].tail_task(q.side, tasks[q.task], seeds[k].n_hits, seeds[k].first, seeds[k].last);
+            st.tails.push_back(gamdp_l1_tail_call{tasks[q.task].begin_a, q.mi, (uint8_t)(q.side == Machine::RIGHT), (uint8_t)seeds[k].source, {0, 0}});
         }
         const auto t1 = now();
         res.assign(tasks.size(), gamdp_result{});
@@ -893,8 +939,158 @@ void run_cohort(Ctx* c, std::vector<Machine>& M, const std::vector<u32>& ids, st
         st.rounds++;
         if (diag().timing && chained)
             std::fprintf(stderr, "gamdp cohort %p: round %d at %.2f ms after the chain launch: %zu calls of %zu machines, pending %.2f ms, align %.2f ms, %zu still on the device\n",
-                         (void*)c, st.rounds, msec(run->t_launch, t0), tasks.size(), owner.size(), msec(t0, t1), msec(t1, t2), waiting.size());
+                         (void*)c, st.rounds, msec(run.t_launch, t0), tasks.size(), owner.size(), msec(t0, t1), msec(t1, t2), waiting.size());
     }
+}
+
+// ---- the entry point, step by step ----------------------------------------------------------------------------------------
+
+// 1. The machines of the call (argument checks included) and the predicted cells of each
+int build_machines(Ctx* c, const SeqSet* ms, const SeqSet* ss, const gamdp_mb_in* in, const size_t n, const u32 band, gamdp_mb_out* out,
+                   gamdp_result* audit, const u32 audit_stride, std::vector<Machine>& M, std::vector<u64>& weight)
+{
+    M.assign(n, Machine{});
+    weight.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        Machine& m = M[i];
+        m.in = &in[i]; m.out = &out[i]; m.ms = ms; m.ss = ss; m.band = band;
+        if (!ms->has_codes() || !ss->has_codes()) { c->set_error("merge blocks need sequence sets with host codes"); return GAMDP_EINVAL; }
+        if (in[i].m_id < 0 || in[i].s_id < 0 || (size_t)in[i].m_id >= ms->lens.size() || (size_t)in[i].s_id >= ss->lens.size()) {
+            c->set_error("merge block " + std::to_string(i) + ": contig id out of range");
+            return GAMDP_EINVAL;
+        }
+        m.mlen = ms->lens[in[i].m_id];
+        m.slen = ss->lens[in[i].s_id];
+        if (audit) { m.audit = audit + i * (size_t)audit_stride; m.audit_cap = audit_stride; }
+        m.init();
+        for (u32 k = 0; k < in[i].n_blocks && in[i].blocks; k++)
+            weight[i] += (u64)frame_len(in[i].blocks[k].s_begin, in[i].blocks[k].s_end) * (2ull * band + 1);
+    }
+    return 0;
+}
+
+// 2. Cohorts: host threads, each with its own context (stream, staging buffers, scratch arena) on this device; the merge
+// blocks are dealt by predicted cells (LPT), so the cohorts' chains have similar depth.  A round lasts as long as its
+// longest call, so smaller cohorts mean shorter rounds that overlap on the (nearly empty) GPU -- up to a point: 4 cohorts
+// of >= 48 merge blocks, up to 16 from ~1 500 merge blocks on (measured on the GAGE-shaped workloads when every call went
+// through this loop: 192 merge blocks 12.5 / 11.5 / 8.8 / 13.1 ms with 1 / 2 / 4 / 8 cohorts, 1 967 merge blocks 103 / 77 /
+// 60 / 54 / 63 ms with 1 / 2 / 4 / 8 / 12; with the main chains on the device only the tails are left, two rounds bound by
+// findHits on the host: 192 merge blocks 7.4 / 7.2 / 7.0 / 7.1 ms with 1 / 2 / 4 / 8, 1 967: 56 / 46 / 38 / 37 ms with
+// 2 / 4 / 8 / 16).  GAMDP_L1_HITS_DEVICE moves those findHits calls to the device, a round's as one batch: DESIGN.md section 6
+// has both modes side by side.
+// GAMDP_L1_COHORTS=k (<= 16) and GAMDP_L1_COHORT_MIN=m set the cap and the floor by hand.  Results do not depend on the
+// split: every machine only sees its own results.
+int cohort_count(const size_t n, const Tuning& t)
+{
+    const size_t forced = (size_t)t.l1_cohorts, cmin = t.l1_cohort_min;
+    return forced ? (int)std::max<size_t>(1, std::min<size_t>(forced, n / cmin))
+                  : (int)std::max<size_t>(1, std::max(std::min<size_t>(4, n / cmin), std::min<size_t>(16, n / (4 * cmin))));
+}
+
+// 3. The K cohort contexts (the owner and its first K - 1 helpers, which exist) share the device for this call: 1/K of the owner's
+// budget each, whatever was set or determined before -- or 1/2K while a chain launch runs beside them: half of the budget is for
+// its scratch slots (`chain_arena`).  Every path out of the call leaves arena_div = 1 behind.
+struct ArenaSplit {
+    Ctx* c; int K;
+    u64 chain_arena;
+    void drop_chain_scratch() { if (c->d_chain_scratch) { (void)hipFree(c->d_chain_scratch); c->d_chain_scratch = nullptr; c->cap_chain_scratch = 0; } }
+    void set(u32 div) { c->arena_div = div; for (int k = 1; k < K; k++) c->helpers[(size_t)k - 1]->arena_div = div; }
+    ArenaSplit(Ctx* c_, int K_) : c(c_), K(K_)
+    {
+        set(2u * (u32)K);
+        for (int k = 1; k < K; k++) {
+            Ctx* h = c->helpers[(size_t)k - 1];
+            h->arena_limit = c->arena_limit; h->arena_share = c->arena_share;
+            h->trim_scratch();
+        }
+        c->trim_scratch();
+        chain_arena = c->arena_limit / (2ull * (u64)(c->arena_share ? c->arena_share : 1));
+        if (c->cap_chain_scratch * sizeof(u32) > chain_arena) drop_chain_scratch();
+    }
+    // no chain launch after all (another band, GAMDP_L1_ROUNDS=1, no main chain to run, a frame too long for the slots): the
+    // round loops take the whole budget
+    void no_chains() { set((u32)K); drop_chain_scratch(); }
+    ~ArenaSplit() { set(1); }
+};
+
+// (see Ctx::defer_frees: on while a chain launch runs beside the K cohort contexts; what they outgrew is freed when the call is over)
+struct DeferFrees {
+    Ctx* c; int K;
+    void set(bool on) { c->defer_frees = on; for (int k = 1; k < K; k++) c->helpers[(size_t)k - 1]->defer_frees = on; }
+    ~DeferFrees() { set(false); c->flush_frees(); for (int k = 1; k < K; k++) c->helpers[(size_t)k - 1]->flush_frees(); }
+};
+
+// 5. The cohort threads: cohort k runs the round loop over ids[k] on its own context, the owner's thread takes cohort 0
+void run_cohorts(Ctx* c, const int K, std::vector<Machine>& M, const std::vector<std::vector<u32>>& ids, const ChainRun& run,
+                 std::vector<CohortStats>& cst, std::vector<std::vector<std::pair<float, float>>>& intervals)
+{
+    RcCache rc_cache;
+    auto body = [&](int k) noexcept {
+        Ctx* cc = k == 0 ? c : c->helpers[(size_t)k - 1];
+        if (k > 0) { cc->kernel_ms = 0; cc->kernel_launches = 0; cc->ref_event = c->ref_event; }
+        cc->interval_sink = &intervals[(size_t)k];
+        const int rc_k = guarded(cc, [&]() -> int {
+            if (hipSetDevice(cc->device) != hipSuccess) { cc->set_error("hipSetDevice failed"); return GAMDP_EHIP; }
+            run_cohort(cc, M, ids[(size_t)k], rc_cache, cst[(size_t)k], run, c->l1_hits_mode);
+            return 0;
+        });
+        if (rc_k && !cst[(size_t)k].rc) cst[(size_t)k].rc = rc_k;
+        cc->interval_sink = nullptr;
+        if (k > 0) cc->ref_event = nullptr;  // borrowed
+    };
+    Threads pool;   // joined on every path out, also when starting a later thread fails
+    for (int k = 1; k < K; k++) pool.start(body, k);
+    body(0);
+}
+
+// the time a set of intervals covers (sorts the list)
+double union_ms(std::vector<std::pair<float, float>>& iv)
+{
+    std::sort(iv.begin(), iv.end());
+    double sum = 0;
+    float lo = 0, hi = -1;
+    for (const auto& x : iv) {
+        if (hi < lo) { lo = x.first; hi = x.second; }
+        else if (x.first <= hi) hi = std::max(hi, x.second);
+        else { sum += hi - lo; lo = x.first; hi = x.second; }
+    }
+    return hi >= lo ? sum + (hi - lo) : sum;
+}
+
+// 6. The statistics of the call (gamdp_ctx_l1_stats, _l1_hits_stats, _l1_tail_calls); the helpers' kernel time is accounted to
+// the caller's context.  k0_ms / k0_n: the context's kernel time and launches when the call began.
+void collect_stats(Ctx* c, const size_t n, const gamdp_mb_out* out, const int K, const std::vector<CohortStats>& cst,
+                   const std::vector<std::vector<std::pair<float, float>>>& intervals, const bool chained, const float chain_at,
+                   const float chain_ms, const double k0_ms, const u64 k0_n)
+{
+    gamdp_l1_stats& S = c->last_l1;
+    S = gamdp_l1_stats{};
+    for (int k = 1; k < K; k++) { c->kernel_ms += c->helpers[(size_t)k - 1]->kernel_ms; c->kernel_launches += c->helpers[(size_t)k - 1]->kernel_launches; }
+    S.merge_blocks = n; S.cohorts = (uint32_t)K;
+    for (size_t i = 0; i < n; i++) { S.dp_calls += out[i].n_dp; S.cells += out[i].cells; }
+    gamdp_l1_hits_stats& H = c->last_l1_hits;
+    H = gamdp_l1_hits_stats{};
+    H.mode = (uint32_t)c->l1_hits_mode;
+    c->last_l1_tails.clear();
+    std::vector<std::pair<float, float>> all;
+    for (int k = 0; k < K; k++) {
+        const CohortStats& s = cst[(size_t)k];
+        const gamdp_l1_hits_stats& h = s.hits;
+        c->last_l1_tails.insert(c->last_l1_tails.end(), s.tails.begin(), s.tails.end());
+        H.tail_queries += h.tail_queries; H.device_queries += h.device_queries; H.trivial_queries += h.trivial_queries;
+        H.host_fallback += h.host_fallback; H.host_queries += h.host_queries; H.hits_launches += h.hits_launches;
+        H.hits_kernel_ms += h.hits_kernel_ms; H.host_hits_ms += h.host_hits_ms;
+        S.rounds = std::max<uint32_t>(S.rounds, (uint32_t)s.rounds + (chained ? 1u : 0u));
+        S.host_pending_ms += s.pending_ms; S.host_feed_ms += s.feed_ms;
+        all.insert(all.end(), intervals[(size_t)k].begin(), intervals[(size_t)k].end());
+    }
+    std::sort(c->last_l1_tails.begin(), c->last_l1_tails.end(), [](const gamdp_l1_tail_call& x, const gamdp_l1_tail_call& y) {
+        return x.merge_block != y.merge_block ? x.merge_block < y.merge_block : x.right < y.right;
+    });
+    if (chained) all.emplace_back(chain_at, chain_at + chain_ms);
+    S.launches = (uint32_t)(c->kernel_launches - k0_n);
+    S.kernel_sum_ms = c->kernel_ms - k0_ms;
+    S.gpu_busy_ms = union_ms(all);
 }
 
 }  // namespace
@@ -911,161 +1107,55 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
     if (band > GAMDP_MAX_BAND) { c->set_error("band exceeds GAMDP_MAX_BAND"); return GAMDP_ENOTSUP; }
     if (hipSetDevice(c->device) != hipSuccess) { c->set_error("hipSetDevice failed"); return GAMDP_EHIP; }
     return guarded(c, [&]() -> int {
-    const auto t_begin = std::chrono::steady_clock::now();
-    std::vector<Machine> M(n);
-    std::vector<u64> weight(n, 0);
-    for (size_t i = 0; i < n; i++) {
-        Machine& m = M[i];
-        m.in = &in[i]; m.out = &out[i]; m.ms = ms; m.ss = ss; m.band = band;
-        if (!ms->has_codes() || !ss->has_codes()) { c->set_error("merge blocks need sequence sets with host codes"); return GAMDP_EINVAL; }
-        if (in[i].m_id < 0 || in[i].s_id < 0 || (size_t)in[i].m_id >= ms->lens.size() || (size_t)in[i].s_id >= ss->lens.size()) {
-            c->set_error("merge block " + std::to_string(i) + ": contig id out of range");
-            return GAMDP_EINVAL;
+        const auto t_begin = now();
+        std::vector<Machine> M;
+        std::vector<u64> weight;
+        int rc_ = build_machines(c, ms, ss, in, n, band, out, audit, audit_stride, M, weight);
+        if (rc_) return rc_;
+        const double k0_ms = c->kernel_ms; const u64 k0_n = c->kernel_launches;
+        const int K = cohort_count(n, tuning());
+        while ((int)c->helpers.size() < K - 1) {
+            Ctx* h = new (std::nothrow) Ctx();
+            if (!h || h->init(c->device) != 0) { c->set_error("helper context: " + (h ? h->err : std::string("out of memory"))); delete h; return GAMDP_ENODEV; }
+            c->helpers.push_back(h);
         }
-        m.mlen = ms->lens[in[i].m_id];
-        m.slen = ss->lens[in[i].s_id];
-        if (audit) { m.audit = audit + i * (size_t)audit_stride; m.audit_cap = audit_stride; }
-        m.init();
-        for (u32 k = 0; k < in[i].n_blocks && in[i].blocks; k++)
-            weight[i] += (u64)frame_len(in[i].blocks[k].s_begin, in[i].blocks[k].s_end) * (2ull * band + 1);
-    }
-    const double k0_ms = c->kernel_ms; const u64 k0_n = c->kernel_launches;
-    // Cohorts: host threads, each with its own context (stream, staging buffers, scratch arena) on this device; the merge
-    // blocks are dealt by predicted cells (LPT), so the cohorts' chains have similar depth.  A round lasts as long as its
-    // longest call, so smaller cohorts mean shorter rounds that overlap on the (nearly empty) GPU -- up to a point: 4 cohorts
-    // of >= 48 merge blocks, up to 16 from ~1 500 merge blocks on (measured on the GAGE-shaped workloads when every call went
-    // through this loop: 192 merge blocks 12.5 / 11.5 / 8.8 / 13.1 ms with 1 / 2 / 4 / 8 cohorts, 1 967 merge blocks 103 / 77 /
-    // 60 / 54 / 63 ms with 1 / 2 / 4 / 8 / 12; with the main chains on the device only the tails are left, two rounds bound by
-    // findHits on the host: 192 merge blocks 7.4 / 7.2 / 7.0 / 7.1 ms with 1 / 2 / 4 / 8, 1 967: 56 / 46 / 38 / 37 ms with
-    // 2 / 4 / 8 / 16).  GAMDP_L1_HITS_DEVICE moves those findHits calls to the device, a round's as one batch: DESIGN.md section 6
-    // has both modes side by side.
-    // GAMDP_L1_COHORTS=k (<= 16) and GAMDP_L1_COHORT_MIN=m set the cap and the floor by hand.  Results do not depend on the
-    // split: every machine only sees its own results.
-    const int forced_cohorts = tuning().l1_cohorts;
-    const size_t cohort_min = tuning().l1_cohort_min;
-    const int K = forced_cohorts ? (int)std::max<size_t>(1, std::min<size_t>((size_t)forced_cohorts, n / cohort_min))
-                                 : (int)std::max<size_t>(1, std::max(std::min<size_t>(4, n / cohort_min), std::min<size_t>(16, n / (4 * cohort_min))));
-    while ((int)c->helpers.size() < K - 1) {
-        Ctx* h = new (std::nothrow) Ctx();
-        if (!h || h->init(c->device) != 0) { c->set_error("helper context: " + (h ? h->err : std::string("out of memory"))); delete h; return GAMDP_ENODEV; }
-        c->helpers.push_back(h);
-    }
-    // the K cohort contexts share the device for this call: 1/K of the owner's budget each, whatever was set or
-    // determined before (helpers that already exist included)
-    if (c->arena_budget(true) == 0) { c->set_error("hipMemGetInfo failed"); return GAMDP_EHIP; }
-    struct DivGuard {
-        Ctx* c; int K;
-        ~DivGuard() { c->arena_div = 1; for (int k = 1; k < K; k++) c->helpers[(size_t)k - 1]->arena_div = 1; }
-    } div_guard{c, K};
-    // (half of the budget for the chain launch's scratch slots, the other half for the K round loops beside it)
-    c->arena_div = 2u * (u32)K;
-    for (int k = 1; k < K; k++) {
-        Ctx* h = c->helpers[(size_t)k - 1];
-        h->arena_limit = c->arena_limit; h->arena_share = c->arena_share; h->arena_div = 2u * (u32)K;
-        h->trim_scratch();
-    }
-    c->trim_scratch();
-    const u64 chain_arena = c->arena_limit / (2ull * (u64)(c->arena_share ? c->arena_share : 1));
-    if (c->d_chain_scratch && c->cap_chain_scratch * sizeof(u32) > chain_arena) { (void)hipFree(c->d_chain_scratch); c->d_chain_scratch = nullptr; c->cap_chain_scratch = 0; }
-    std::vector<u32> part(n, 0);
-    if (K > 1) partition_lpt(weight.data(), n, K, part.data());
-    std::vector<std::vector<u32>> ids((size_t)K);
-    for (size_t i = 0; i < n; i++) ids[part[i]].push_back((u32)i);
-
-    if (!c->ref_event && hipEventCreate(&c->ref_event) != hipSuccess) { c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
-    if (hipEventRecord(c->ref_event, c->stream) != hipSuccess || hipEventSynchronize(c->ref_event) != hipSuccess) { c->set_error("hipEventRecord failed"); return GAMDP_EHIP; }
-    std::vector<std::vector<std::pair<float, float>>> intervals((size_t)K);
-    std::vector<CohortStats> cst((size_t)K);
-    std::unordered_map<u32, std::vector<uint8_t>> rc_cache;
-    std::mutex rc_mu;
-    // the main chains: one launch on the device, beside the round loops that take over what it hands back
-    ChainRun run;
-    {
-        const int rc_chain = launch_main_chains(c, M, ms, ss, band, chain_arena, run);
-        if (rc_chain) return rc_chain;
-    }
-    const bool chained = run.launched;
-    if (!chained) {
-        // no chain launch after all (another band, GAMDP_L1_ROUNDS=1, no main chain to run, a frame too long for the slots):
-        // the round loops get the whole budget, not the half that was kept for the launch's scratch slots
-        c->arena_div = (u32)K;
-        for (int k = 1; k < K; k++) c->helpers[(size_t)k - 1]->arena_div = (u32)K;
-        if (c->d_chain_scratch) { (void)hipFree(c->d_chain_scratch); c->d_chain_scratch = nullptr; c->cap_chain_scratch = 0; }
-    }
-    float chain_ms = 0, chain_at = 0;
-    struct FreeGuard {   // (see Ctx::defer_frees)
-        Ctx* c; int K;
-        void set(bool on) { c->defer_frees = on; for (int k = 1; k < K; k++) c->helpers[(size_t)k - 1]->defer_frees = on; }
-        ~FreeGuard() { set(false); c->flush_frees(); for (int k = 1; k < K; k++) c->helpers[(size_t)k - 1]->flush_frees(); }
-    } free_guard{c, K};
-    free_guard.set(chained);
-    auto body = [&](int k) noexcept {
-        Ctx* cc = k == 0 ? c : c->helpers[(size_t)k - 1];
-        if (k > 0) { cc->kernel_ms = 0; cc->kernel_launches = 0; cc->ref_event = c->ref_event; }
-        cc->interval_sink = &intervals[(size_t)k];
-        const int rc_k = guarded(cc, [&]() -> int {
-            if (hipSetDevice(cc->device) != hipSuccess) { cc->set_error("hipSetDevice failed"); return GAMDP_EHIP; }
-            run_cohort(cc, M, ids[(size_t)k], rc_cache, rc_mu, cst[(size_t)k], &run, c->l1_hits_mode);
-            return 0;
-        });
-        if (rc_k && !cst[(size_t)k].rc) cst[(size_t)k].rc = rc_k;
-        cc->interval_sink = nullptr;
-        if (k > 0) cc->ref_event = nullptr;  // borrowed
-    };
-    {
-        Threads pool;   // joined on every path out, also when starting a later thread fails
-        for (int k = 1; k < K; k++) pool.start(body, k);
-        body(0);
-    }
-    const int rc_fin = run.finish(c, &chain_at, &chain_ms);   // (also after an error in a cohort: the launch owns buffers of the context)
-    for (int k = 0; k < K; k++)
-        if (cst[(size_t)k].rc) {
-            if (k > 0) c->set_error(c->helpers[(size_t)k - 1]->err);
-            return cst[(size_t)k].rc;
-        }
-    if (rc_fin) return rc_fin;
-    // statistics of this call; the helpers' kernel time is accounted to the caller's context
-    gamdp_l1_stats& S = c->last_l1;
-    S = gamdp_l1_stats{};
-    for (int k = 1; k < K; k++) { c->kernel_ms += c->helpers[(size_t)k - 1]->kernel_ms; c->kernel_launches += c->helpers[(size_t)k - 1]->kernel_launches; }
-    S.merge_blocks = n; S.cohorts = (uint32_t)K;
-    for (size_t i = 0; i < n; i++) { S.dp_calls += out[i].n_dp; S.cells += out[i].cells; }
-    gamdp_l1_hits_stats& H = c->last_l1_hits;
-    H = gamdp_l1_hits_stats{};
-    H.mode = (uint32_t)c->l1_hits_mode;
-    c->last_l1_tails.clear();
-    for (int k = 0; k < K; k++) c->last_l1_tails.insert(c->last_l1_tails.end(), cst[(size_t)k].tails.begin(), cst[(size_t)k].tails.end());
-    std::sort(c->last_l1_tails.begin(), c->last_l1_tails.end(), [](const gamdp_l1_tail_call& x, const gamdp_l1_tail_call& y) {
-        return x.merge_block != y.merge_block ? x.merge_block < y.merge_block : x.right < y.right;
-    });
-    std::vector<std::pair<float, float>> all;
-    for (int k = 0; k < K; k++) {
-        const gamdp_l1_hits_stats& h = cst[(size_t)k].hits;
-        H.tail_queries += h.tail_queries; H.device_queries += h.device_queries; H.trivial_queries += h.trivial_queries;
-        H.host_fallback += h.host_fallback; H.host_queries += h.host_queries; H.hits_launches += h.hits_launches;
-        H.hits_kernel_ms += h.hits_kernel_ms; H.host_hits_ms += h.host_hits_ms;
-        S.rounds = std::max<uint32_t>(S.rounds, (uint32_t)cst[(size_t)k].rounds + (chained ? 1u : 0u));
-        S.host_pending_ms += cst[(size_t)k].pending_ms; S.host_feed_ms += cst[(size_t)k].feed_ms;
-        all.insert(all.end(), intervals[(size_t)k].begin(), intervals[(size_t)k].end());
-    }
-    if (chained) all.emplace_back(chain_at, chain_at + chain_ms);
-    S.launches = (uint32_t)(c->kernel_launches - k0_n);
-    S.kernel_sum_ms = c->kernel_ms - k0_ms;
-    std::sort(all.begin(), all.end());
-    float cur_lo = 0, cur_hi = -1;
-    for (auto& iv : all) {
-        if (cur_hi < cur_lo) { cur_lo = iv.first; cur_hi = iv.second; }
-        else if (iv.first <= cur_hi) cur_hi = std::max(cur_hi, iv.second);
-        else { S.gpu_busy_ms += cur_hi - cur_lo; cur_lo = iv.first; cur_hi = iv.second; }
-    }
-    if (cur_hi >= cur_lo) S.gpu_busy_ms += cur_hi - cur_lo;
-    S.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    if (gamdp::diag().timing)
-        std::fprintf(stderr, "gamdp_align_merge_blocks: %zu merge blocks, %d cohorts, %u rounds, %u launches: wall %.2f ms, GPU busy %.2f ms (kernels %.2f ms), pending %.2f ms, feed %.2f ms\n",
-                     n, K, S.rounds, S.launches, S.wall_ms, S.gpu_busy_ms, S.kernel_sum_ms, S.host_pending_ms, S.host_feed_ms);
-    return 0;
+        if (c->arena_budget(true) == 0) { c->set_error("hipMemGetInfo failed"); return GAMDP_EHIP; }
+        ArenaSplit arena(c, K);
+        std::vector<u32> part(n, 0);
+        if (K > 1) partition_lpt(weight.data(), n, K, part.data());
+        std::vector<std::vector<u32>> ids((size_t)K);
+        for (size_t i = 0; i < n; i++) ids[part[i]].push_back((u32)i);
+        // the reference point of the call's time line
+        if (!c->ref_event && hipEventCreate(&c->ref_event) != hipSuccess) { c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
+        if (hipEventRecord(c->ref_event, c->stream) != hipSuccess || hipEventSynchronize(c->ref_event) != hipSuccess) { c->set_error("hipEventRecord failed"); return GAMDP_EHIP; }
+        // the main chains: one launch on the device, beside the round loops that take over what it hands back
+        ChainRun run;
+        if ((rc_ = launch_main_chains(c, M, ms, ss, band, arena.chain_arena, run))) return rc_;
+        const bool chained = run.launched;
+        if (!chained) arena.no_chains();
+        DeferFrees defer{c, K};
+        defer.set(chained);
+        std::vector<std::vector<std::pair<float, float>>> intervals((size_t)K);
+        std::vector<CohortStats> cst((size_t)K);
+        run_cohorts(c, K, M, ids, run, cst, intervals);
+        float chain_ms = 0, chain_at = 0;
+        const int rc_fin = run.finish(c, &chain_at, &chain_ms);   // (also after an error in a cohort: the launch owns buffers of the context)
+        for (int k = 0; k < K; k++)
+            if (cst[(size_t)k].rc) {
+                if (k > 0) c->set_error(c->helpers[(size_t)k - 1]->err);
+                return cst[(size_t)k].rc;
+            }
+        if (rc_fin) return rc_fin;
+        collect_stats(c, n, out, K, cst, intervals, chained, chain_at, chain_ms, k0_ms, k0_n);
+        gamdp_l1_stats& S = c->last_l1;
+        S.wall_ms = msec(t_begin, now());
+        if (gamdp::diag().timing)
+            std::fprintf(stderr, "gamdp_align_merge_blocks: %zu merge blocks, %d cohorts, %u rounds, %u launches: wall %.2f ms, GPU busy %.2f ms (kernels %.2f ms), pending %.2f ms, feed %.2f ms\n",
+                         n, K, S.rounds, S.launches, S.wall_ms, S.gpu_busy_ms, S.kernel_sum_ms, S.host_pending_ms, S.host_feed_ms);
+        return 0;
     });
 }
+
 
 extern "C" int gamdp_ctx_set_l1_hits(gamdp_ctx* ctx, int mode)
 {
