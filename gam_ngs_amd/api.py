@@ -80,6 +80,14 @@ class Context:
         self.lib.gamdp_ctx_launch_info(self.handle, arr, n.value, C.byref(n))
         return [arr[i].as_dict() for i in range(n.value)]
 
+    def score_info(self):
+        """The launches of the last gamdp_score_batch call on this context, as dicts (gamdp_ctx_score_info)."""
+        n = C.c_size_t()
+        self.lib.gamdp_ctx_score_info(self.handle, None, 0, C.byref(n))
+        arr = (L.ScoreLaunchInfo * max(1, n.value))()
+        self.lib.gamdp_ctx_score_info(self.handle, arr, n.value, C.byref(n))
+        return [arr[i].as_dict() for i in range(n.value)]
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.gamdp_ctx_destroy(self.handle)
@@ -318,12 +326,9 @@ class BandedSmithWaterman:
                        want_ops=False) -> MyAlignment:
         return self.find_alignments([(a, begin_a, end_a, b, begin_b, end_b, force_start, force_end)], want_ops)[0]
 
-    def find_alignments(self, calls, want_ops=False, bands=None) -> List[MyAlignment]:
-        """calls: list of (a, begin_a, end_a, b, begin_b, end_b[, force_start[, force_end]]); all a's
-        must come from one SequenceSet and all b's from one SequenceSet."""
+    def _tasks(self, calls, bands):
+        """The gamdp_task array of a batch of calls and the two sequence sets they refer to."""
         n = len(calls)
-        if n == 0:
-            return []
         sa, sb = calls[0][0].seqset, calls[0][3].seqset
         tasks = (L.Task * n)()
         m64 = (1 << 64) - 1
@@ -338,6 +343,29 @@ class BandedSmithWaterman:
             t.a_rc, t.b_rc, t.force_start, t.force_end = int(a.rc), int(b.rc), int(fs), int(fe)
             t.band = self.band if bands is None else bands[i]
             t.begin_a, t.end_a, t.begin_b, t.end_b = begin_a & m64, end_a & m64, begin_b & m64, end_b & m64
+        return tasks, sa, sb
+
+    def find_scores(self, calls, bands=None):
+        """Score and end cell of every call without the traceback (gamdp_score_batch: a second, int32-only kernel that uses no
+        scratch arena): a list of (score, end_a, end_b, status, cells) for the calls find_alignments takes.  score, status and
+        cells equal those of find_alignments; (end_a, end_b) is the cell the alignment ends in."""
+        n = len(calls)
+        if n == 0:
+            return []
+        if isinstance(self.ctx, MultiContext):
+            raise L.GamdpError("find_scores is a single-context call")
+        tasks, sa, sb = self._tasks(calls, bands)
+        out = (L.ScoreResult * n)()
+        _check(self.ctx, self.ctx.lib.gamdp_score_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out), "gamdp_score_batch")
+        return [(r.score, r.end_a, r.end_b, r.status, r.cells) for r in out]
+
+    def find_alignments(self, calls, want_ops=False, bands=None) -> List[MyAlignment]:
+        """calls: list of (a, begin_a, end_a, b, begin_b, end_b[, force_start[, force_end]]); all a's
+        must come from one SequenceSet and all b's from one SequenceSet."""
+        n = len(calls)
+        if n == 0:
+            return []
+        tasks, sa, sb = self._tasks(calls, bands)
         out = (L.Result * n)()
         ops_struct = None
         # want_ops: one flag for the batch, or one per call (a capacity of 0 = no edit string for that call)

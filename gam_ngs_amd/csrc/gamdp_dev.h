@@ -294,4 +294,21 @@ int launch_align(int kid, const LaunchParams& p, unsigned n_slots, unsigned dyn_
 int launch_wide(const LaunchParams& p, unsigned n_slots, void* stream);   // K_WIDE (gamdp_wide.hip): n_slots workgroups
 constexpr int WIDE_WORKGROUPS_PER_CU = 8;
 
+// ---- score and end cell without the traceback (k_score, gamdp_score.hip; gamdp_score_batch) -----------------------------
+// What a wavefront leaves of a task, written as one 16-byte store.
+struct alignas(16) ScoreRec {
+    int32_t score, end_a, end_b;   // 0 unless the status is OK
+    u32 info;                      // bits 0-7 status (GAMDP_ST_*), bits 8.. the band columns per lane of the instantiation that ran
+};
+struct ScoreParams {
+    const DevTask* tasks;   // by decreasing rows; a2 .. flags and res_idx are read, the rest of a descriptor is not
+    u32 n_tasks;
+    u32* cursor;            // work-queue head (zeroed before the launch)
+    ScoreRec* results;      // indexed by DevTask::res_idx
+};
+int score_cols(u32 band);                    // band columns per lane of the instantiation a band takes: the smallest of 2, 3, 5, 9, 17 with 2*band+1 <= 64*C
+const char* score_kernel_name(int cols);     // as rocprofv3 prints it, e.g. "k_score<5>"
+int score_waves_per_cu(int cols);            // resident wavefronts per CU, from the occupancy the runtime reports
+int launch_score(int cols, const ScoreParams& p, unsigned n_wavefronts, void* stream);   // returns hipError_t as int
+
 }  // namespace gamdp

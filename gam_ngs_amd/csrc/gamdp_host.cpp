@@ -794,6 +794,24 @@ int Ctx::align_plan(u64 arena_call)
 
 // ---- staging, launching, collecting -------------------------------------------------------------------
 
+// Pinned staging for the task upload and the result download (pageable copies cost ~20 ms per 60 k tasks): room for `base` tasks
+// and results, and one more
+int Ctx::grow_staging(u64 base)
+{
+    if (base + 1 <= cap_pinned) return 0;
+    free_host(h_tasks);
+    free_host(h_results);
+    h_tasks = nullptr; h_results = nullptr; cap_pinned = 0;
+    const u64 want = base + base / 4 + 256;
+    if (hipHostMalloc(&h_tasks, want * sizeof(DevTask)) != hipSuccess ||
+        hipHostMalloc(&h_results, want * sizeof(DevResult)) != hipSuccess) {
+        set_error("hipHostMalloc of staging buffers failed");
+        return GAMDP_ENOMEM;
+    }
+    cap_pinned = want;
+    return 0;
+}
+
 // The padded task list of all launches in pinned memory (the last wavefront of a multi-task launch is filled up with copies of
 // its last task that write to the dump slot), sized from the finished plan -- however many launches the peeling made.
 int Ctx::align_stage(const AlignCall& a)
@@ -801,19 +819,7 @@ int Ctx::align_stage(const AlignCall& a)
     const Plan& plan = w_plan;
     int rc_ = grow(this, d_tasks, cap_tasks, plan.n_host_tasks + 1);
     if (rc_) return rc_;
-    // pinned staging for the task upload and the result download (pageable copies cost ~20 ms per 60 k tasks)
-    if (std::max<u64>(plan.n_host_tasks, a.n) + 1 > cap_pinned) {
-        free_host(h_tasks);
-        free_host(h_results);
-        h_tasks = nullptr; h_results = nullptr; cap_pinned = 0;
-        const u64 base = std::max<u64>(plan.n_host_tasks, a.n), want = base + base / 4 + 256;
-        if (hipHostMalloc(&h_tasks, want * sizeof(DevTask)) != hipSuccess ||
-            hipHostMalloc(&h_results, want * sizeof(DevResult)) != hipSuccess) {
-            set_error("hipHostMalloc of staging buffers failed");
-            return GAMDP_ENOMEM;
-        }
-        cap_pinned = want;
-    }
+    if ((rc_ = grow_staging(std::max<u64>(plan.n_host_tasks, a.n)))) return rc_;
     for (size_t li = 0; li < plan.launches.size(); li++) {
         const std::vector<u32>& cur = plan.items[li];
         const Launch& L = plan.launches[li];
@@ -1082,6 +1088,108 @@ int Ctx::align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_op
     return 0;
 }
 
+// ---- score and end cell without the traceback (gamdp_score_batch; the kernel: gamdp_score.hip) ---------------------------
+// The same checks, pre-checks and descriptors as align(); then one launch of k_score<C> per column count C the batch's bands take,
+// each over its tasks by decreasing rows.  No scratch arena, no planner: a wavefront needs nothing but its registers.
+int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out)
+{
+    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_EHIP; }
+    score_log.clear();
+    if (n == 0) return 0;
+    int rc_ = align_check(tasks, n);
+    if (rc_) return rc_;
+    for (size_t i = 0; i < n; i++) {
+        const u32 band = tasks[i].band;
+        if (band > GAMDP_MAX_TUNED_BAND) {
+            set_error("gamdp_score_batch: task " + std::to_string(i) + " has band " + std::to_string(band) + ", above GAMDP_MAX_TUNED_BAND");
+            return GAMDP_ENOTSUP;
+        }
+    }
+    if (w_prep.size() < n) { w_prep.resize(n); w_status.resize(n); w_key.resize(n); w_kid.resize(n); w_rows.resize(n); }
+    std::vector<int8_t> colsv(n);   // band columns per lane of the instantiation a task takes (-1: settled by the pre-checks)
+    parallel_for(n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            const int st = w_status[i] = prepare_task(tasks[i], w_prep[i]);
+            w_key[i] = w_prep[i].cells;
+            std::memset(&out[i], 0, sizeof(out[i]));
+            out[i].status = (uint8_t)st;
+            out[i].cells = w_prep[i].cells;
+            w_prep[i].dt.res_idx = (u32)i;
+            colsv[i] = st != GAMDP_ST_OK ? (int8_t)-1 : (int8_t)score_cols((u32)w_prep[i].dt.band);
+            w_rows[i] = st != GAMDP_ST_OK ? 0u : (u32)w_prep[i].dt.X;
+        }
+    });
+    // the launches: the tasks of every column count, longest first, one behind the other in the staged list
+    static const int COLS[] = {2, 3, 5, 9, 17};
+    struct SLaunch { int cols; u32 first, count, band_max; };
+    std::vector<SLaunch> launches;
+    std::vector<u32> order, g;
+    for (const int cols : COLS) {
+        g.clear();
+        u32 band_max = 0;
+        for (size_t i = 0; i < n; i++) if (colsv[i] == cols) { g.push_back((u32)i); band_max = std::max(band_max, (u32)w_prep[i].dt.band); }
+        if (g.empty()) continue;
+        sort_by_key_desc(g, w_rows, &w_sort_tmp, &w_sort_count);
+        launches.push_back({cols, (u32)order.size(), (u32)g.size(), band_max});
+        order.insert(order.end(), g.begin(), g.end());
+    }
+    if (launches.empty()) return 0;   // every task was settled by the pre-checks
+    // (the task and result staging of align(), the latter as raw memory: a ScoreRec is smaller than a DevResult)
+    static_assert(sizeof(ScoreRec) <= sizeof(DevResult), "score records are staged in the result buffers of align()");
+    if ((rc_ = grow(this, d_tasks, cap_tasks, order.size() + 1))) return rc_;
+    if ((rc_ = grow(this, d_results, cap_results, n + 1))) return rc_;
+    if ((rc_ = grow_staging(n))) return rc_;
+    ScoreRec* const d_rec = reinterpret_cast<ScoreRec*>(d_results);
+    ScoreRec* const h_rec = reinterpret_cast<ScoreRec*>(h_results);
+    parallel_for(order.size(), [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) h_tasks[k] = w_prep[order[k]].dt; });
+    HIPCHK(this, hipMemsetAsync(d_cursor, 0, launches.size() * sizeof(u32), stream));   // (cap_cursor >= 64 words)
+    HIPCHK(this, hipMemcpyAsync(d_tasks, h_tasks, order.size() * sizeof(DevTask), hipMemcpyHostToDevice, stream));
+    while (events.size() < launches.size()) {
+        hipEvent_t e0, e1;
+        HIPCHK(this, hipEventCreate(&e0));
+        HIPCHK(this, hipEventCreate(&e1));
+        events.push_back({e0, e1});
+    }
+    std::vector<u32> slots(launches.size());
+    for (size_t li = 0; li < launches.size(); li++) {
+        const SLaunch& L = launches[li];
+        ScoreParams p;
+        p.tasks = d_tasks + L.first; p.n_tasks = L.count; p.cursor = d_cursor + li; p.results = d_rec;
+        slots[li] = (u32)std::min<u64>(L.count, (u64)n_cu * (u64)score_waves_per_cu(L.cols));
+        HIPCHK(this, hipEventRecord(events[li].first, stream));
+        const int e = launch_score(L.cols, p, slots[li], stream);
+        if (e != 0) { set_error(std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)e)); return GAMDP_EHIP; }
+        HIPCHK(this, hipEventRecord(events[li].second, stream));
+    }
+    HIPCHK(this, hipMemcpyAsync(h_rec, d_rec, n * sizeof(ScoreRec), hipMemcpyDeviceToHost, stream));
+    HIPCHK(this, hipStreamSynchronize(stream));
+    parallel_for(n, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            if (colsv[i] < 0) continue;   // settled by the pre-checks
+            const ScoreRec& r = h_rec[i];
+            out[i].status = (uint8_t)(r.info & 0xFFu);
+            if (out[i].status != GAMDP_ST_OK) continue;
+            out[i].score = r.score;
+            out[i].end_a = (u64)(int64_t)r.end_a; out[i].end_b = (u64)(int64_t)r.end_b;
+        }
+    });
+    for (size_t li = 0; li < launches.size(); li++) {
+        const SLaunch& L = launches[li];
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, events[li].first, events[li].second) == hipSuccess) { kernel_launches++; kernel_ms += ms; }
+        gamdp_score_launch_info r;
+        std::memset(&r, 0, sizeof(r));
+        std::snprintf(r.kernel, sizeof(r.kernel), "%s", score_kernel_name(L.cols));
+        // the column count as the wavefronts wrote it into their records (0: they do not all say the same)
+        r.cols = h_rec[order[L.first]].info >> 8;
+        for (u32 k = 0; k < L.count; k++) if ((h_rec[order[L.first + k]].info >> 8) != r.cols) r.cols = 0;
+        r.tasks = L.count; r.slots = slots[li]; r.band_max = L.band_max;
+        r.kernel_ms = (double)ms;
+        score_log.push_back(r);
+    }
+    return 0;
+}
+
 // ---- batch pieces -------------------------------------------------------------------------------------
 
 // How gamdp_align_batch takes a batch of the caller's tasks (b operands in `sb`): whole (false), or in four pieces on two contexts,
@@ -1312,6 +1420,27 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     if (rc[1]) c->set_error(cc[1]->err);
     return rc[0] ? rc[0] : rc[1];
     });
+}
+
+int gamdp_score_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
+                      gamdp_score_result* out)
+{
+    if (!ctx || !set_a || !set_b || !out || (n && !tasks)) return GAMDP_EINVAL;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return guarded(c, [&]() -> int {
+        TaskSrc src;   // the caller's array, read in place
+        src.gt = tasks; src.sa = reinterpret_cast<const SeqSet*>(set_a); src.sb = reinterpret_cast<const SeqSet*>(set_b);
+        return c->score(src, n, out);
+    });
+}
+
+int gamdp_ctx_score_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n)
+{
+    if (!ctx || (cap && !out)) return GAMDP_EINVAL;
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    if (n) *n = c->score_log.size();
+    for (size_t i = 0; i < c->score_log.size() && i < cap; i++) out[i] = c->score_log[i];
+    return 0;
 }
 
 int gamdp_task_preflight(uint64_t alen, uint64_t blen, uint32_t band, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,

@@ -255,6 +255,10 @@ struct Ctx {
     int align_scratch(u64 arena_call);
     int align_run(AlignCall& a);
     void align_collect(AlignCall& a);
+    int grow_staging(u64 base);   // h_tasks / h_results
+    // gamdp_score_batch (gamdp_host.cpp; the kernel: gamdp_score.hip), and what its last call launched (gamdp_ctx_score_info)
+    int score(const TaskSrc& tasks, size_t n, gamdp_score_result* out);
+    std::vector<gamdp_score_launch_info> score_log;
     int align(const ITask* tasks, size_t n, gamdp_result* out, const gamdp_ops* ops) { TaskSrc s; s.it = tasks; return align(s, n, out, ops); }
     int align(const std::vector<ITask>& tasks, gamdp_result* out, const gamdp_ops* ops) { return align(tasks.data(), tasks.size(), out, ops); }
     ~Ctx();

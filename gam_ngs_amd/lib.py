@@ -23,7 +23,7 @@ SYMBOLS = [
     "gamdp_blocks_open", "gamdp_blocks_close", "gamdp_blocks_count", "gamdp_blocks_data", "gamdp_blocks_write",
     "gamdp_no_blocks_contigs", "gamdp_no_blocks_after_filter", "gamdp_pctgs_not_merged", "gamdp_fasta_write_selected",
     "gamdp_find_hits_batch", "gamdp_ctx_set_l1_hits", "gamdp_ctx_l1_hits_stats",
-    "gamdp_ctx_l1_tail_calls",
+    "gamdp_ctx_l1_tail_calls", "gamdp_score_batch", "gamdp_ctx_score_info",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
@@ -53,6 +53,23 @@ class Result(C.Structure):
         """Same tuple layout as the oracle's / golden vectors' keys."""
         return (self.status, self.begin_a, self.begin_b, self.score, self.n_match, self.length, self.first_a,
                 self.first_b, self.first_found, self.last_a, self.last_b, self.last_found, self.homology)
+
+
+class ScoreResult(C.Structure):
+    """gamdp_score_result: score and end cell of one find_alignment call (gamdp_score_batch)."""
+    _fields_ = [("score", C.c_int64), ("end_a", C.c_uint64), ("end_b", C.c_uint64), ("cells", C.c_uint64),
+                ("status", C.c_uint8), ("pad_", C.c_uint8 * 7)]
+
+
+class ScoreLaunchInfo(C.Structure):
+    """gamdp_score_launch_info: one kernel launch of the last gamdp_score_batch call."""
+    _fields_ = [("kernel", C.c_char * 24), ("cols", C.c_uint32), ("tasks", C.c_uint32), ("slots", C.c_uint32),
+                ("band_max", C.c_uint32), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = d["kernel"].decode()
+        return d
 
 
 class HitsTask(C.Structure):
@@ -194,6 +211,10 @@ def load_library():
     lib.gamdp_align_batch.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(Result), C.POINTER(Ops)]
     lib.gamdp_align_merge_blocks.argtypes = [vp, vp, vp, C.POINTER(MbIn), C.c_size_t, u32, C.POINTER(MbOut),
                                              C.POINTER(Result), u32]
+    lib.gamdp_score_batch.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(ScoreResult)]
+    lib.gamdp_score_batch.restype = C.c_int
+    lib.gamdp_ctx_score_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gamdp_ctx_score_info.restype = C.c_int
     lib.gamdp_task_preflight.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int, C.POINTER(u64)]
     lib.gamdp_ctx_l1_stats.argtypes = [vp, C.POINTER(L1Stats)]
     lib.gamdp_ctx_set_l1_hits.argtypes = [vp, C.c_int]

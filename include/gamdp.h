@@ -224,6 +224,45 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
 int gamdp_task_preflight(uint64_t alen, uint64_t blen, uint32_t band, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,
                          uint64_t end_b, int force_start, int force_end, uint64_t* cells);
 
+/* Score and end cell of BandedSmithWaterman(band).find_alignment(...) without the traceback: the fill
+ * (banded_smith_waterman.cc:80-171) and the end-cell search (:173-215).  score = MyAlignment::score()
+ * (max_score, :189/:207); (end_a, end_b) = the end cell's position in the a view and in b
+ * (pos = begin_a + max_i + max_j - band, begin_b + max_i); last_pos (my_alignment.cc:197-226) of the alignment
+ * the reference would return is (end_a + 1, end_b + 1). */
+typedef struct gamdp_score_result {
+    int64_t score;
+    uint64_t end_a, end_b;
+    uint64_t cells;          /* as gamdp_result.cells */
+    uint8_t status;          /* GAMDP_ST_*, equal to what gamdp_align_batch reports for the same task */
+    uint8_t pad_[7];
+} gamdp_score_result;        /* 40 bytes */
+/* Tasks as for gamdp_align_batch (reverse-complement and suffix views, a band per task); status, score and cells of every task equal
+ * those of its gamdp_result, the cases gamdp_task_preflight settles included, and GAMDP_ST_EMPTY (no end cell, :215) /
+ * GAMDP_ST_OUT_OF_RANGE (the end cell's pos >= |a|: the traceback's a.at(pos) throws) decided at the end cell.  For a status other
+ * than GAMDP_ST_OK score, end_a and end_b are 0.
+ * A second implementation, not a mode of the alignment kernels: every cell is computed in int32, one call per wavefront, by a kernel
+ * that shares no code with them.  It keeps no direction and no row of the matrix -- the end cell is searched while the cells are
+ * computed -- so the scratch arena (gamdp_ctx_set_arena_bytes) is NOT used: a batch too large for the arena can be scored, and a
+ * gamdp_align_batch run can be checked on the device it ran on (tools/score_crosscheck.py).  Exact arithmetic and no scratch are what
+ * it offers; it makes no promise of speed.
+ * GAMDP_EINVAL for NULL ctx / sets / out, NULL tasks with n > 0, ids out of range and reverse complements of a packed-only set (as
+ * gamdp_align_batch); n == 0 succeeds.  Bands above GAMDP_MAX_TUNED_BAND are not taken: a batch that holds one returns
+ * GAMDP_ENOTSUP as a whole (gamdp_last_error names the task; the context stays usable).  tasks must not change before the call
+ * returns.  The launches count toward gamdp_ctx_kernel_time; gamdp_ctx_launch_info keeps describing the last gamdp_align_batch. */
+int gamdp_score_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b,
+                      const gamdp_task* tasks, size_t n, gamdp_score_result* out);
+/* What the last gamdp_score_batch call on this context launched, in launch order: one launch per instantiation its bands take. */
+typedef struct gamdp_score_launch_info {
+    char kernel[24];         /* the instantiation, e.g. "k_score<5>" */
+    uint32_t cols;           /* band columns per lane, as the wavefronts of the launch reported it with their results (0: they differ) */
+    uint32_t tasks;          /* calls in the launch */
+    uint32_t slots;          /* resident wavefronts */
+    uint32_t band_max;       /* widest band among the calls */
+    double kernel_ms;        /* HIP events around the launch */
+} gamdp_score_launch_info;   /* 48 bytes */
+/* copies up to `cap` records to out (may be NULL when cap == 0); *n = how many launches the call made */
+int gamdp_ctx_score_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n);
+
 /* bit 0: this library is the diagnostics build (-DGAMDP_DIAG; honours the GAMDP_DIAG_* switches that change kernel
  * paths or invalidate results).  The product build returns 0 and ignores those switches. */
 unsigned gamdp_build_info(void);

@@ -1,0 +1,92 @@
+"""Cross-checks gamdp_align_batch against gamdp_score_batch on the device both ran on, and times them.
+
+gamdp_score_batch (gam_ngs_amd/csrc/gamdp_score.hip) computes score, status and cells of every call with a second kernel, in int32,
+that shares no code with the alignment kernels -- the packed-f16 ones included, whose exactness rests on a range argument only the
+diagnostics build asserts.  This tool runs both calls on one workload in one process, asserts that score,
+status and cells agree for every task, and prints one JSON line: the task count, the mismatches (must be 0), the kernels
+gamdp_align_batch launched, and each call's kernel time (gamdp_ctx_kernel_time) over --reps alternating repetitions.  It reads
+nothing but the package and tests/_mixed.py.
+
+Workloads:  --pairs N --len L --band B   N synthetic pairs of L bases (SequenceSet.synthetic), whole-sequence windows
+            --mixed N                    N calls shaped like the merge-block driver's (tests/_mixed.py), band --band (default 150)
+
+The planner switches of DESIGN.md section 6 apply to gamdp_align_batch as always (read once per process): with
+GAMDP_NO_PAIR=1 GAMDP_QUAD_MIN=1000000000 in the environment it stays on the one-task int32 kernels.
+
+Usage: python tools/score_crosscheck.py --pairs 4096 --len 50000 --band 150 [--reps 5] [--first-pair K]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import gam_ngs_amd as gam  # noqa: E402
+from gam_ngs_amd import lib as L  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=0)
+    ap.add_argument("--len", type=int, default=50000)
+    ap.add_argument("--band", type=int, default=150)
+    ap.add_argument("--mixed", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--first-pair", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=20261019)
+    args = ap.parse_args()
+    if bool(args.pairs) == bool(args.mixed):
+        ap.error("one of --pairs N or --mixed N")
+    ctx = gam.Context(0)
+    if args.mixed:
+        import _mixed
+        seqs, calls = _mixed.mixed_batch(args.seed, max(1, args.mixed // 8), 8, band=args.band)
+        n = len(calls)
+        sset = gam.SequenceSet(ctx, seqs, ascii=False)
+        tasks = (L.Task * n)()
+        _mixed.fill_tasks(tasks, calls)
+        workload = dict(workload="mixed", calls=n, band=args.band, seed=args.seed)
+    else:
+        n = args.pairs
+        sset = gam.SequenceSet.synthetic(ctx, args.first_pair, n, args.len)
+        tasks = (L.Task * n)()
+        for k in range(n):
+            t = tasks[k]
+            t.a_id, t.b_id, t.band = 2 * k, 2 * k + 1, args.band
+            t.begin_a, t.end_a, t.begin_b, t.end_b = 0, args.len - 1, 0, sset.lengths[2 * k + 1] - 1
+        workload = dict(workload="pairs", pairs=n, len=args.len, band=args.band)
+    res, sc = (L.Result * n)(), (L.ScoreResult * n)()
+    align_ms, score_ms = [], []
+    mismatches, first_bad = 0, None
+    for rep in range(args.reps + 1):   # (the first pass warms up: buffers, reverse complements, code objects)
+        ctx.kernel_time(reset=True)
+        rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res, None)
+        assert rc == 0, ("gamdp_align_batch", rc, ctx.last_error())
+        a_ms = ctx.kernel_time(reset=True)[0]
+        rc = ctx.lib.gamdp_score_batch(ctx.handle, sset.handle, sset.handle, tasks, n, sc)
+        assert rc == 0, ("gamdp_score_batch", rc, ctx.last_error())
+        s_ms = ctx.kernel_time(reset=True)[0]
+        if rep:
+            align_ms.append(a_ms)
+            score_ms.append(s_ms)
+        for i in range(n):
+            if (res[i].score, res[i].status, res[i].cells) != (sc[i].score, sc[i].status, sc[i].cells):
+                mismatches += 1
+                if first_bad is None:
+                    first_bad = dict(task=i, align=(res[i].score, res[i].status, res[i].cells), score=(sc[i].score, sc[i].status, sc[i].cells))
+    cells = sum(r.cells for r in res)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    rec = dict(workload, tasks=n, mismatches=mismatches, first_mismatch=first_bad, ok=sum(1 for r in res if r.status == 0), cells=cells,
+               align_kernels=sorted({r["kernel"] for r in ctx.launch_info()}), score_kernels=[r["kernel"] for r in ctx.score_info()],
+               align_kernel_ms=[round(v, 3) for v in align_ms], score_kernel_ms=[round(v, 3) for v in score_ms],
+               align_gcups=round(cells / med(align_ms) / 1e6, 1), score_gcups=round(cells / med(score_ms) / 1e6, 1))
+    print(json.dumps(rec), flush=True)
+    sset.close()
+    sys.exit(0 if mismatches == 0 else 1)
+
+
+if __name__ == "__main__":
+    main()
