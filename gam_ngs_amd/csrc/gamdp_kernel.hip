@@ -382,7 +382,7 @@ __device__ __forceinline__ void finish_many(const LaunchParams& p, const u32 fir
                         if (lane == 0) {
                             WalkCarry& w = wcs[s];
                             w.old_q = w.mat_q; w.old_lo = w.mat_lo; w.old_hi = w.mat_hi;
-                            w.mat_q = q_s; w.mat_hi = 4 * ghi_s + 3; w.mat_lo = max(4 * (ghi_s - (Strip<LPT, PK>::NB - 1)), lds_tk[s].df_lo);
+                            w.mat_q = q_s; w.mat_hi = 4 * ghi_s + 3; w.mat_lo = max(4 * (ghi_s - (Strip<LPT, PK>::groups_of(q_s) - 1)), lds_tk[s].df_lo);
                             w.mat_calls++;
                         }
                     }
@@ -416,7 +416,7 @@ __device__ __forceinline__ void run_pair(const LaunchParams& p, const u32 qi, u3
     u32* const sideA = slot + 2 * p.dir_words;
     Tk ta = make_tk(da, p, slot, sideA, slot);
     Tk tb = make_tk(db, p, slot + p.dir_words, sideA + 4u * p.ypad, slot);
-    ta.sshift = tb.sshift = strip_shift<C, Strip<64, true>::SL>(max(ta.band, tb.band));
+    ta.sshift = tb.sshift = strip_shift_of<C, 64, true>(max(ta.band, tb.band));
     const Plan pa = make_plan<C>(ta), pb = make_plan<C>(tb);
     // the packed range: fast blocks of BOTH tasks, whole groups of 4 blocks, at least one tagged fast block in front of it
     // for either task (what a lane receives at a group start must be its neighbour's plain last column)

@@ -27,27 +27,71 @@ enum { M_FAST = 0, M_TOP = 1, M_END = 2, M_BOTH = 3 };
 #ifndef GAMDP_OCTO_STRIP_LANES
 #define GAMDP_OCTO_STRIP_LANES 2
 #endif
+// The two-task packed kernel (round 7) keeps its 16 boundary slots and makes them the edges of strips of DIFFERENT widths: 2 lanes
+// where the alignments run (the band's middle: every call starts on column y = band), 4 and 8 lanes towards the band's outer
+// lanes, where no path of the workload goes.  A materialise() call on a 2-lane strip re-enacts 32 groups with the instructions the
+// 4-lane call spends on 16; the fill stores what it stored (same slots, same bytes, same flush) -- only WHICH lanes are edges
+// changes.  (Uniform 2-lane strips, rounds 3 and 4, needed 32 slots: 4 KB per block, a 4 KB staging area, fill +8 %.)
+// -DGAMDP_PAIR_STRIP_TABLE=0 brings the uniform 4-lane strips back (A/B: make pvariant).
+#ifndef GAMDP_PAIR_STRIP_TABLE
+#define GAMDP_PAIR_STRIP_TABLE 1
+#endif
+// The table, in u = wavefront lane + Tk::sshift (0 .. 64):  strip   0  1 |  2  3 |  4  5  6  7  8  9 10 11 | 12 13 | 14 15 | (16)
+//                                                           first u 0  8 | 16 20 | 24 26 28 30 32 34 36 38 | 40 44 | 48 56 | (64)
+//                                                           lanes      8 |     4 |                       2 |     4 |     8 |
+// (strip 16 exists with sshift = 1 only: the task's last lane, behind the band's last column; it stores what strip 15 consumes
+// from its right, in slot 0 -- which strip 0, whose first lane lies outside the task then, does not use -- and is never made.)
+struct PairStripTable {
+    static constexpr int N = 16;
+    static constexpr __host__ __device__ int first_of(const int q)
+    {
+        return q < 2 ? 8 * q : (q < 4 ? 16 + 4 * (q - 2) : (q < 12 ? 24 + 2 * (q - 4) : (q < 14 ? 40 + 4 * (q - 12) : 48 + 8 * (q - 14))));
+    }
+    static constexpr __host__ __device__ int width_of(const int q) { return (q < 2 || q >= 14) ? 8 : ((q < 4 || q >= 12) ? 4 : 2); }
+    static constexpr __host__ __device__ int strip_of(const int u)
+    {
+        return u < 16 ? u >> 3 : (u < 24 ? 2 + ((u - 16) >> 2) : (u < 40 ? 4 + ((u - 24) >> 1) : (u < 48 ? 12 + ((u - 40) >> 2) : 14 + ((u - 48) >> 3))));
+    }
+    static constexpr bool consistent()
+    {
+        for (int q = 0; q < N; ++q) {
+            const int w = width_of(q);
+            if (!(w == 2 || w == 4 || w == 8) || first_of(q) % w != 0 || first_of(q + 1) != first_of(q) + w) return false;   // aligned in a call's lane space, no gaps
+            for (int u = first_of(q); u < first_of(q) + w; ++u) if (strip_of(u) != q) return false;
+        }
+        return first_of(0) == 0 && first_of(N) == 64 && strip_of(64) == N;
+    }
+};
+static_assert(PairStripTable::consistent(), "at most 16 strips of 2, 4 and 8 lanes, every lane in exactly one");
+
 template <int LPT, bool PK = false>
 struct Strip {
+    static constexpr bool TABLE = PK && LPT == 64 && GAMDP_PAIR_STRIP_TABLE;   // strips of different widths (PairStripTable)
     static constexpr int SL = PK ? ((LPT == 64) ? GAMDP_PAIR_STRIP_LANES : GAMDP_OCTO_STRIP_LANES)
-                                 : ((LPT == 64) ? GAMDP_STRIP_LANES : GAMDP_QUAD_STRIP_LANES);  // lanes per strip
+                                 : ((LPT == 64) ? GAMDP_STRIP_LANES : GAMDP_QUAD_STRIP_LANES);  // lanes per strip (TABLE: lanes per boundary slot on average)
     static constexpr int SLOG = (SL == 4) ? 2 : 1;
-    static constexpr int NB = 64 / SL;                 // boundaries per row-time = groups re-enacted per materialise() call
+    static constexpr int NB = 64 / SL;                 // boundaries per row-time (slots); uniform strips: also the groups re-enacted per materialise() call
+    static constexpr int WMIN = TABLE ? 2 : SL, WMAX = TABLE ? 8 : SL;   // the widths materialise() is instantiated for
     // boundary words per block: [slot NB][received | handed][row-time 16], where slot q holds what strip q consumes: the
-    // values lane SL*q received from its left neighbour and the values lane SL*(q+1) handed to ITS left neighbour -- one
+    // values its first lane received from its left neighbour and the values the first lane of strip q+1 handed to ITS left neighbour -- one
     // contiguous piece per strip and block (FI = 16 row-times per flush: a block is ONE piece of [slot][received | handed][16]).
     static constexpr int FI = 16;   // (round 5: the eight-task kernel too flushes once per block -- whole 128 B lines per slot; until then its 2 KB staging area went out every 8 row-times and a strip's 16 row-times of a block lay in two lines)
     static constexpr u32 BND_WORDS = 2u * NB * 16u;
     static_assert(SL == 2 || SL == 4, "strips are 2 or 4 lanes wide");
+    static_assert(!TABLE || NB == PairStripTable::N, "the table's strips are the 16 boundary slots of the 4-lane format");
     static __device__ __forceinline__ u32* staging() { return (LPT == 64) ? s_bnd_full : s_qbnd; }
-    // Where the strips begin (Tk::sshift = sh, wave-uniform): strip q = wavefront lanes SL*q - sh .. SL*q - sh + SL-1, so that
+    // Where the strips begin (Tk::sshift = sh, wave-uniform): strip q = wavefront lanes first_of(q) - sh .. + width_of(q) - 1 (uniform
+    // strips: SL*q - sh .. SL*q - sh + SL-1), so that
     // the middle of the band -- where an alignment that starts at (begin_a, begin_b) runs, give or take its net indels --
     // lies in the middle of a strip and not, as column 150 of 301 did with 19 columns per lane, two columns from a strip's
     // edge (a walk that keeps changing sides there has both strips re-created for every row).  A strip at the edge of a task
     // has lanes that belong to the neighbouring task or to nobody: materialise() leaves those alone.
-    static __device__ __forceinline__ int strip_of(const int wlane, const int sh) { return (wlane + sh) >> SLOG; }          // 0 .. NB
-    static __device__ __forceinline__ bool opens_strip(const int wlane, const int sh) { return ((wlane + sh) & (SL - 1)) == 0; }
-    static __device__ __forceinline__ u32 slot_of(const int wlane, const int sh) { return (u32)(((wlane + sh) >> SLOG) & (NB - 1)); }   // where the lane that opens a strip stores
+    static __device__ __forceinline__ int strip_of(const int wlane, const int sh) { return TABLE ? PairStripTable::strip_of(wlane + sh) : (wlane + sh) >> SLOG; }   // 0 .. NB
+    static __device__ __forceinline__ int first_of(const int strip) { return TABLE ? PairStripTable::first_of(strip) : SL * strip; }   // its first lane + sh
+    static __device__ __forceinline__ int width_of(const int strip) { return TABLE ? PairStripTable::width_of(strip) : SL; }
+    static __device__ __forceinline__ int groups_of(const int strip) { return 64 / width_of(strip); }   // groups re-enacted per materialise() call
+    static __device__ __forceinline__ bool opens_strip(const int wlane, const int sh) { return TABLE ? first_of(strip_of(wlane, sh)) == wlane + sh : ((wlane + sh) & (SL - 1)) == 0; }
+    static __device__ __forceinline__ u32 slot_of(const int wlane, const int sh) { return (u32)(strip_of(wlane, sh) & (NB - 1)); }   // where the lane that opens a strip stores
     // word offset, inside a block's boundary image, of row-time r (0..15) of half h (0 received, 1 handed) of the lane
     // that opens strip `strip` (its handed values are in the slot of the strip to its left; strip 0's wrap to a slot
     // half nobody reads)
@@ -75,6 +119,16 @@ __device__ __forceinline__ int strip_shift(const int band)
         if (d < best_d) { best_d = d; best = sh; }
     }
     return best;
+}
+// ... and for the strips of Strip<LPT, PK>: the table's middle strips are 2 lanes wide, the shift is what puts the middle column mid-strip there
+template <int C, int LPT, bool PK>
+__device__ __forceinline__ int strip_shift_of(const int band)
+{
+    typedef Strip<LPT, PK> ST;
+    if constexpr (ST::TABLE) {
+        static_assert(C == 17, "the table is laid out for band 512 at 17 columns per lane: the middle column in lane 30, strips 2 lanes wide from lane 23 to 38");
+        return strip_shift<C, 2>(band);
+    } else return strip_shift<C, ST::SL>(band);
 }
 // (5 columns per lane -- band 150, one task per wavefront -- keeps a direction per cell: a direction-free variant was built and measured
 // in round 3 and is not worth a second kernel instance; tools/experiments/instrumentation/ has it as a patch.)

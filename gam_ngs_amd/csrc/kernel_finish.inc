@@ -133,7 +133,6 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
     const int lane_base = (LPT == 64) ? 0 : uni(lane_base_);
     const int pk_half = PK ? uni(pk_half_) : 0;
     typedef Strip<LPT, PK> ST;
-    constexpr int NB = ST::NB;
     const Tk t = load_uniform(tp);
     const DevTask* dtp = unip(dtp_);
     const u32 dt_flags = (u32)uni((int)dtp->flags) & TF_LIVE_MASK, dt_res_idx = (u32)uni((int)dtp->res_idx);
@@ -185,7 +184,7 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
             // lower indices, so one refill (one coalesced 256 B load) covers the next ~1000 bases.
             int64_t sa_w0 = INT64_MIN, sb_w0 = INT64_MIN, san_w0 = INT64_MIN, sbn_w0 = INT64_MIN;
             u32 sa_v = 0, sb_v = 0, san_v = 0, sbn_v = 0;  // (the N-plane windows only exist in the N-aware kernels)
-            // strip of direction-free blocks whose directions materialise() has produced: lanes 4*mat_q .. +3, blocks
+            // strip of direction-free blocks whose directions materialise() has produced: the lanes of strip mat_q (Strip::first_of, width_of), blocks
             // mat_lo .. mat_hi
             int mat_q = uni(wcp->mat_q), mat_lo = uni(wcp->mat_lo), mat_hi = uni(wcp->mat_hi), mat_calls = uni(wcp->mat_calls);
             int old_q = uni(wcp->old_q), old_lo = uni(wcp->old_lo), old_hi = uni(wcp->old_hi);  // the strip materialised before that one
@@ -219,7 +218,7 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                                 __builtin_amdgcn_s_waitcnt(0);
                                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                                 old_q = mat_q; old_lo = mat_lo; old_hi = mat_hi;
-                                mat_q = ST::strip_of(lane_base + l_, t.sshift); mat_hi = 4 * g_hi + 3; mat_lo = max(4 * (g_hi - (NB - 1)), t.df_lo);
+                                mat_q = ST::strip_of(lane_base + l_, t.sshift); mat_hi = 4 * g_hi + 3; mat_lo = max(4 * (g_hi - (ST::groups_of(mat_q) - 1)), t.df_lo);
                                 mat_calls++;
                             }
                             cvalid_lo = (mat_lo == t.df_lo) ? 0 : mat_lo;  // below df_lo the tagged blocks are all there
@@ -240,7 +239,7 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                     // timing diagnostics: with GAMDP_DIAG_COUNT_MAT as well, do the strip materialisations a walk down
                     // the middle of the band would ask for, and nothing else
                     if (dt_flags & TF_DIAG_COUNT_MAT)
-                        for (int g_hi = (t.df_hi >> 2) - 1; g_hi >= (t.df_lo >> 2); g_hi -= NB)
+                        for (int g_hi = (t.df_hi >> 2) - 1; g_hi >= (t.df_lo >> 2); g_hi -= ST::groups_of(ST::strip_of(lane_base + (Y / 2) / C, t.sshift)))
                             materialise_auto<C, (DIRFREE_OK<CE, C, HASN> ? CE : 0), HASN, LPT, PK>(tp, ST::strip_of(lane_base + (Y / 2) / C, t.sshift), g_hi, lane, pk_half, lane_base);
                 }
                 x = -1;

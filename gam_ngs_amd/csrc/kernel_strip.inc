@@ -1,11 +1,15 @@
-// Part of gamdp_kernel.hip (included inside namespace gamdp::{anonymous}): materialise(): the direction words of an SL-lane strip, re-created on demand for the walk.
+// Part of gamdp_kernel.hip (included inside namespace gamdp::{anonymous}): materialise(): the direction words of a strip of 2, 4 or 8 lanes, re-created on demand for the walk.
 
-// ---- directions of a strip (SL = 4 or 2 lanes), on demand ----------------------------------------------------
-// Re-enacts lanes SL*q - sshift .. SL*q - sshift + SL-1 of the sweep over 64/SL groups (64 row-times each) at once -- lanes SL*k .. of this
+// ---- directions of a strip (SW = 2, 4 or 8 lanes), on demand ----------------------------------------------------
+// Re-enacts the SW lanes of strip q (Strip::first_of(q) - sshift on: SW*q - sshift .. with uniform strips) of the sweep over 64/SW
+// groups (64 row-times each) at once -- lanes SW*k .. of this
 // wavefront do group g_hi-k -- from what do_block_df / pair_range stored, this time with the tagged cell, and writes the
 // direction words of those lanes exactly where the tagged fill would have put them.  The walk (finish_walk, walk_many)
 // calls it when it enters direction-free blocks whose strip is not there yet; an alignment path drifts sideways only by
 // its net indel count, so nearly every call serves 1 000 (4-lane strips) or 2 000 (2-lane strips) rows of path.
+// SW: the width of the strip, a template parameter -- the two-task kernel's strips differ in width (PairStripTable, kernel_fill.inc),
+// every other kernel's are Strip::SL wide.  Strips are aligned in the call's own lane space (lane & (SW - 1) = the lane's place in
+// its strip), whatever sshift says about the fill's lanes.
 // (Four tasks per wavefront: q counts strips across the whole wavefront; the lane geometry inside the task is R & 15.  *tp holds
 // the values of the task the walk is in, in every lane.)
 // PK = the packed stores of the two-task kernels (kernel_pair.inc): f16 pairs relative to per-lane bases; HALF says
@@ -13,13 +17,13 @@
 // the same sweep.
 // TOP: some of the groups hold packed top blocks (pair_top_range): the pos == -1 cell of a row is forced to H = 0 after it has
 // been computed, exactly as do_block<M_TOP> does it (the cells further left hold whatever: they only ever feed each other).
-// Strips begin sshift lanes before a multiple of SL (Strip::strip_of): the first and the last strip of a task then have lanes
+// Strips begin sshift lanes before where Strip::first_of puts them (a multiple of SL with uniform strips): the first and the last strip of a task then have lanes
 // that belong to the task next door or to nobody.  lane_base_ = the task's first wavefront lane; such a lane re-enacts its
 // neighbour inside the task once more and stores nothing; the task's first lane takes NEG from its left as in the fill (its
 // outside neighbour does not stay dead: it takes that lane's column 0 as an `up` source), its last lane may take anything from
 // its right (that feeds the columns behind the band's last one only, whose way back is cut at column CE of lane LE).
 // HALF (PK only): which task of the pair, compile-time -- the half-word select of every conversion is then part of the conversion.
-template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool TOP = false, int HALF = 0>
+template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool TOP = false, int HALF = 0, int SW = Strip<LPT, PK>::SL>
 __device__ __forceinline__ void materialise_impl(const Tk* tp, const int q_, const int g_hi_, const int lane, const int lane_base_ = 0)
 {
     static_assert((CE < 0 || CE < C - 1) && C - 1 <= 32, "the edge column inside a lane (tuned kernels) or a runtime one (CE < 0: the generic kernels)");
@@ -28,18 +32,21 @@ __device__ __forceinline__ void materialise_impl(const Tk* tp, const int q_, con
     constexpr bool RT_EDGE = (CE == -1);
     constexpr int HR = 8;  // row-times per unrolled chunk
     typedef Strip<LPT, PK> ST;
-    constexpr int SL = ST::SL, SLOG = ST::SLOG, NB = ST::NB;
+    static_assert(SW >= ST::WMIN && SW <= ST::WMAX && (SW == 2 || SW == 4 || SW == 8), "a width this kernel's strips have");
+    constexpr int SWLOG = (SW == 8) ? 3 : ((SW == 4) ? 2 : 1);
+    constexpr int NB = ST::NB;        // boundary slots per row-time
+    constexpr int NG = 64 / SW;       // groups per call
     constexpr u32 BND_WORDS = ST::BND_WORDS;
     const Tk t = load_uniform(tp);
     const int q = uni(q_), g_hi = uni(g_hi_);
-    const int lam = lane & (SL - 1);
+    const int lam = lane & (SW - 1);
     const int lane_base = (LPT == 64) ? 0 : uni(lane_base_);
-    const int Rw0 = SL * q + lam - t.sshift;
+    const int Rw0 = ST::first_of(q) + lam - t.sshift;
     const bool real = Rw0 >= lane_base && Rw0 < lane_base + LPT;
     const int Rw = min(max(Rw0, lane_base), lane_base + LPT - 1);   // the wavefront lane of the fill this lane re-enacts (where its words live)
     const int R = Rw & (LPT - 1);     // ... and its lane within the task (which columns, which rows)
     const int g_first = t.df_lo >> 2;
-    const int g = g_hi - (lane >> SLOG);
+    const int g = g_hi - (lane >> SWLOG);
     const bool live = g >= g_first;
     const int gg = live ? g : g_first;  // lanes beyond the range redo the first group and store nothing
     const int LE = (t.Y - 1) / C;
@@ -88,9 +95,10 @@ __device__ __forceinline__ void materialise_impl(const Tk* tp, const int q_, con
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = 0;
     }
-    // quad shifts: lane lam <- lam-1 / lam+1 of the same strip (the strip's outer lanes take the stored values)
-    auto from_left = [](int v) { return __builtin_amdgcn_update_dpp(v, v, SL == 4 ? 0x90 : 0xA0, 0xf, 0xf, false); };   // quad_perm:[0,0,1,2] | [0,0,2,2]
-    auto from_right = [](int v) { return __builtin_amdgcn_update_dpp(v, v, SL == 4 ? 0xF9 : 0xF5, 0xf, 0xf, false); };  // quad_perm:[1,2,3,3] | [1,1,3,3]
+    // quad shifts: lane lam <- lam-1 / lam+1 of the same strip (the strip's outer lanes take the stored values); 8 lanes: a row
+    // shift by one (what a strip's outer lanes get from the strip next door, or keep at a row's end, is not used)
+    auto from_left = [](int v) { return __builtin_amdgcn_update_dpp(v, v, SW == 8 ? 0x111 : (SW == 4 ? 0x90 : 0xA0), 0xf, 0xf, false); };   // row_shr:1 | quad_perm:[0,0,1,2] | [0,0,2,2]
+    auto from_right = [](int v) { return __builtin_amdgcn_update_dpp(v, v, SW == 8 ? 0x101 : (SW == 4 ? 0xF9 : 0xF5), 0xf, 0xf, false); };  // row_shl:1 | quad_perm:[1,2,3,3] | [1,1,3,3]
     int Lin = from_left(Lp[C - 1]);  // what the left neighbour handed over at the end of the previous row-time
     const int tau_g = gg * 64;
     const int64_t iaW = t.a_base + t.begin_a - t.band + (int64_t)(C - 1) * R + tau_g;  // W[k] <-> a[iaW + k]
@@ -103,12 +111,12 @@ __device__ __forceinline__ void materialise_impl(const Tk* tp, const int q_, con
     u32* const sqa = s_qbnd + QB_SEQ_AT;   // SQW words of a, then SQW words of b (behind them: the walks' carries, gamdp_kernel.hip finish_many)
     int64_t wa0 = 0, wb0 = 0;              // the global word index of sqa[0] / sqa[SQW]
     if constexpr (SEQ_LDS) {
-        const int gmin = max(g_hi - (NB - 1), g_first);
-        const int Rlo = min(max(SL * q - t.sshift, lane_base), lane_base + LPT - 1) & (LPT - 1);
-        const int Rhi = min(max(SL * q + (SL - 1) - t.sshift, lane_base), lane_base + LPT - 1) & (LPT - 1);
+        const int gmin = max(g_hi - (NG - 1), g_first);
+        const int Rlo = min(max(ST::first_of(q) - t.sshift, lane_base), lane_base + LPT - 1) & (LPT - 1);
+        const int Rhi = min(max(ST::first_of(q) + (SW - 1) - t.sshift, lane_base), lane_base + LPT - 1) & (LPT - 1);
         wa0 = (t.a_base + t.begin_a - t.band + (int64_t)(C - 1) * Rlo + (int64_t)gmin * 64) >> 4;
         wb0 = (t.b_base + t.begin_b + (int64_t)gmin * 64 - Rhi) >> 4;
-        static_assert(NB * 64 + 64 + 2 * (C - 1) + 8 + 32 + 16 <= SQW * 16, "the windows of a call fit SQW words each");
+        static_assert(NG * 64 + 64 + 2 * (C - 1) + 8 + 32 + 16 <= SQW * 16, "the windows of a call fit SQW words each");
         if (lane < SQW / 4) {
             *(u32x4*)(sqa + 4 * lane) = *(g4ptr)(t.a2 + wa0 + 4 * lane);
             *(u32x4*)(sqa + SQW + 4 * lane) = *(g4ptr)(t.b2 + wb0 + 4 * lane);
@@ -131,9 +139,9 @@ __device__ __forceinline__ void materialise_impl(const Tk* tp, const int q_, con
     }
     const u32 tagK = (R == LE) ? 0x80000001u : 1u;
     const int kill_c = (RT_EDGE && R == LE) ? (t.Y - 1) % C : -1;   // generic kernels: this lane's column without an `up` source (do_block)
-    // the stored boundary values this lane consumes: lam 0 the chain value entering the strip from the left, lam 3 the
-    // `up` hand-off entering from the right (none right of lane 63); lam 1, 2 load the left one and ignore it
-    const bool right_edge = lam == SL - 1;
+    // the stored boundary values this lane consumes: lam 0 the chain value entering the strip from the left (slot q), lam SW-1 the
+    // `up` hand-off entering from the right (the slot of strip q+1; none right of lane 63); the lanes between load the left one and ignore it
+    const bool right_edge = lam == SW - 1;
     const bool has_left = R != 0, has_right = R != LPT - 1;  // not the task's first / last lane
     constexpr u32 BLK_STRIDE = PK ? PairFmt<C, LPT>::BND_WORDS : BND_WORDS;   // words per block of the boundary store
     const u32 sq = (u32)((right_edge && has_right) ? q + 1 : q) & (u32)(NB - 1);   // the slot of the lane whose stream this lane consumes
@@ -226,10 +234,10 @@ __device__ __forceinline__ void materialise_impl(const Tk* tp, const int q_, con
 // Out of line: called from inside a walk (finish_walk, and walk_many of the two-task kernel), whose state stays in registers across the
 // call -- the calling convention has the callee save the 28 callee-saved registers it needs (14 KB of scratch stored and
 // re-loaded per call).
-template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool TOP = false, int HALF = 0>
+template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool TOP = false, int HALF = 0, int SW = Strip<LPT, PK>::SL>
 __device__ __noinline__ void materialise(const Tk* tp, const int q, const int g_hi, const int lane, const int lane_base = 0)
 {
-    materialise_impl<C, CE, HASN, LPT, PK, TOP, HALF>(tp, q, g_hi, lane, lane_base);
+    materialise_impl<C, CE, HASN, LPT, PK, TOP, HALF, SW>(tp, q, g_hi, lane, lane_base);
 }
 
 // the strip the walk asks for: the TOP-aware re-enactment when the groups of the call reach into packed top blocks
@@ -238,11 +246,21 @@ __device__ __noinline__ void materialise(const Tk* tp, const int q, const int g_
 template <int C, int CE, bool HASN, int LPT, bool PK, bool INLINE = false>
 __device__ __forceinline__ void materialise_auto(const Tk* tp, const int q, const int g_hi, const int lane, const int half, const int lane_base)
 {
-    auto run = [&](auto top, auto hf) __attribute__((always_inline)) {
+    typedef Strip<LPT, PK> ST;
+    auto run_w = [&](auto top, auto hf, auto sw) __attribute__((always_inline)) {
         constexpr bool T = decltype(top)::value;
-        constexpr int H = decltype(hf)::value;
-        if constexpr (INLINE) materialise_impl<C, CE, HASN, LPT, PK, T, H>(tp, q, g_hi, lane, lane_base);
-        else materialise<C, CE, HASN, LPT, PK, T, H>(tp, q, g_hi, lane, lane_base);
+        constexpr int H = decltype(hf)::value, W = decltype(sw)::value;
+        if constexpr (INLINE) materialise_impl<C, CE, HASN, LPT, PK, T, H, W>(tp, q, g_hi, lane, lane_base);
+        else materialise<C, CE, HASN, LPT, PK, T, H, W>(tp, q, g_hi, lane, lane_base);
+    };
+    // the strip's width is wave-uniform: one instance per width the kernel's strips have
+    auto run = [&](auto top, auto hf) __attribute__((always_inline)) {
+        if constexpr (ST::TABLE) {
+            const int w = uni(ST::width_of(uni(q)));
+            if (w == 2) run_w(top, hf, std::integral_constant<int, 2>{});
+            else if (w == 4) run_w(top, hf, std::integral_constant<int, 4>{});
+            else run_w(top, hf, std::integral_constant<int, 8>{});
+        } else run_w(top, hf, std::integral_constant<int, ST::SL>{});
     };
     typedef std::integral_constant<bool, true> Yes;
     typedef std::integral_constant<bool, false> No;
@@ -250,7 +268,7 @@ __device__ __forceinline__ void materialise_auto(const Tk* tp, const int q, cons
     typedef std::integral_constant<int, 1> H1;
     if constexpr (PK && !HASN) {
         const int df_lo = uni(tp->df_lo), df_top = uni(tp->df_top);
-        const bool top = df_top > df_lo && max(4 * (uni(g_hi) - (Strip<LPT, PK>::NB - 1)), df_lo) < df_top;
+        const bool top = df_top > df_lo && max(4 * (uni(g_hi) - (ST::groups_of(uni(q)) - 1)), df_lo) < df_top;
         if (uni(half) != 0) {
             if (top) run(Yes{}, H1{});
             else run(No{}, H1{});

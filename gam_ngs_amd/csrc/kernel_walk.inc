@@ -33,7 +33,6 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
     static_assert((LPT == QL && (NT == 4 || NT == 8)) || (LPT == 64 && NT == 2 && PK), "one or two quads, or the pair of the two-task kernel");
     static_assert(!HASN, "only the N-free kernels use it (the N planes would be two more word pairs per lane and iteration)");
     typedef Strip<LPT, PK> ST;
-    constexpr int NB = ST::NB;
     const int g = lane >> 3, j = lane & 7;
     const int gt = min(g, NT - 1);        // the task this lane works on (groups past the last task idle along with it)
     const int half = (LPT == 64) ? gt : gt >> 2, s4 = gt & 3;
@@ -195,7 +194,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         if (g == sel) {
             old_q = mat_q; old_lo = mat_lo; old_hi = mat_hi;
-            mat_q = q_s; mat_hi = 4 * ghi_s + 3; mat_lo = max(4 * (ghi_s - (NB - 1)), df_lo);
+            mat_q = q_s; mat_hi = 4 * ghi_s + 3; mat_lo = max(4 * (ghi_s - (ST::groups_of(q_s) - 1)), df_lo);
             mat_calls++;
         }
         m_need &= ~(0xFFull << (8 * sel));
