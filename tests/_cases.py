@@ -185,6 +185,55 @@ def adversarial_case(kind, n, band):
     return dict(a=a.encode(), b=b.encode(), band=band, begin_a=0, end_a=len(a) - 1, begin_b=0, end_b=len(b) - 1, fs=False, fe=False)
 
 
+def sprinkle_n(rng, s, p):
+    """s with every base turned into N with probability p"""
+    return "".join("N" if rng.random() < p else ch for ch in s)
+
+
+TIE_FLAGS = ((False, False), (False, True), (True, False), (True, True))   # (fs, fe)
+
+
+def tie_window_cases(seed, bands, ns, per):
+    """`per` windows on adversarial_pair(kind, n, band), for every band, every kind of ADVERSARIAL_KINDS and every n: the tie-rich long
+    pairs (homopolymer, dinucleotide, tandem, complement ...) with what the committed adversarial vectors lack -- windows, force flags, N.
+    They are there for the two tie rules of find_alignment: the first maximum of the end-cell scan wins (banded_smith_waterman.cc:174-212),
+    the traceback prefers the diagonal (:217-311).
+
+    Window w of a pair: flags TIE_FLAGS[w] for w < 4, drawn after that; N at 0.3 % on both sequences when w % 3 == 2;
+        begin_a  of {0, 1, band - 1, band, band + 1, uniform in the first half of a}, clamped to |a| - 1
+        end_a    of {|a| - 1 (twice), begin_a + band / 2, uniform in [begin_a, |a| - 1], |a| + 40}
+        begin_b  of {0 (twice), 13, uniform in the first third of b}
+        end_b    of {|b| - 1 (twice), uniform in [begin_b, |b| - 1], |b| + 9}
+    Deterministic in the arguments; the draws of one (kind, n, band) depend on nothing else, so a subset of bands or lengths gives the
+    same cases for those.  case["tag"] = (kind, n, w) goes into every assertion message.
+
+    Measured with the oracle (which equals the reference on all of them, tests/test_oracle_vs_ref.py) for seed 0, bands (20, 150, 200,
+    512, 600), ns (700, 2600), per 6:
+        720 cases: 492 OK, 177 EMPTY, 51 OUT_OF_RANGE, none INVALID;  31 (ins_past_band_a) to 50 (tandem19) OK per kind;
+        OK of 144 per band: 84 (20), 95 (150), 100 (200), 103 (512), 110 (600);  every (kind, band) has an OK case;
+        OK per (fs, fe): 177 of 181 (-, -), 70 of 179 (-, fe), 177 of 178 (fs, -), 68 of 182 (fs, fe);  201 OK cases hold an N.
+    """
+    out = []
+    for band in bands:
+        for kind in ADVERSARIAL_KINDS:
+            for n in ns:
+                a0, b0 = adversarial_pair(kind, n, band)
+                rng = random.Random(zlib_seed("tie%d/%s" % (seed, kind), n, band))
+                for w in range(per):
+                    a, b = a0, b0
+                    if w % 3 == 2:
+                        a, b = sprinkle_n(rng, a, 0.003), sprinkle_n(rng, b, 0.003)
+                    la, lb = len(a), len(b)
+                    fs, fe = TIE_FLAGS[w] if w < 4 else rng.choice(TIE_FLAGS)
+                    ba = min(rng.choice([0, 1, band - 1, band, band + 1, rng.randint(0, la // 2)]), la - 1)
+                    ea = rng.choice([la - 1, la - 1, ba + band // 2, rng.randint(ba, la - 1), la + 40])
+                    bb = rng.choice([0, 0, 13, rng.randint(0, lb // 3)])
+                    eb = rng.choice([lb - 1, lb - 1, rng.randint(bb, lb - 1), lb + 9])
+                    out.append(dict(a=a.encode(), b=b.encode(), band=band, begin_a=ba, end_a=ea, begin_b=bb, end_b=eb, fs=fs, fe=fe,
+                                    tag=(kind, n, w)))
+    return out
+
+
 def window_cases(seed, band, count=60):
     """Random windowed cases of 0.6 - 14 kb for the direction-free / packed kernels of one band (tools/parity_band512.py and
     tests/test_gpu_l0_parity.py::test_window_cases_on_long_pairs): lengths such that the direction-free range is empty, one

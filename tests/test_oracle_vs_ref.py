@@ -46,8 +46,16 @@ def medium_cases():
     return out
 
 
+TIE_BANDS, TIE_NS, TIE_PER = (20, 150, 200, 512, 600), (700, 2600), 6
+
+
+def tie_window_cases():
+    return _cases.tie_window_cases(0, TIE_BANDS, TIE_NS, TIE_PER)
+
+
 ALIGN_GROUPS = dict([("random_%d" % s, (lambda s=s: random_cases(s))) for s in range(8)] +
-                    [("out_of_range", out_of_range_cases), ("beyond", beyond_cases), ("medium", medium_cases)])
+                    [("out_of_range", out_of_range_cases), ("beyond", beyond_cases), ("medium", medium_cases),
+                     ("tie_windows", tie_window_cases)])
 
 NORMALISE_INPUT = b"acgtnACGTNRYKMxX-*"
 
@@ -156,6 +164,25 @@ def test_begin_a_at_or_past_the_end_of_a_matches_reference():
 
 def test_medium_pairs_band150_and_512():
     assert check_group("medium") == [O.OK] * 3
+
+
+def test_tie_rich_windowed_and_forced_long_pairs_match_reference():
+    """tests/_cases.py tie_window_cases: windows, force flags and N on the adversarial pairs, 0.7 and 2.6 kb at a band of every
+    kernel family.  These are the expected values of tests/test_gpu_tie_windows.py; the conditions below keep a change of the
+    generator from hollowing the group out (they hold for the reference's answers alone)."""
+    cases = tie_window_cases()
+    status = check_group("tie_windows")
+    assert len(cases) == len(TIE_BANDS) * len(_cases.ADVERSARIAL_KINDS) * len(TIE_NS) * TIE_PER
+    assert "invalid" not in status
+    ok = [c for c, s in zip(cases, status) if s == O.OK]
+    assert 2 * len(ok) >= len(cases), (len(ok), len(cases))
+    for flags in _cases.TIE_FLAGS:
+        n_all = sum(1 for c in cases if (c["fs"], c["fe"]) == flags)
+        n_ok = sum(1 for c in ok if (c["fs"], c["fe"]) == flags)
+        assert n_all > 0 and 4 * n_ok >= n_all, (flags, n_ok, n_all)
+    missing = {(k, b) for k in _cases.ADVERSARIAL_KINDS for b in TIE_BANDS} - {(c["tag"][0], c["band"]) for c in ok}
+    assert not missing, sorted(missing)
+    assert sum(1 for c in ok if b"N" in c["a"] or b"N" in c["b"]) >= 100
 
 
 def ref_normalise(s):
