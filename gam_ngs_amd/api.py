@@ -88,6 +88,14 @@ class Context:
         self.lib.gamdp_ctx_score_info(self.handle, arr, n.value, C.byref(n))
         return [arr[i].as_dict() for i in range(n.value)]
 
+    def carry_info(self):
+        """The launches of the last gamdp_carry_batch call on this context, as dicts (gamdp_ctx_carry_info)."""
+        n = C.c_size_t()
+        self.lib.gamdp_ctx_carry_info(self.handle, None, 0, C.byref(n))
+        arr = (L.ScoreLaunchInfo * max(1, n.value))()
+        self.lib.gamdp_ctx_carry_info(self.handle, arr, n.value, C.byref(n))
+        return [arr[i].as_dict() for i in range(n.value)]
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.gamdp_ctx_destroy(self.handle)
@@ -358,6 +366,20 @@ class BandedSmithWaterman:
         out = (L.ScoreResult * n)()
         _check(self.ctx, self.ctx.lib.gamdp_score_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out), "gamdp_score_batch")
         return [(r.score, r.end_a, r.end_b, r.status, r.cells) for r in out]
+
+    def find_results(self, calls, bands=None) -> List[MyAlignment]:
+        """Every call's whole result from a fill alone (gamdp_carry_batch: a third, int32-only kernel in which every cell carries the
+        summary of the traceback that would start in it; no scratch arena, no walk): a list of MyAlignment without edit strings
+        (ops None), field by field what find_alignments returns for the same calls."""
+        n = len(calls)
+        if n == 0:
+            return []
+        if isinstance(self.ctx, MultiContext):
+            raise L.GamdpError("find_results is a single-context call")
+        tasks, sa, sb = self._tasks(calls, bands)
+        out = (L.Result * n)()
+        _check(self.ctx, self.ctx.lib.gamdp_carry_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out), "gamdp_carry_batch")
+        return [MyAlignment.from_result(r, None) for r in out]
 
     def find_alignments(self, calls, want_ops=False, bands=None) -> List[MyAlignment]:
         """calls: list of (a, begin_a, end_a, b, begin_b, end_b[, force_start[, force_end]]); all a's

@@ -311,4 +311,17 @@ const char* score_kernel_name(int cols);     // as rocprofv3 prints it, e.g. "k_
 int score_waves_per_cu(int cols);            // resident wavefronts per CU, from the occupancy the runtime reports
 int launch_score(int cols, const ScoreParams& p, unsigned n_wavefronts, void* stream);   // returns hipError_t as int
 
+// ---- the whole result from a fill alone (k_carry, gamdp_carry.hip; gamdp_carry_batch) -----------------------------------
+// A wavefront leaves a task's DevResult; bits 16.. of its flags hold the band columns per lane of the instantiation that ran.
+struct CarryParams {
+    const DevTask* tasks;   // by decreasing rows; a2 .. flags and res_idx are read, the rest of a descriptor is not
+    u32 n_tasks;
+    u32* cursor;            // work-queue head (zeroed before the launch)
+    DevResult* results;     // indexed by DevTask::res_idx
+};
+constexpr u32 CARRY_COLS_SHIFT = 16;
+const char* carry_kernel_name(int cols);     // e.g. "k_carry<5>"; the instantiation a band takes is score_cols(band)
+int carry_waves_per_cu(int cols);            // resident wavefronts per CU, from the occupancy the runtime reports
+int launch_carry(int cols, const CarryParams& p, unsigned n_wavefronts, void* stream);   // returns hipError_t as int
+
 }  // namespace gamdp

@@ -1088,20 +1088,62 @@ int Ctx::align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_op
     return 0;
 }
 
-// ---- score and end cell without the traceback (gamdp_score_batch; the kernel: gamdp_score.hip) ---------------------------
-// The same checks, pre-checks and descriptors as align(); then one launch of k_score<C> per column count C the batch's bands take,
-// each over its tasks by decreasing rows.  No scratch arena, no planner: a wavefront needs nothing but its registers.
-int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out)
+// ---- the fill-only calls: gamdp_score_batch (k_score, gamdp_score.hip) and gamdp_carry_batch (k_carry, gamdp_carry.hip) ----
+// The same checks, pre-checks and descriptors as align(); then one launch of the call's kernel per column count C the batch's bands
+// take, each over its tasks by decreasing rows.  No scratch arena, no planner: a wavefront needs nothing but its registers.
+
+// What the two calls differ in: the record a wavefront leaves, the kernel that writes it, and the caller's result made from it.
+struct ScoreCall {
+    typedef ScoreRec Rec;
+    typedef gamdp_score_result Out;
+    static constexpr const char* api = "gamdp_score_batch";
+    static const char* kernel_name(int cols) { return score_kernel_name(cols); }
+    static int waves_per_cu(int cols) { return score_waves_per_cu(cols); }
+    static int launch(int cols, const DevTask* t, u32 n, u32* cursor, Rec* results, unsigned slots, void* stream)
+    {
+        ScoreParams p;
+        p.tasks = t; p.n_tasks = n; p.cursor = cursor; p.results = results;
+        return launch_score(cols, p, slots, stream);
+    }
+    static u32 cols_of(const Rec& r) { return r.info >> 8; }
+    static void collect(const Rec& r, u64 cells, Out& o)
+    {
+        (void)cells;   // (set with the pre-checks' status)
+        o.status = (uint8_t)(r.info & 0xFFu);
+        if (o.status != GAMDP_ST_OK) return;
+        o.score = r.score;
+        o.end_a = (u64)(int64_t)r.end_a; o.end_b = (u64)(int64_t)r.end_b;
+    }
+};
+struct CarryCall {
+    typedef DevResult Rec;
+    typedef gamdp_result Out;
+    static constexpr const char* api = "gamdp_carry_batch";
+    static const char* kernel_name(int cols) { return carry_kernel_name(cols); }
+    static int waves_per_cu(int cols) { return carry_waves_per_cu(cols); }
+    static int launch(int cols, const DevTask* t, u32 n, u32* cursor, Rec* results, unsigned slots, void* stream)
+    {
+        CarryParams p;
+        p.tasks = t; p.n_tasks = n; p.cursor = cursor; p.results = results;
+        return launch_carry(cols, p, slots, stream);
+    }
+    static u32 cols_of(const Rec& r) { return r.flags >> CARRY_COLS_SHIFT; }
+    static void collect(const Rec& r, u64 cells, Out& o) { fill_result(r, cells, o); }   // as align() makes a gamdp_result of a record
+};
+
+template <class K>
+int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log)
 {
+    typedef typename K::Rec Rec;
     if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_EHIP; }
-    score_log.clear();
+    log.clear();
     if (n == 0) return 0;
     int rc_ = align_check(tasks, n);
     if (rc_) return rc_;
     for (size_t i = 0; i < n; i++) {
         const u32 band = tasks[i].band;
         if (band > GAMDP_MAX_TUNED_BAND) {
-            set_error("gamdp_score_batch: task " + std::to_string(i) + " has band " + std::to_string(band) + ", above GAMDP_MAX_TUNED_BAND");
+            set_error(std::string(K::api) + ": task " + std::to_string(i) + " has band " + std::to_string(band) + ", above GAMDP_MAX_TUNED_BAND");
             return GAMDP_ENOTSUP;
         }
     }
@@ -1134,13 +1176,13 @@ int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out)
         order.insert(order.end(), g.begin(), g.end());
     }
     if (launches.empty()) return 0;   // every task was settled by the pre-checks
-    // (the task and result staging of align(), the latter as raw memory: a ScoreRec is smaller than a DevResult)
-    static_assert(sizeof(ScoreRec) <= sizeof(DevResult), "score records are staged in the result buffers of align()");
+    // (the task and result staging of align(), the latter as raw memory: a record is no larger than a DevResult)
+    static_assert(sizeof(Rec) <= sizeof(DevResult), "the records are staged in the result buffers of align()");
     if ((rc_ = grow(this, d_tasks, cap_tasks, order.size() + 1))) return rc_;
     if ((rc_ = grow(this, d_results, cap_results, n + 1))) return rc_;
     if ((rc_ = grow_staging(n))) return rc_;
-    ScoreRec* const d_rec = reinterpret_cast<ScoreRec*>(d_results);
-    ScoreRec* const h_rec = reinterpret_cast<ScoreRec*>(h_results);
+    Rec* const d_rec = reinterpret_cast<Rec*>(d_results);
+    Rec* const h_rec = reinterpret_cast<Rec*>(h_results);
     parallel_for(order.size(), [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) h_tasks[k] = w_prep[order[k]].dt; });
     HIPCHK(this, hipMemsetAsync(d_cursor, 0, launches.size() * sizeof(u32), stream));   // (cap_cursor >= 64 words)
     HIPCHK(this, hipMemcpyAsync(d_tasks, h_tasks, order.size() * sizeof(DevTask), hipMemcpyHostToDevice, stream));
@@ -1153,24 +1195,18 @@ int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out)
     std::vector<u32> slots(launches.size());
     for (size_t li = 0; li < launches.size(); li++) {
         const SLaunch& L = launches[li];
-        ScoreParams p;
-        p.tasks = d_tasks + L.first; p.n_tasks = L.count; p.cursor = d_cursor + li; p.results = d_rec;
-        slots[li] = (u32)std::min<u64>(L.count, (u64)n_cu * (u64)score_waves_per_cu(L.cols));
+        slots[li] = (u32)std::min<u64>(L.count, (u64)n_cu * (u64)K::waves_per_cu(L.cols));
         HIPCHK(this, hipEventRecord(events[li].first, stream));
-        const int e = launch_score(L.cols, p, slots[li], stream);
+        const int e = K::launch(L.cols, d_tasks + L.first, L.count, d_cursor + li, d_rec, slots[li], stream);
         if (e != 0) { set_error(std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)e)); return GAMDP_EHIP; }
         HIPCHK(this, hipEventRecord(events[li].second, stream));
     }
-    HIPCHK(this, hipMemcpyAsync(h_rec, d_rec, n * sizeof(ScoreRec), hipMemcpyDeviceToHost, stream));
+    HIPCHK(this, hipMemcpyAsync(h_rec, d_rec, n * sizeof(Rec), hipMemcpyDeviceToHost, stream));
     HIPCHK(this, hipStreamSynchronize(stream));
     parallel_for(n, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; i++) {
             if (colsv[i] < 0) continue;   // settled by the pre-checks
-            const ScoreRec& r = h_rec[i];
-            out[i].status = (uint8_t)(r.info & 0xFFu);
-            if (out[i].status != GAMDP_ST_OK) continue;
-            out[i].score = r.score;
-            out[i].end_a = (u64)(int64_t)r.end_a; out[i].end_b = (u64)(int64_t)r.end_b;
+            K::collect(h_rec[i], w_key[i], out[i]);
         }
     });
     for (size_t li = 0; li < launches.size(); li++) {
@@ -1179,16 +1215,19 @@ int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out)
         if (hipEventElapsedTime(&ms, events[li].first, events[li].second) == hipSuccess) { kernel_launches++; kernel_ms += ms; }
         gamdp_score_launch_info r;
         std::memset(&r, 0, sizeof(r));
-        std::snprintf(r.kernel, sizeof(r.kernel), "%s", score_kernel_name(L.cols));
+        std::snprintf(r.kernel, sizeof(r.kernel), "%s", K::kernel_name(L.cols));
         // the column count as the wavefronts wrote it into their records (0: they do not all say the same)
-        r.cols = h_rec[order[L.first]].info >> 8;
-        for (u32 k = 0; k < L.count; k++) if ((h_rec[order[L.first + k]].info >> 8) != r.cols) r.cols = 0;
+        r.cols = K::cols_of(h_rec[order[L.first]]);
+        for (u32 k = 0; k < L.count; k++) if (K::cols_of(h_rec[order[L.first + k]]) != r.cols) r.cols = 0;
         r.tasks = L.count; r.slots = slots[li]; r.band_max = L.band_max;
         r.kernel_ms = (double)ms;
-        score_log.push_back(r);
+        log.push_back(r);
     }
     return 0;
 }
+
+int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out) { return fill_only<ScoreCall>(tasks, n, out, score_log); }
+int Ctx::carry(const TaskSrc& tasks, size_t n, gamdp_result* out) { return fill_only<CarryCall>(tasks, n, out, carry_log); }
 
 // ---- batch pieces -------------------------------------------------------------------------------------
 
@@ -1440,6 +1479,27 @@ int gamdp_ctx_score_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, siz
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
     if (n) *n = c->score_log.size();
     for (size_t i = 0; i < c->score_log.size() && i < cap; i++) out[i] = c->score_log[i];
+    return 0;
+}
+
+int gamdp_carry_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
+                      gamdp_result* out)
+{
+    if (!ctx || !set_a || !set_b || !out || (n && !tasks)) return GAMDP_EINVAL;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return guarded(c, [&]() -> int {
+        TaskSrc src;   // the caller's array, read in place
+        src.gt = tasks; src.sa = reinterpret_cast<const SeqSet*>(set_a); src.sb = reinterpret_cast<const SeqSet*>(set_b);
+        return c->carry(src, n, out);
+    });
+}
+
+int gamdp_ctx_carry_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n)
+{
+    if (!ctx || (cap && !out)) return GAMDP_EINVAL;
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    if (n) *n = c->carry_log.size();
+    for (size_t i = 0; i < c->carry_log.size() && i < cap; i++) out[i] = c->carry_log[i];
     return 0;
 }
 

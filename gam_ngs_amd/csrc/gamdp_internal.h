@@ -259,6 +259,10 @@ struct Ctx {
     // gamdp_score_batch (gamdp_host.cpp; the kernel: gamdp_score.hip), and what its last call launched (gamdp_ctx_score_info)
     int score(const TaskSrc& tasks, size_t n, gamdp_score_result* out);
     std::vector<gamdp_score_launch_info> score_log;
+    // gamdp_carry_batch (the kernel: gamdp_carry.hip), and what its last call launched (gamdp_ctx_carry_info)
+    int carry(const TaskSrc& tasks, size_t n, gamdp_result* out);
+    std::vector<gamdp_score_launch_info> carry_log;
+    template <class K> int fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log);   // what the two share (gamdp_host.cpp)
     int align(const ITask* tasks, size_t n, gamdp_result* out, const gamdp_ops* ops) { TaskSrc s; s.it = tasks; return align(s, n, out, ops); }
     int align(const std::vector<ITask>& tasks, gamdp_result* out, const gamdp_ops* ops) { return align(tasks.data(), tasks.size(), out, ops); }
     ~Ctx();

@@ -23,7 +23,7 @@ SYMBOLS = [
     "gamdp_blocks_open", "gamdp_blocks_close", "gamdp_blocks_count", "gamdp_blocks_data", "gamdp_blocks_write",
     "gamdp_no_blocks_contigs", "gamdp_no_blocks_after_filter", "gamdp_pctgs_not_merged", "gamdp_fasta_write_selected",
     "gamdp_find_hits_batch", "gamdp_ctx_set_l1_hits", "gamdp_ctx_l1_hits_stats",
-    "gamdp_ctx_l1_tail_calls", "gamdp_score_batch", "gamdp_ctx_score_info",
+    "gamdp_ctx_l1_tail_calls", "gamdp_score_batch", "gamdp_ctx_score_info", "gamdp_carry_batch", "gamdp_ctx_carry_info",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
@@ -215,6 +215,10 @@ def load_library():
     lib.gamdp_score_batch.restype = C.c_int
     lib.gamdp_ctx_score_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
     lib.gamdp_ctx_score_info.restype = C.c_int
+    lib.gamdp_carry_batch.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(Result)]
+    lib.gamdp_carry_batch.restype = C.c_int
+    lib.gamdp_ctx_carry_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gamdp_ctx_carry_info.restype = C.c_int
     lib.gamdp_task_preflight.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int, C.POINTER(u64)]
     lib.gamdp_ctx_l1_stats.argtypes = [vp, C.POINTER(L1Stats)]
     lib.gamdp_ctx_set_l1_hits.argtypes = [vp, C.c_int]

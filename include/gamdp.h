@@ -263,6 +263,30 @@ typedef struct gamdp_score_launch_info {
 /* copies up to `cap` records to out (may be NULL when cap == 0); *n = how many launches the call made */
 int gamdp_ctx_score_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n);
 
+/* The whole result of BandedSmithWaterman(band).find_alignment(...) from a fill alone.  The reference's traceback
+ * (banded_smith_waterman.cc:227-311) is a pointer chase whose step from a cell depends only on that cell's value and its three
+ * neighbours' values (:229-308), which the fill holds when it computes the cell; so every cell carries the summary of the traceback
+ * that would start in it -- where it ends (:321), its ops, its MATCH ops (:239, :274), its first and last MATCH
+ * (first_match_pos, my_alignment.cc:167-193; last_match_pos, :228-262) -- made from the summary of the cell the step leads to, and
+ * the summary of the end cell (:173-215) is the result.
+ * Tasks as for gamdp_align_batch.  Every field of every gamdp_result equals what gamdp_align_batch writes for the same task, the cases
+ * gamdp_task_preflight settles included, and GAMDP_ST_EMPTY (:215) / GAMDP_ST_OUT_OF_RANGE (the traceback's a.at(pos) throws) decided
+ * at the end cell; homology is computed on the host from n_match and length (:319).  There is no edit string.
+ * What it is for: a check of gamdp_align_batch's traceback half -- strips, re-created directions, walks, side captures -- on the
+ * device the batch ran on, call by call at any scale (tools/score_crosscheck.py --carry), as gamdp_score_batch is of its fill.  A
+ * third implementation: int32, one call per wavefront, by a kernel that shares its sequence windows and scoring rows with
+ * gamdp_score_batch's and no code with the alignment kernels.  It keeps no direction and no row of the matrix, and the scratch arena
+ * (gamdp_ctx_set_arena_bytes) is NOT used.  It makes no promise of speed.
+ * Refusals as gamdp_score_batch: GAMDP_EINVAL for NULL ctx / sets / out, NULL tasks with n > 0, ids out of range and reverse
+ * complements of a packed-only set; n == 0 succeeds; a batch that holds a band above GAMDP_MAX_TUNED_BAND returns GAMDP_ENOTSUP as a
+ * whole (gamdp_last_error names the task; the context stays usable).  tasks must not change before the call returns.  The launches
+ * count toward gamdp_ctx_kernel_time; gamdp_ctx_launch_info and gamdp_ctx_score_info keep describing their own calls. */
+int gamdp_carry_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b,
+                      const gamdp_task* tasks, size_t n, gamdp_result* out);
+/* What the last gamdp_carry_batch call on this context launched, in launch order: one launch ("k_carry<5>") per instantiation its
+ * bands take; the fields as for gamdp_ctx_score_info. */
+int gamdp_ctx_carry_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n);
+
 /* bit 0: this library is the diagnostics build (-DGAMDP_DIAG; honours the GAMDP_DIAG_* switches that change kernel
  * paths or invalidate results).  The product build returns 0 and ignores those switches. */
 unsigned gamdp_build_info(void);

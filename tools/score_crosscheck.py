@@ -7,13 +7,18 @@ status and cells agree for every task, and prints one JSON line: the task count,
 gamdp_align_batch launched, and each call's kernel time (gamdp_ctx_kernel_time) over --reps alternating repetitions.  It reads
 nothing but the package and tests/_mixed.py.
 
+With --carry a third call, gamdp_carry_batch (gam_ngs_amd/csrc/gamdp_carry.hip: the whole result from a fill in which every cell
+carries the summary of the traceback that would start in it), checks the other half: every field of every gamdp_result -- begin,
+score, n_match, length, first and last match, homology, status -- and cells must equal gamdp_align_batch's; the line then also holds
+carry_mismatches, carry_kernels, carry_kernel_ms and carry_gcups.  Without the flag the output is what it was.
+
 Workloads:  --pairs N --len L --band B   N synthetic pairs of L bases (SequenceSet.synthetic), whole-sequence windows
             --mixed N                    N calls shaped like the merge-block driver's (tests/_mixed.py), band --band (default 150)
 
 The planner switches of DESIGN.md section 6 apply to gamdp_align_batch as always (read once per process): with
 GAMDP_NO_PAIR=1 GAMDP_QUAD_MIN=1000000000 in the environment it stays on the one-task int32 kernels.
 
-Usage: python tools/score_crosscheck.py --pairs 4096 --len 50000 --band 150 [--reps 5] [--first-pair K]
+Usage: python tools/score_crosscheck.py --pairs 4096 --len 50000 --band 150 [--carry] [--reps 5] [--first-pair K]
 """
 import argparse
 import json
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--first-pair", type=int, default=0)
     ap.add_argument("--seed", type=int, default=20261019)
+    ap.add_argument("--carry", action="store_true", help="also run gamdp_carry_batch and compare whole results")
     args = ap.parse_args()
     if bool(args.pairs) == bool(args.mixed):
         ap.error("one of --pairs N or --mixed N")
@@ -59,8 +65,11 @@ def main():
             t.begin_a, t.end_a, t.begin_b, t.end_b = 0, args.len - 1, 0, sset.lengths[2 * k + 1] - 1
         workload = dict(workload="pairs", pairs=n, len=args.len, band=args.band)
     res, sc = (L.Result * n)(), (L.ScoreResult * n)()
-    align_ms, score_ms = [], []
+    ca = (L.Result * n)() if args.carry else None
+    align_ms, score_ms, carry_ms = [], [], []
     mismatches, first_bad = 0, None
+    carry_mismatches, carry_first_bad = 0, None
+    whole = lambda r: r.key() + (r.cells,)  # noqa: E731
     for rep in range(args.reps + 1):   # (the first pass warms up: buffers, reverse complements, code objects)
         ctx.kernel_time(reset=True)
         rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res, None)
@@ -69,23 +78,36 @@ def main():
         rc = ctx.lib.gamdp_score_batch(ctx.handle, sset.handle, sset.handle, tasks, n, sc)
         assert rc == 0, ("gamdp_score_batch", rc, ctx.last_error())
         s_ms = ctx.kernel_time(reset=True)[0]
+        if args.carry:
+            rc = ctx.lib.gamdp_carry_batch(ctx.handle, sset.handle, sset.handle, tasks, n, ca)
+            assert rc == 0, ("gamdp_carry_batch", rc, ctx.last_error())
+            c_ms = ctx.kernel_time(reset=True)[0]
         if rep:
             align_ms.append(a_ms)
             score_ms.append(s_ms)
+            if args.carry:
+                carry_ms.append(c_ms)
         for i in range(n):
             if (res[i].score, res[i].status, res[i].cells) != (sc[i].score, sc[i].status, sc[i].cells):
                 mismatches += 1
                 if first_bad is None:
                     first_bad = dict(task=i, align=(res[i].score, res[i].status, res[i].cells), score=(sc[i].score, sc[i].status, sc[i].cells))
+            if args.carry and whole(res[i]) != whole(ca[i]):
+                carry_mismatches += 1
+                if carry_first_bad is None:
+                    carry_first_bad = dict(task=i, align=whole(res[i]), carry=whole(ca[i]))
     cells = sum(r.cells for r in res)
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
     rec = dict(workload, tasks=n, mismatches=mismatches, first_mismatch=first_bad, ok=sum(1 for r in res if r.status == 0), cells=cells,
                align_kernels=sorted({r["kernel"] for r in ctx.launch_info()}), score_kernels=[r["kernel"] for r in ctx.score_info()],
                align_kernel_ms=[round(v, 3) for v in align_ms], score_kernel_ms=[round(v, 3) for v in score_ms],
                align_gcups=round(cells / med(align_ms) / 1e6, 1), score_gcups=round(cells / med(score_ms) / 1e6, 1))
+    if args.carry:
+        rec.update(carry_mismatches=carry_mismatches, carry_first_mismatch=carry_first_bad, carry_kernels=[r["kernel"] for r in ctx.carry_info()],
+                   carry_kernel_ms=[round(v, 3) for v in carry_ms], carry_gcups=round(cells / med(carry_ms) / 1e6, 1))
     print(json.dumps(rec), flush=True)
     sset.close()
-    sys.exit(0 if mismatches == 0 else 1)
+    sys.exit(0 if mismatches == 0 and carry_mismatches == 0 else 1)
 
 
 if __name__ == "__main__":
