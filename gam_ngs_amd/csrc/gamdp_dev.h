@@ -133,6 +133,15 @@ enum KernelId : int {
 #else
 #define GAMDP_HD
 #endif
+
+// ---- the pattern format of the two-task band-512 kernel (kernel_pair.inc has the argument; tests/native/pattern_order_test.cpp checks
+// these functions over the whole range on the CPU).  A half-word holds PAT_OFF + (value - base) as a plain 16-bit integer; a live one
+// lies in [PAT_MIN, PAT_MAX]: a normal, finite, non-negative f16 that stays one when a match's 21 is added.
+constexpr u32 PAT_OFF = 0x2000u, PAT_MIN = 0x0400u, PAT_MAX = 0x7BFFu - 21u;
+GAMDP_HD inline u32 pat_encode(int rel) { return (PAT_OFF + (u32)rel) & 0xFFFFu; }
+// read as SIGNED 16-bit: a pattern with the top bit set ("no source", 0xFC00, or what a dead cell holds) decodes below every live value
+GAMDP_HD inline int pat_decode(u32 p16) { return (int)(int16_t)(uint16_t)p16 - (int)PAT_OFF; }
+
 GAMDP_HD inline int preflight_hd(u64 alen, u64 blen, u64 band, u64 begin_a, u64 end_a, u64 begin_b, u64 end_b, bool fs, bool fe,
                                  u64* X_out, u64* cells_out)
 {

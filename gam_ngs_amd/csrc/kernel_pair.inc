@@ -6,6 +6,7 @@
 // task B in the high halves -- with
 //       v_perm_b32          one byte look-up per task: 4.0 (mismatch) or 7.0 (match) as the high byte of an f16
 //       v_pk_fma_f16        diag candidate  = previous row + 3 * that  (+12 / +21: the tilted scores, without the x4)
+//                           (two-task kernel: the look-up is 12 or 21 itself, the candidate a v_add_u32 on bit patterns, see below)
 //       v_pk_maximum3_f16   max(diag, up, left)
 // per cell PAIR: 1.5 instructions per cell instead of 2 (measured 20.4 against 13.9 Tcell/s, tools/valu_rate5.hip).
 // Values are kept relative to a per-lane, per-task base (an int32) that is re-centred every group of four blocks, so they stay
@@ -17,6 +18,11 @@
 // stored packed as well: the live row of every 4th block and the per-row boundary values of every 2nd / 4th lane as f16 pairs
 // (half the bytes of the int32 kernels) plus the bases they are relative to; materialise() converts back to int32 and re-enacts
 // exactly the same tagged sweep as for the int32 kernels, so results are bit-identical.
+// The TWO-task kernel (LPT == 64) goes one step further in its plain and END ranges (pair_range): a half is not an f16 NUMBER but
+// the integer bit PATTERN of one ("the pattern format", below), so that the diag candidate of both tasks is one 32-bit integer add
+// (v_add_u32 issues faster than v_pk_fma_f16: tools/valu_rate7.hip) while v_pk_maximum3_f16 still takes the three-way maximum.  Its
+// top blocks compute in f16 (the NaN marker needs it) and convert what they store, so that a slot holds one layout.  The eight-task
+// kernel (LPT == 16) is f16-numeric throughout.
 #ifndef GAMDP_PACKED_TOP
 #define GAMDP_PACKED_TOP 1
 #endif
@@ -42,6 +48,46 @@ __device__ __forceinline__ int h_to_g4(const _Float16 h, const int base)
     if (!(f > -60000.0f)) return NEG;          // -inf (or garbage of a dead cell)
     if (!(f < 60000.0f)) return 0;             // garbage of a dead cell
     return 4 * ((int)f + base);
+}
+
+// ---- the PATTERN format of the two-task kernel (LPT == 64) ---------------------------------------------------------------------
+// The bit patterns of the non-negative finite f16 numbers, 0x0000 ... 0x7BFF, are ordered exactly like the unsigned integers they
+// are, and v_pk_maximum3_f16 hands back one of its operands bit for bit while they are normal numbers (patterns >= 0x0400;
+// tools/valu_rate7.hip checks both on the device).  So the plain and END ranges of the two-task kernel keep a half-word as the
+// INTEGER pattern PAT_OFF + (G - base): the three-way maximum is unchanged, and the diag candidate "+12 / +21 on both tasks" is one
+// 32-bit integer add of (sB << 16) | sA -- nothing is rounded, nothing depends on a binade.  A live value stays inside
+// [PAT_MIN, PAT_MAX] (pair_range has the bound), so the add of the low half never carries into the high half.  "No source" stays
+// 0xFC00 (-inf), which the maximum orders below every pattern; it never passes through an add: an add would make it a NaN.
+// Everything else that touches a half -- the base differences of the hand-offs, the re-centring -- is packed 16-bit integer
+// arithmetic (no carry between the tasks).  The stored layout (checkpoint rows, boundary words) holds the same patterns, read as
+// SIGNED 16-bit: value = (int16)pattern - PAT_OFF + base, so that every pattern with the top bit set (0xFC00, and whatever a dead
+// lane holds) decodes far below the live values around it.
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+constexpr u32 PAT_OFF2 = PAT_OFF * 0x00010001u;   // (PAT_OFF, PAT_MIN, PAT_MAX, pat_encode, pat_decode: gamdp_dev.h)
+__device__ __forceinline__ u32 pat_add(const u32 a, const u32 b) { return __builtin_bit_cast(u32, __builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b)); }
+__device__ __forceinline__ u32 pat_sub(const u32 a, const u32 b) { return __builtin_bit_cast(u32, __builtin_bit_cast(us2, a) - __builtin_bit_cast(us2, b)); }
+__device__ __forceinline__ u32 pk16(const int lo, const int hi) { return ((u32)lo & 0xFFFFu) | ((u32)hi << 16); }
+__device__ __forceinline__ u32 pat_lo(const u32 v) { return v & 0xFFFFu; }
+__device__ __forceinline__ u32 pat_hi(const u32 v) { return v >> 16; }
+// G4 value (multiple of 4, or NEG) -> pattern relative to `base`, and back (a pattern with the top bit set: "no source", or what a
+// dead cell holds)
+__device__ __forceinline__ u32 g4_to_pat(const int g4, const int base)
+{
+    if (g4 <= NEG / 2) return 0xFC00u;
+    return pat_encode((g4 >> 2) - base);
+}
+__device__ __forceinline__ int pat_to_g4(const u32 p, const int base)
+{
+    if (p & 0x8000u) return NEG;
+    return 4 * (pat_decode(p) + base);
+}
+// a packed f16 pair of the top blocks -> the stored patterns.  Clamped to +-16 000 first (a live value is an integer inside
+// +-2 048 and converts exactly; -inf and the garbage of dead cells become a pattern that decodes to -16 000 or +16 000)
+__device__ __forceinline__ u32 h2_to_pat(const u32 v)
+{
+    const h2 lim = {(_Float16)16000.0f, (_Float16)16000.0f};
+    const h2 c = __builtin_elementwise_min(__builtin_elementwise_max(as_h2(v), -lim), lim);
+    return pat_add(pk16((int)(short)c.x, (int)(short)c.y), PAT_OFF2);
 }
 
 // layout of the packed row / boundary stores inside a slot (words)
@@ -71,6 +117,9 @@ __shared__ u32 s_pcap[QT][2][20];
 // the per-row operands of a pair: ring A entry = v_perm selector for both tasks, ring B entries = the look-up bytes
 __device__ __forceinline__ u32 pk_sel(const u32 codeA, const u32 codeB) { return 0x000C000Cu | (codeA << 8) | ((4u + codeB) << 24); }
 __device__ __forceinline__ u32 pk_tab(const u32 codeb) { return 0x44444444u + (0x03u << (codeb * 8u)); }  // high byte of 4.0 / 7.0
+// the pattern format: the looked-up byte is the score itself, 12 or 21, in the LOW byte of each half, zero above it
+__device__ __forceinline__ u32 pat_sel(const u32 codeA, const u32 codeB) { return 0x0C000C00u | codeA | ((4u + codeB) << 16); }
+__device__ __forceinline__ u32 pat_tab(const u32 codeb) { return 0x0C0C0C0Cu + (0x09u << (codeb * 8u)); }
 
 __device__ __forceinline__ u32 code2_at(gcptr p2, int64_t idx) { return (p2[idx >> 4] >> ((idx & 15) * 2)) & 3u; }
 
@@ -79,13 +128,17 @@ __device__ __forceinline__ u32 code2_at(gcptr p2, int64_t idx) { return (p2[idx 
 // per wavefront, band 150): one set of rings per DPP row; ring A entries are 16 bit (code of A's base, 4 + code of B's
 // base) and become the selector with one v_perm + one v_or per row and lane -- dword rings for four rows do not fit.
 __shared__ u32 s_oB2[QT][64 + ROWS];   // (s_oA16: kernel_common.inc, shared with the int32 phases' byte ring)
-template <int C, int LPT>
+// PAT: the entries are in the pattern format's forms (pair_range of the two-task kernel; the rings are primed per range)
+template <int C, int LPT, bool PAT = false>
 struct PRing {
+    static_assert(!PAT || LPT == 64, "the pattern format is the two-task kernel's");
+    static __device__ __forceinline__ u32 sel(const u32 codeA, const u32 codeB) { return PAT ? pat_sel(codeA, codeB) : pk_sel(codeA, codeB); }
+    static __device__ __forceinline__ u32 tab(const u32 codeb) { return PAT ? pat_tab(codeb) : pk_tab(codeb); }
     typedef typename std::conditional<LPT == 64, const u32*, const uint16_t*>::type APtr;
     static constexpr int SZ = QRing<C>::SZ;
     static __device__ __forceinline__ void put_a(const int sub, const int k, const u32 codeA, const u32 codeB)
     {
-        if constexpr (LPT == 64) RingA<C>::put(k, pk_sel(codeA, codeB));
+        if constexpr (LPT == 64) RingA<C>::put(k, sel(codeA, codeB));
         else {
             const u32 pos = (u32)k % (u32)SZ;
             const uint16_t v = (uint16_t)(codeA | ((4u + codeB) << 8));
@@ -142,6 +195,17 @@ struct PRing {
             return __builtin_bit_cast(_Float16, reinterpret_cast<const uint16_t*>(cb)[2 * idx + half]);
         }
     }
+    // the same for a row of patterns (two-task kernel, pair_range): the 16 bits as they are
+    template <int C2>
+    static __device__ __forceinline__ u32 cap_pick_pat(const int wlane, const int half, const u32 (&Lp)[C2], const int idx)
+    {
+        static_assert(LPT == 64, "the pattern format is the two-task kernel's");
+        u32* const cb = (u32*)s_cap[half][wlane & 1];
+#pragma unroll
+        for (int c = 0; c < C2; ++c) cb[c] = Lp[c];
+        const u32 v = cb[idx];
+        return half ? pat_hi(v) : pat_lo(v);
+    }
     // the producers expand the 16 new entries of the block whose first row-time is T (lanes 0..15, or every lane for its row)
     // MARK (the top blocks): the entry of a task's base -1 -- ring index km1A / km1B -- is not a look-up but the NaN marker
     // (code 13 / 9: the selector byte 0x0D, which v_perm turns into 0xFF; pair_top_range)
@@ -155,7 +219,7 @@ struct PRing {
             u32 cA = (awA >> (2 * r)) & 3u, cB = (awB >> (2 * r)) & 3u;
             if constexpr (MARK) { cA = (k == km1A) ? MARK_A : cA; cB = (k == km1B) ? MARK_B : cB; }
             put_a(lane >> 4, k, cA, cB);
-            put_b(lane >> 4, T + r, pk_tab((bwA >> (2 * r)) & 3u), pk_tab((bwB >> (2 * r)) & 3u));
+            put_b(lane >> 4, T + r, tab((bwA >> (2 * r)) & 3u), tab((bwB >> (2 * r)) & 3u));
         }
     }
     // everything block `blk` of the packed sweep reads from the rings
@@ -170,7 +234,7 @@ struct PRing {
             put_a(sub, k, cA, cB);
         }
         const int64_t Ba = ta.b_base + ta.begin_b, Bb = tb.b_base + tb.begin_b;
-        for (int k = T0 - (LPT - 1) + tl; k <= T0 + ROWS - 1; k += LPT) put_b(sub, k, pk_tab(code2_at(ta.b2, Ba + k)), pk_tab(code2_at(tb.b2, Bb + k)));
+        for (int k = T0 - (LPT - 1) + tl; k <= T0 + ROWS - 1; k += LPT) put_b(sub, k, tab(code2_at(ta.b2, Ba + k)), tab(code2_at(tb.b2, Bb + k)));
     }
 };
 
@@ -240,21 +304,30 @@ __device__ __forceinline__ void cap_table(const int wlane, const int half, const
         *reinterpret_cast<int4*>(s_captab[LPT == 64 ? 0 : wlane >> 4][half]) = e;
     }
 }
-template <int C, int CE, int LPT, bool LAST>
+// PAT: the row holds patterns (pair_range of the two-task kernel): value = pattern - PAT_OFF + base
+template <int C, int CE, int LPT, bool LAST, bool PAT = false>
 __device__ __forceinline__ void side_capture(const int wlane, const int half, const int T, const int base, const u32 (&Lp)[C], const int cap_max, giptr const cap_slot)
 {
     const int lane = wlane & (LPT - 1);
     const int4 e = *reinterpret_cast<const int4*>(s_captab[LPT == 64 ? 0 : wlane >> 4][half]);
     const int cE = e.x - (C - 1) * lane - T;
     if ((u32)cE < (u32)cap_max && T <= e.y + lane) {
-        const _Float16 vE = PRing<C, LPT>::cap_pick(wlane, half, Lp, cE);
-        cap_slot[e.z - lane + T] = (int)(float)vE + base + 8 * (lane - e.x - T);
+        if constexpr (PAT) {
+            const u32 vE = PRing<C, LPT>::cap_pick_pat(wlane, half, Lp, cE);
+            cap_slot[e.z - lane + T] = pat_decode(vE) + base + 8 * (lane - e.x - T);
+        } else {
+            const _Float16 vE = PRing<C, LPT>::cap_pick(wlane, half, Lp, cE);
+            cap_slot[e.z - lane + T] = (int)(float)vE + base + 8 * (lane - e.x - T);
+        }
     }
     if constexpr (LAST) {
         if (T == e.y + lane && cap_max > 0) {   // the lane's last row (cap_max: C, CE + 1 in the band's last lane, 0 behind it)
             giptr const lp = cap_slot + (e.w + C * lane);
             const int k1 = base - 16 * e.y - 8 * C * lane;
-            auto put = [&](const int c) __attribute__((always_inline)) { lp[c] = (int)(float)(half ? hi_of(Lp[c]) : lo_of(Lp[c])) + (k1 - 8 * c); };
+            auto put = [&](const int c) __attribute__((always_inline)) {
+                if constexpr (PAT) lp[c] = pat_decode(half ? pat_hi(Lp[c]) : pat_lo(Lp[c])) + (k1 - 8 * c);
+                else lp[c] = (int)(float)(half ? hi_of(Lp[c]) : lo_of(Lp[c])) + (k1 - 8 * c);
+            };
 #pragma unroll
             for (int c = 0; c <= CE; ++c) put(c);
             if (cap_max == C) {
@@ -279,7 +352,9 @@ template <int C, int CE, bool END, int LPT = 64>
 __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, const Tk* tpa, const Tk* tpb, const int blk_begin_, const int blk_end_, const int wlane)
 {
     static_assert(CE >= 0 && CE < C - 1 && (LPT == QL || (C - 1) % 16 == 0), "band 512 on 64 lanes (transposed ring A) or band 150 on 16");
-    typedef PRing<C, LPT> PR;
+    // PAT: the two-task kernel keeps its halves as integer patterns (the pattern format, above); the eight-task kernel as f16 numbers
+    constexpr bool PAT = (LPT == 64);
+    typedef PRing<C, LPT, PAT> PR;
     const Tk ta = load_tk<LPT>(tpa), tb = load_tk<LPT>(tpb);
     const int blk_begin = uni(blk_begin_), blk_end = uni(blk_end_);
     const int lane = wlane & (LPT - 1);  // lane within the task: owns band columns [C*lane, C*lane + C)
@@ -291,14 +366,25 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
         // bases: the lane's own column 0; dead lanes (NEG everywhere) get 0
         baseA = (sta->Lp[0] <= NEG / 2) ? 0 : (sta->Lp[0] >> 2);
         baseB = (stb->Lp[0] <= NEG / 2) ? 0 : (stb->Lp[0] >> 2);
-#pragma unroll
-        for (int c = 0; c < C; ++c) Lp[c] = pk(g4_to_h(sta->Lp[c], baseA), g4_to_h(stb->Lp[c], baseB));
-        Lin = pk(g4_to_h(sta->Lin, baseA), g4_to_h(stb->Lin, baseB));
         // what has to be added to a value that arrives from the left / right neighbour: its base minus mine
         const int lA = __shfl_up(baseA, 1, LPT), lB = __shfl_up(baseB, 1, LPT), rA = __shfl_down(baseA, 1, LPT), rB = __shfl_down(baseB, 1, LPT);
         const bool hasL = lane >= 1 && lane <= LE, hasR = lane < LE;
-        dL = hasL ? pk((_Float16)(float)(lA - baseA), (_Float16)(float)(lB - baseB)) : 0u;
-        dR = hasR ? pk((_Float16)(float)(rA - baseA), (_Float16)(float)(rB - baseB)) : 0u;
+        if constexpr (PAT) {
+            // NEG -> 0xFC00: lane 0's Lin (it stays that: the DPP shift leaves lane 0 alone, its dL is 0 and the re-centring skips
+            // it) and the cells of the dead lanes and columns, which an add turns into garbage that only dead cells ever see (below)
+#pragma unroll
+            for (int c = 0; c < C; ++c) Lp[c] = g4_to_pat(sta->Lp[c], baseA) | (g4_to_pat(stb->Lp[c], baseB) << 16);
+            Lin = g4_to_pat(sta->Lin, baseA) | (g4_to_pat(stb->Lin, baseB) << 16);
+            // signed differences as 16-bit two's complement: added per half (pat_add), never with a 32-bit add
+            dL = hasL ? pk16(lA - baseA, lB - baseB) : 0u;
+            dR = hasR ? pk16(rA - baseA, rB - baseB) : 0u;
+        } else {
+#pragma unroll
+            for (int c = 0; c < C; ++c) Lp[c] = pk(g4_to_h(sta->Lp[c], baseA), g4_to_h(stb->Lp[c], baseB));
+            Lin = pk(g4_to_h(sta->Lin, baseA), g4_to_h(stb->Lin, baseB));
+            dL = hasL ? pk((_Float16)(float)(lA - baseA), (_Float16)(float)(lB - baseB)) : 0u;
+            dR = hasR ? pk((_Float16)(float)(rA - baseA), (_Float16)(float)(rB - baseB)) : 0u;
+        }
         // selector window of row-time blk_begin*16: W[k] <-> a index begin_a - band + (C-1)*lane + T0 + k
         const int T0 = blk_begin * ROWS;
         const int64_t sa = ta.a_base + ta.begin_a - ta.band + (int64_t)(C - 1) * lane + T0, sb = tb.a_base + tb.begin_a - tb.band + (int64_t)(C - 1) * lane + T0;
@@ -306,7 +392,7 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
         const u32 wa2 = (C - 1 > 16) ? fetch16(ta.a2, sa + 16) : 0u, wb2 = (C - 1 > 16) ? fetch16(tb.a2, sb + 16) : 0u;
 #pragma unroll
         for (int k = 0; k < C - 1; ++k)
-            W[k] = (k < 16) ? pk_sel((wa >> (2 * k)) & 3u, (wb >> (2 * k)) & 3u) : pk_sel((wa2 >> (2 * (k - 16))) & 3u, (wb2 >> (2 * (k - 16))) & 3u);
+            W[k] = (k < 16) ? PR::sel((wa >> (2 * k)) & 3u, (wb >> (2 * k)) & 3u) : PR::sel((wa2 >> (2 * (k - 16))) & 3u, (wb2 >> (2 * (k - 16))) & 3u);
 #pragma unroll
         for (int k = C - 1; k < C + 15; ++k) W[k] = 0;
     }
@@ -323,10 +409,17 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
     // s_waitcnt then sits behind the boundary stores the previous block issued a moment ago and drains them (SQ_WAIT_ANY 21 %
     // of a lone wavefront's time, ~1 500 cycles per block; hidden behind the other wavefronts only when a SIMD has four).
     asm volatile("" : "+v"(aA_lo), "+v"(aA_hi), "+v"(bA_lo), "+v"(bA_hi), "+v"(aB_lo), "+v"(aB_hi), "+v"(bB_lo), "+v"(bB_hi));
-    const h2 three = {(_Float16)3.0f, (_Float16)3.0f};
+    [[maybe_unused]] const h2 three = {(_Float16)3.0f, (_Float16)3.0f};
     const bool no_up = lane == LE;  // the last band column (column CE of this lane) has no `up` source
     typedef Strip<LPT, true> ST;
     typedef PairFmt<C, LPT> FMT;
+    // PAT, the range argument: the lanes re-centre on column 0 at group ends, a column grows by at most 21 per row and a lane's C
+    // columns span at most (C - 1) x 21, so between two re-centrings a live value of a lane -- its columns, the chain value from the
+    // left (which may lie below column 0), the hand-off from the right (above column C - 1), each a neighbour of one of the lane's
+    // own cells -- stays within SPAN + 21 of the lane's base on either side: 1 701 for 17 columns, where 7 168 are free below
+    // PAT_OFF and 23 509 above it.
+    constexpr int SPAN = (C - 1) * 21 + FMT::RC * ROWS * 21;
+    static_assert(!PAT || ((int)PAT_OFF - (SPAN + 21) >= (int)PAT_MIN && (int)PAT_OFF + SPAN + 21 <= (int)PAT_MAX), "the live patterns of a group stay normal, finite f16 numbers");
     constexpr int NB = ST::NB, FI = ST::FI;
     const int sshift = uni(ta.sshift);
     const bool edge = ST::opens_strip(wlane, sshift);
@@ -387,8 +480,15 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
                 const int r = g / C, c = g % C;
                 m[g % 3] = __builtin_amdgcn_perm(tB[r & 1], tA[r & 1], W[WX(r + c)]);
             };
+            // PAT: the looked-up word is (sB << 16) | sA with s = 12 or 21, the diag candidate one 32-bit add (v_add_u32) -- the low
+            // half of a live cell cannot carry (PAT_MAX).  A dead cell's can: into the other task's half of the SAME register, which
+            // is the same column of the same lane and dead as well, because the two tasks of a unit share Y (LE, CE).  Dead are the
+            // lanes behind LE and the columns behind CE in lane LE; what they hold reaches no live cell: the one `up` source that
+            // could is cut off in do_max (no_up), the chain value runs left to right, away from the band, and lane LE + 1 hands its
+            // column 0 to column C - 1 of lane LE, a dead one.  Rows past a task's X - 1 (END) are ordinary cells on padding.
             auto do_fma = [&](const int g) __attribute__((always_inline)) {
-                D[g % 2] = as_u(__builtin_elementwise_fma(as_h2(m[g % 3]), three, as_h2(Lp[g % C])));
+                if constexpr (PAT) D[g % 2] = m[g % 3] + Lp[g % C];
+                else D[g % 2] = as_u(__builtin_elementwise_fma(as_h2(m[g % 3]), three, as_h2(Lp[g % C])));
             };
             auto do_max = [&](const int g) __attribute__((always_inline)) {
                 const int c = g % C;
@@ -416,7 +516,9 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
                     }
                     if (c == 2) xkeep = lane_shl1<LPT>(xkeep, (int)Lp[0]);   // lane l <- lane l+1 of the same task
                     if (c == 3) {
-                        x = as_u(as_h2((u32)xkeep) + as_h2(dR));
+                        // (PAT: lanes >= LE have dR = 0 and take their neighbour's word as it is -- 0xFC00 in lane 63, a dead lane's
+                        // column 0 otherwise --: it feeds column C - 1 of a lane whose columns behind CE are dead)
+                        x = PAT ? pat_add((u32)xkeep, dR) : as_u(as_h2((u32)xkeep) + as_h2(dR));
                         lds_store2_masked<4 * (r % FI) * NB, 4 * (NB * FI + (r % FI) * NB)>(sb, Lrecv, Lp[0], edge_mask);
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -426,12 +528,12 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
                 // after the row's last maximum (a hazard nop per row-time otherwise)
                 if constexpr (r + 2 < ROWS) { W[WX(C + 1 + r)] = PR::a_read(ringA_lane, r + 2); tA[r & 1] = rbA[r + 2]; tB[r & 1] = rbB[r + 2]; }
                 Lin = (u32)lane_shr1<LPT>((int)Lin, (int)L);  // lane l <- lane l-1 ; lane 0 of a task keeps -inf
-                // (lane 0's own previous Lin is -inf relative to any base: adding dL = 0 leaves it)
-                Lin = as_u(as_h2(Lin) + as_h2(dL));
+                // (lane 0's own previous Lin is -inf relative to any base: adding dL = 0 leaves it -- as a pattern, 0xFC00 + 0)
+                Lin = PAT ? pat_add(Lin, dL) : as_u(as_h2(Lin) + as_h2(dL));
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (END) {
-                    side_capture<C, CE, LPT, true>(wlane, 0, tau0 + r, baseA, Lp, cap_max, cap_slot);
-                    side_capture<C, CE, LPT, true>(wlane, 1, tau0 + r, baseB, Lp, cap_max, cap_slot);
+                    side_capture<C, CE, LPT, true, PAT>(wlane, 0, tau0 + r, baseA, Lp, cap_max, cap_slot);
+                    side_capture<C, CE, LPT, true, PAT>(wlane, 1, tau0 + r, baseB, Lp, cap_max, cap_slot);
                 }
                 if ((r % FI) == FI - 1) {
                     // the staging area is full: its [slot][received | handed][FI row-times] image (Strip::offset) leaves as one
@@ -458,6 +560,25 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
             // garbage that never reaches a live cell -- the one `up` source that could is cut off above -- and do not
             // count.)  Kept cheap -- a packed maximum of magnitudes, ~45 instructions per block -- so that the diagnostics
             // build stays usable for timing.  A violation marks the task(s): finish_walk reports GAMDP_ST_DIAG_RANGE.
+            // PAT: the same cells, integer compares on the patterns, both bounds: [PAT_MIN, PAT_MAX]
+            if constexpr (PAT) {
+                auto mn = [](const u32 a, const u32 b) { return __builtin_bit_cast(u32, __builtin_elementwise_min(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b))); };
+                auto mx = [](const u32 a, const u32 b) { return __builtin_bit_cast(u32, __builtin_elementwise_max(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b))); };
+                u32 nIn = 0xFFFFFFFFu, xIn = 0, nOut = 0xFFFFFFFFu, xOut = 0;   // packed min / max over the columns inside the band in every lane / only in lanes < LE
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    if (c <= CE) { nIn = mn(nIn, Lp[c]); xIn = mx(xIn, Lp[c]); }
+                    else { nOut = mn(nOut, Lp[c]); xOut = mx(xOut, Lp[c]); }
+                }
+                if (lane >= 1) { nIn = mn(nIn, Lin); xIn = mx(xIn, Lin); }
+                const u32 xv = pat_add((u32)xkeep, dR);
+                if (blk > blk_begin) { nOut = mn(nOut, xv); xOut = mx(xOut, xv); }
+                if (lane < LE) { nIn = mn(nIn, nOut); xIn = mx(xIn, xOut); }
+                if (lane <= LE) {
+                    if (pat_lo(nIn) < PAT_MIN || pat_lo(xIn) > PAT_MAX) ta.pos0[-1] = 1;
+                    if (pat_hi(nIn) < PAT_MIN || pat_hi(xIn) > PAT_MAX) tb.pos0[-1] = 1;
+                }
+            } else {
             u32 mIn = 0, mOut = 0;   // packed max |value| over the columns that are inside the band in every lane / only in lanes < LE
 #pragma unroll
             for (int c = 0; c < C; ++c) {
@@ -473,6 +594,7 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
                 if (!((float)lo_of(mIn) < 2040.0f)) ta.pos0[-1] = 1;
                 if (!((float)hi_of(mIn) < 2040.0f)) tb.pos0[-1] = 1;
             }
+            }
         }
 #endif
         // Re-centre on column 0 (both tasks at once) at GROUP ends only (FMT::RC = 4 blocks): a column grows by at most 21 per row
@@ -481,6 +603,23 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
         // relative to ONE pair of bases per lane, the ones in its checkpoint row (PairFmt::GRP); its packed ranges begin and end at
         // group boundaries (run_octo), so "the last block of the range" is a group end too.  The two-task kernel keeps its per-block
         // base words (they simply repeat within a group).
+        // PAT: integer arithmetic per half.  What the f16 form got from -inf / NaN being absorbing is said outright: a lane behind LE
+        // holds garbage and shifts nothing (its base stays what it was), a live lane's column 0 is a live cell, lane 0's Lin stays
+        // 0xFC00, and only the lanes that take a hand-off adjust its base difference.
+        if constexpr (PAT) {
+            if ((blk & (FMT::RC - 1)) == FMT::RC - 1 || blk + 1 == blk_end) {
+                const u32 d = (lane <= LE) ? pat_sub(Lp[0], PAT_OFF2) : 0u;
+                baseA += (int)(short)pat_lo(d);
+                baseB += (int)d >> 16;
+#pragma unroll
+                for (int c = 0; c < C; ++c) Lp[c] = pat_sub(Lp[c], d);
+                if (lane != 0) Lin = pat_sub(Lin, d);
+                const u32 dl = (u32)lane_shr1<LPT>((int)d, (int)d);  // left neighbour's shift (a task's lane 0: its own)
+                const u32 dr = (u32)lane_shl1<LPT>((int)d, (int)d);  // right neighbour's (its last lane: its own)
+                if (lane >= 1 && lane <= LE) dL = pat_sub(pat_add(dL, dl), d);
+                if (lane < LE) dR = pat_sub(pat_add(dR, dr), d);
+            }
+        } else
         if ((blk & (FMT::RC - 1)) == FMT::RC - 1 || blk + 1 == blk_end) {
             const float fa = (float)lo_of(Lp[0]), fb = (float)hi_of(Lp[0]);
             const bool oka = fa > -60000.0f && fa < 60000.0f, okb = fb > -60000.0f && fb < 60000.0f;
@@ -515,12 +654,19 @@ __device__ __noinline__ void pair_range(BlockState<C>* sta, BlockState<C>* stb, 
         for (int blk = blk_begin; blk < blk_end; ++blk) block_body(std::integral_constant<int, 0>{}, blk);
     }
     // back to the int32 states (direction words empty, rings and a-window to be primed by the caller's next step)
+    // PAT: a lane behind LE goes back to NEG, as it came (its words are garbage by now); a pattern with the top bit set -- lane 0's
+    // Lin, or what a dead column of lane LE may hold -- is NEG too
+    const bool dead_lane = PAT && lane > LE;
+    auto back = [&](const u32 v, const int half, const int base) -> int {
+        if constexpr (PAT) return dead_lane ? NEG : pat_to_g4(half ? pat_hi(v) : pat_lo(v), base);
+        else return h_to_g4(half ? hi_of(v) : lo_of(v), base);
+    };
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        sta->Lp[c] = h_to_g4(lo_of(Lp[c]), baseA); stb->Lp[c] = h_to_g4(hi_of(Lp[c]), baseB);
+        sta->Lp[c] = back(Lp[c], 0, baseA); stb->Lp[c] = back(Lp[c], 1, baseB);
         sta->acc[c] = 0; stb->acc[c] = 0;
     }
-    sta->Lin = h_to_g4(lo_of(Lin), baseA); stb->Lin = h_to_g4(hi_of(Lin), baseB);
+    sta->Lin = back(Lin, 0, baseA); stb->Lin = back(Lin, 1, baseB);
     sta->Lout = sta->Lp[C - 1]; stb->Lout = stb->Lp[C - 1];
 }
 
@@ -628,7 +774,14 @@ __device__ __noinline__ void pair_top_range(BlockState<C>* sta, BlockState<C>* s
         PR::template produce<true>(T, wlane, __builtin_amdgcn_alignbit(aA_hi, aA_lo, shaA), __builtin_amdgcn_alignbit(aB_hi, aB_lo, shaB),
                                    __builtin_amdgcn_alignbit(bA_hi, bA_lo, shbA), __builtin_amdgcn_alignbit(bB_hi, bB_lo, shbB), km1A, km1B);
         if ((blk & 3) == 0) {
-            ck_store<C, LPT>(ckpt + (u64)(blk >> 2) * FMT::CK_WORDS, wlane, Lp, baseA, baseB);
+            if constexpr (LPT == 64) {
+                // the two-task kernel's slot holds ONE layout, the pattern format: the top blocks compute in f16 (the NaN marker
+                // needs it) and convert what they store -- checkpoint rows here, boundary words below; the bases are the same
+                u32 Pp[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) Pp[c] = h2_to_pat(Lp[c]);
+                ck_store<C, LPT>(ckpt + (u64)(blk >> 2) * FMT::CK_WORDS, wlane, Pp, baseA, baseB);
+            } else ck_store<C, LPT>(ckpt + (u64)(blk >> 2) * FMT::CK_WORDS, wlane, Lp, baseA, baseB);
             g0A = baseA; g0B = baseB;
         }
         if constexpr (!FMT::GRP) {
@@ -676,8 +829,8 @@ __device__ __noinline__ void pair_top_range(BlockState<C>* sta, BlockState<C>* s
             cell(0);
             xkeep = lane_shl1<LPT>(xkeep, (int)Lp[0]);
             x = as_u(as_h2((u32)xkeep) + as_h2(dR));
-            lds_store2_masked<4 * (r % FI) * NB, 4 * (NB * FI + (r % FI) * NB)>(sb, FMT::GRP ? as_u(as_h2(Lrecv) + as_h2(Kpk)) : Lrecv,
-                                                                               FMT::GRP ? as_u(as_h2(Lp[0]) + as_h2(Kpk)) : Lp[0], edge_mask);
+            lds_store2_masked<4 * (r % FI) * NB, 4 * (NB * FI + (r % FI) * NB)>(sb, FMT::GRP ? as_u(as_h2(Lrecv) + as_h2(Kpk)) : h2_to_pat(Lrecv),
+                                                                               FMT::GRP ? as_u(as_h2(Lp[0]) + as_h2(Kpk)) : h2_to_pat(Lp[0]), edge_mask);
 #pragma unroll
             for (int c = 1; c < C; ++c) cell(c);
             Lin = (u32)lane_shr1<LPT>((int)Lin, (int)L);

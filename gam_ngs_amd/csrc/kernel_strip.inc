@@ -60,7 +60,15 @@ __device__ __forceinline__ void materialise_impl(const Tk* tp, const int q_, con
     // packed f16 pair -> G4 of this task, branch-free (a branch per row made the loop spill): -inf ("no source": what
     // lane 0 of the band receives, the rows of dead lanes) is clamped to -2^27, which as a G4 value (about -2^29) loses
     // every comparison against a live value just like NEG does; +inf / NaN only ever sit in dead cells.
+    // Two-task kernel (LPT == 64): the slot holds patterns (kernel_pair.inc, the pattern format), read as SIGNED 16-bit: a bit-field
+    // extract and an add.  A live value decodes exactly.  A "no source" word has the top bit set -- 0xFC00 from the plain ranges,
+    // the clamped -inf of the top blocks -- and decodes at least 9 000 below the base of the lane that stored it, when the live
+    // values of that lane and of its neighbours lie within ~2 000 of it: it loses every comparison against them, as NEG does.
+    // (Where it must lose against everything -- the stream right of the task's last lane -- the base is NEG_BASE.)
     auto unpack = [&](const u32 v, const int base) -> int {
+        if constexpr (PK && LPT == 64) {
+            return 4 * (pat_decode(HALF ? v >> 16 : v & 0xFFFFu) + base);
+        }
         const float f = __builtin_amdgcn_fmed3f((float)(HALF ? hi_of(v) : lo_of(v)), -134217728.0f, 134217728.0f);
         return 4 * ((int)f + base);
     };
