@@ -58,6 +58,18 @@ class Context:
         _check(self, self.lib.gamdp_ctx_l1_hits_stats(self.handle, C.byref(st)), "gamdp_ctx_l1_hits_stats")
         return st.as_dict()
 
+    def set_l1_chain(self, mode: int):
+        """Which kernel runs the main chains of alignMergeBlocks on the device: L.L1_CHAIN_WALK (the default: k_chain2, band 150,
+        scratch slots from the arena) or L.L1_CHAIN_CARRY (k_chain_c: any band up to 543, no scratch; gamdp_ctx_set_l1_chain).
+        The results do not depend on it."""
+        _check(self, self.lib.gamdp_ctx_set_l1_chain(self.handle, mode), "gamdp_ctx_set_l1_chain")
+
+    def l1_chain_stats(self):
+        """The chain launch of the last alignMergeBlocks on this context, as a dict (gamdp_ctx_l1_chain_stats)."""
+        st = L.L1ChainStats()
+        _check(self, self.lib.gamdp_ctx_l1_chain_stats(self.handle, C.byref(st)), "gamdp_ctx_l1_chain_stats")
+        return st.as_dict()
+
     def l1_tail_calls(self):
         """The tail alignments of the last alignMergeBlocks on this context and the seed each was given, as
         (merge_block, right, begin_a, source) tuples ordered by merge block, left before right (gamdp_ctx_l1_tail_calls)."""
@@ -185,6 +197,22 @@ class MultiContext:
         for i in range(len(self.devices)):
             if self.lib.gamdp_ctx_set_l1_hits(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
                 raise L.GamdpError("gamdp_ctx_set_l1_hits(%r) failed on context %d" % (mode, i))
+
+    def set_l1_chain(self, mode: int):
+        """Context.set_l1_chain on every context of the handle."""
+        for i in range(len(self.devices)):
+            if self.lib.gamdp_ctx_set_l1_chain(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
+                raise L.GamdpError("gamdp_ctx_set_l1_chain(%r) failed on context %d" % (mode, i))
+
+    def l1_chain_stats(self):
+        """Context.l1_chain_stats of every context of the handle (a list of dicts)."""
+        out = []
+        for i in range(len(self.devices)):
+            st = L.L1ChainStats()
+            if self.lib.gamdp_ctx_l1_chain_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
+                raise L.GamdpError("gamdp_ctx_l1_chain_stats failed on context %d" % i)
+            out.append(st.as_dict())
+        return out
 
     def l1_hits_stats(self):
         """Context.l1_hits_stats of every context of the handle (a list of dicts)."""

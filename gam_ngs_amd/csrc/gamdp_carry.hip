@@ -29,300 +29,7 @@ namespace gamdp {
 namespace {
 
 #include "gamdp_score_common.inc"
-
-constexpr int K_DEAD = -32;            // what a column beyond the band's last adds on its diagonal in the fast blocks
-// The dead-column argument of k_score (gamdp_score.hip), here needed in its strict form: what comes back into the band's last column
-// through `up` from the columns beyond it is at least 12 below that column's own diagonal candidate, so the last column's value never
-// EQUALS its `up` and the fast step rule never takes an `up` the reference does not have there (:292, :303)
-static_assert(-2 * S_GAP >= 16 && -(S_MAX_SCORE + K_DEAD) >= 16 && 16 + S_MIN_SCORE >= 12, "the band's last column could equal its dead `up`");
-// What the kernel reads outside the sequences (the planes are padded by SEQ_PAD_BASES on either side).  In front of a: band bases
-// (pos = begin_a - band + ...), fetched as whole words.  Behind a: lane 63 takes the base at begin_a - band + 63 (C-1) + C + tau with
-// tau < X + LE, X <= |a| + band - begin_a (preflight_hd), LE <= 63; a fast block fetches the window of the block behind it, which
-// begins at a row-time <= X - 1 (K_BLOCK row-times on from one that is fast); a fetch reads 64 bases on from its index (load_win) -- at
-// C = 17 at most 63 * 16 + 17 + 63 + 64 bases behind |a|.  b: rows begin_b + tau, X <= |b| - begin_b.
-constexpr int K_BLOCK = 32;            // row-times of a fast block: what one fetch of 32 bases feeds
-static_assert(543 + 64 <= SEQ_PAD_BASES && 63 * 16 + 17 + 63 + 64 + 64 <= SEQ_PAD_BASES && K_BLOCK <= 32, "k_carry's fetches would leave the padded planes");
-constexpr int K_XSHIFT = 2048;         // cell code x * 2048 + y
-static_assert(543 * 2 + 2 < K_XSHIFT && (int64_t)500001 * K_XSHIFT + K_XSHIFT < (int64_t)1 << 31, "a cell code does not fit an int32");
-
-enum : int { OP_DIAG = 0, OP_UP = 1, OP_LEFT = 2 };   // MATCH or MISMATCH (x--), GAP_A (x--, y++), GAP_B (y--)
-
-struct Sum { int B, ln, nm, F, Lc; };
-__device__ __forceinline__ Sum sum_from_lane_below(const Sum& s) { return {from_lane_below(s.B), from_lane_below(s.ln), from_lane_below(s.nm), from_lane_below(s.F), from_lane_below(s.Lc)}; }
-__device__ __forceinline__ Sum sum_from_lane_above(const Sum& s) { return {from_lane_above(s.B), from_lane_above(s.ln), from_lane_above(s.nm), from_lane_above(s.F), from_lane_above(s.Lc)}; }
-__device__ __forceinline__ Sum pick(const bool d, const Sum& sd, const bool u, const Sum& su, const Sum& sl)
-{
-    return {d ? sd.B : (u ? su.B : sl.B), d ? sd.ln : (u ? su.ln : sl.ln), d ? sd.nm : (u ? su.nm : sl.nm), d ? sd.F : (u ? su.F : sl.F), d ? sd.Lc : (u ? su.Lc : sl.Lc)};
-}
-// one more op in front of the traceback t; `match`: it is a MATCH (:239, :274) at the cell with code `cur`
-__device__ __forceinline__ Sum step_on(Sum t, const bool match, const int cur)
-{
-    t.F = (match && t.nm == 0) ? cur : t.F;
-    t.Lc = match ? cur : t.Lc;
-    t.nm += match ? 1 : 0;
-    t.ln += 1;
-    return t;
-}
-
-template <int C>
-struct CWave {
-    int h[C];        // the lane's cells of the row it was at last: value ...
-    int sB[C], sln[C], snm[C], sF[C], sLc[C];   // ... and summary, a register array per field
-    int a5[C];       // 5 * code of the a bases its columns meet at this row-time (pos = A0 + tau + (C-1) * lane + c)
-    int dead[C];     // fast blocks: 0, or -32 for a column beyond the band's last (the lane holds C columns whatever the band)
-    int leftadd;     // fast blocks: what column 0's `left` adds: 0, or S_NEG in lane 0 (no column left of it)
-    u32 row;         // the scoring-matrix row (fields S + 16) of the lane's b base (comes up from the lane below)
-    SWin sa, sb;     // slow_step's bases (wave-uniform): the a bases lane 63 takes and the b bases lane 0 takes, from row-time tau - used on
-    int used;
-    int64_t aidx, bidx;   // index of the a base lane 63 takes at row-time 0 / of the b base of row 0
-    int bv, bk;           // best candidate of the end-cell search so far: value, scan position ...
-    Sum bs;               // ... and its summary
-
-    __device__ __forceinline__ Sum sum(const int c) const { return {sB[c], sln[c], snm[c], sF[c], sLc[c]}; }
-    __device__ __forceinline__ void set_sum(const int c, const Sum& t) { sB[c] = t.B; sln[c] = t.ln; snm[c] = t.nm; sF[c] = t.F; sLc[c] = t.Lc; }
-
-    // Row-time k of a fast block (every lane that holds band columns is at a row >= 1 below the last, every pos inside (0, |a|), no
-    // candidate of the end-cell search goes by): every cell is sw[i][j] = max(sw[i-1][j] + S, sw[i-1][j+1] + gap, sw[i][j-1] + gap)
-    // (:160-164), kept as sw[i][j] + 16 i + 8 j so that the gap terms add nothing and the diagonal adds the unsigned field S + 16.
-    // The traceback's step from such a cell (:265-307, x > 0, pos > 0): diag if the value equals the diagonal candidate, else up if
-    // 0 < y < Y-1 and it equals `up`, else left; y == 0: up; y == Y-1: left.  All three candidates carry the same offset, so the
-    // comparisons are those of the reference.  Column 0 has no `left` candidate (S_NEG in lane 0), so "not diag" is "equals up" there;
-    // the last column never equals its dead `up` (see K_DEAD).  The a window moves by one register per row-time (a5[c] <- a5[c+1]).
-    __device__ __forceinline__ void fast_cell(const int c, const int uv, const Sum& su, const int lv, const Sum& sl, const int cur)
-    {
-        const int f = cell_score16(row, a5[c]);
-        const int dv = h[c] + f + dead[c];
-        const int v = max3i(dv, uv, lv);
-        const bool isd = v == dv, isu = v == uv;
-        set_sum(c, step_on(pick(isd, sum(c), isu, su, sl), isd && f != S_MIN_SCORE + 16, cur));
-        h[c] = v;
-    }
-    __device__ __forceinline__ void fast_step(const SWin& wa, const SWin& wb, const int k, const int cur0)
-    {
-        row = (u32)shift_in_from_below((int)score_row16(win_code(wb, k), win_isn(wb, k)), (int)row);
-        const int L = from_lane_below(h[C - 1]) + leftadd;
-        const Sum Ls = sum_from_lane_below(sum(C - 1));
-        fast_cell(0, h[1], sum(1), L, Ls, cur0);
-        const int U = from_lane_above(h[0]);   // (lane 63 gets 0, for a column that is always dead: 2*band+1 is odd, 64*C even)
-        const Sum Us = sum_from_lane_above(sum(0));
-#pragma unroll
-        for (int c = 1; c < C - 1; ++c) fast_cell(c, h[c + 1], sum(c + 1), h[c - 1], sum(c - 1), cur0 + c);
-        fast_cell(C - 1, U, Us, h[C - 2], sum(C - 2), cur0 + C - 1);
-        const int enters = shift_in_from_above(a_field(win_code(wa, k), win_isn(wa, k)), a5[1]);
-#pragma unroll
-        for (int c = 0; c < C - 1; ++c) a5[c] = a5[c + 1];
-        a5[C - 1] = enters;
-    }
-    // into / out of the fast blocks' form in front of row-time tau: the lane's cells are those of row tau - 1 - lane
-    __device__ __forceinline__ void to_block(const int tau, const int lane)
-    {
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] = dead[c] ? S_NEG : h[c] + 16 * (tau - 1 - lane) + 8 * (C * lane + c);
-    }
-    __device__ __forceinline__ void from_block(const int tau, const int lane)
-    {
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] -= 16 * (tau - 1 - lane) + 8 * (C * lane + c);
-    }
-
-    // One row-time by the reference's rules, cell by cell: the value as in k_score's slow_step (:112-168), then the step the traceback
-    // takes from the cell (:229-308) and the summary it leaves.  Lanes that are not at a row of the matrix, and cells outside a,
-    // compute along: a traceback never enters them (pos does not grow along it, and a cell with x < 0, y < 0 or pos < 0 ends it).
-    __device__ __forceinline__ void slow_step(const STask& t, const int tau, const int lane)
-    {
-        if (used == 32) {
-            sa = load_win_uniform(t.a2, t.an, aidx + tau);
-            sb = load_win_uniform(t.b2, t.bn, bidx + tau);
-            used = 0;
-        }
-        row = (u32)shift_in_from_below((int)score_row16(win_code(sb, used), win_isn(sb, used)), (int)row);
-        const int i = tau - lane;
-        const int p0 = t.A0 + tau + (C - 1) * lane, j0 = C * lane;
-        const bool row0 = i == 0;
-        const int L = from_lane_below(h[C - 1]);   // (lane 0: unused, its column 0 has no left neighbour)
-        const Sum Ls = sum_from_lane_below(sum(C - 1));
-        int U = 0;
-        Sum Us = {0, 0, 0, 0, 0};
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int pos = p0 + c, j = j0 + c;
-            const int sc = cell_score16(row, a5[c]) - 16;
-            const bool in_a = (u32)pos < (u32)t.alen;
-            const int leftv = c > 0 ? h[c > 0 ? c - 1 : 0] : L;
-            const int upv = c < C - 1 ? h[c < C - 1 ? c + 1 : 0] : U;
-            const Sum lefts = c > 0 ? sum(c > 0 ? c - 1 : 0) : Ls;
-            const Sum ups = c < C - 1 ? sum(c < C - 1 ? c + 1 : 0) : Us;
-            const int dold = h[c];
-            // row 0 (:112-132): `left` is the neighbour itself, without a gap
-            const bool has_left = pos > 0 && j > 0;
-            const bool r0_gap = t.fs ? (u32)pos <= (u32)S_MAXGAP : in_a;                 // :116
-            const bool r0_forced = t.fs && pos > S_MAXGAP && pos < t.alen;               // :125
-            const int v_gap = has_left ? max3i(sc, S_GAP, leftv) : max(S_GAP, sc);
-            const int v_forced = has_left ? max(sc, leftv) : sc;
-            const int v0 = r0_gap ? v_gap : (r0_forced ? v_forced : 0);
-            // rows >= 1 (:141-168)
-            const int up = j < t.Y - 1 ? upv + S_GAP : S_NEG;
-            const int left = pos == 0 ? ((t.fs && i > S_MAXGAP) ? S_NEG : S_GAP) : (j > 0 ? leftv + S_GAP : S_NEG);
-            const int vn = in_a ? max3i(dold + sc, up, left) : 0;
-            const int v = row0 ? v0 : vn;
-            // the traceback's step from this cell.  pos == 0 (:229-262): diag is the score alone, left the gap score (nothing for a
-            // forced start beyond FORCE_MAXGAP_LEN rows), and the last column goes left whatever it holds
-            const int op_p0 = v == sc ? OP_DIAG : ((j == t.Y - 1 || v == ((t.fs && i > S_MAXGAP) ? S_NEG : S_GAP)) ? OP_LEFT : OP_UP);
-            // pos > 0 (:263-308): row 0 has no cell above (diag from 0; up the gap score, or nothing for a forced start beyond
-            // FORCE_MAXGAP_LEN, :269-270); columns 0 and Y-1 compare with the diagonal only
-            const int t_diag = (row0 ? 0 : dold) + sc;
-            const int t_up = row0 ? ((t.fs && pos > S_MAXGAP) ? S_NEG : S_GAP) : (j < t.Y - 1 ? upv + S_GAP : S_GAP);
-            const int op_in = v == t_diag ? OP_DIAG : (j > 0 && j < t.Y - 1) ? (v == t_up ? OP_UP : OP_LEFT) : (j < t.Y - 1 ? OP_UP : OP_LEFT);
-            const int op = pos == 0 ? op_p0 : op_in;
-            // the cell the step leads to: outside (x < 0, y < 0 or pos < 0) the traceback ends and the summary begins (:227, :321)
-            const bool ends = op == OP_DIAG ? (row0 || pos == 0) : op == OP_UP ? row0 : (j == 0 || pos == 0);
-            const int bcode = op == OP_DIAG ? i * K_XSHIFT + j + 1 : op == OP_UP ? i * K_XSHIFT + j + 2 : (i + 1) * K_XSHIFT + j;
-            Sum nt = pick(op == OP_DIAG, sum(c), op == OP_UP, ups, lefts);
-            if (ends) nt = {bcode, 0, 0, 0, 0};
-            set_sum(c, step_on(nt, op == OP_DIAG && sc != S_MIN_SCORE, i * K_XSHIFT + j));
-            h[c] = v;
-            if (c == 0) { U = from_lane_above(h[0]); Us = sum_from_lane_above(sum(0)); }
-        }
-        // the end-cell search (:174-212) as in k_score: the larger value, then the smaller scan position
-        const bool active = i >= 0 && i < t.X;
-        const bool last_row = active && !t.fe && i == t.X - 1;
-        const bool on_diag = active && t.ea >= p0 && t.ea <= p0 + C - 1 &&
-                             (!t.fe || (t.X >= S_MAXGAP + 1 && i >= t.X - 1 - S_MAXGAP));   // :201, an unsigned compare there
-        if (__any(last_row || on_diag)) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int pos = p0 + c, j = j0 + c;
-                const bool ok_row = last_row && j < t.Y && pos >= 0 && pos <= t.ea;
-                const bool ok_diag = on_diag && j < t.Y && pos == t.ea;
-                const int key = ok_row ? j : t.Y + (i - t.iA);
-                const int v = h[c];   // (a cell outside a holds 0, as the reference's matrix does)
-                if ((ok_row || ok_diag) && (v > bv || (v == bv && key < bk))) { bv = v; bk = key; bs = sum(c); }
-            }
-        }
-        // the window moves on by one base
-        const int enters = shift_in_from_above(a_field(win_code(sa, used), win_isn(sa, used)), a5[1]);
-#pragma unroll
-        for (int c = 0; c < C - 1; ++c) a5[c] = a5[c + 1];
-        a5[C - 1] = enters;
-        ++used;
-    }
-};
-
-// One task.  Inlined into k_carry: a call would cost the callee-saved registers' stack slots, and the kernel is to use no private memory.
-template <int C>
-__device__ __forceinline__ void carry_task(const DevTask& dt, DevResult* results, const int lane)
-{
-    STask t;
-    t.a2 = (splane)dt.a2; t.an = (splane)dt.an; t.b2 = (splane)dt.b2; t.bn = (splane)dt.bn;
-    const int band = dt.band;
-    t.A0 = dt.begin_a - band;
-    t.alen = dt.alen; t.X = dt.X; t.Y = 2 * band + 1;
-    t.ea = (int)min(dt.end_a, (int64_t)S_POS_MAX);
-    const int64_t over = dt.end_a - ((int64_t)dt.begin_a + band);
-    t.iA = over >= 0 ? (int)min(over, (int64_t)(1 << 30)) : 0;
-    t.fs = (dt.flags & TF_FORCE_START) != 0; t.fe = (dt.flags & TF_FORCE_END) != 0;
-    const int LE = (t.Y - 1) / C;   // the lane that holds the band's last column
-
-    CWave<C> w;
-    const int64_t ap = dt.a_base + t.A0 + (int64_t)(C - 1) * lane;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int64_t k = ap + c;
-        w.h[c] = 0;
-        w.set_sum(c, {0, 0, 0, 0, 0});
-        w.a5[c] = a_field((t.a2[k >> 4] >> ((u32)(k & 15) * 2u)) & 3u, ((t.an[k >> 5] >> (u32)(k & 31)) & 1u) != 0);
-        w.dead[c] = (C * lane + c >= t.Y) ? K_DEAD : 0;
-    }
-    w.leftadd = lane == 0 ? S_NEG : 0;
-    w.aidx = dt.a_base + t.A0 + 63 * (C - 1) + C;
-    w.bidx = dt.b_base + dt.begin_b;
-    w.sa = load_win_uniform(t.a2, t.an, w.aidx);
-    w.sb = load_win_uniform(t.b2, t.bn, w.bidx);
-    w.used = 0;
-    w.row = 0;
-    w.bv = S_NEG; w.bk = S_KEY_NONE;
-    w.bs = {0, 0, 0, 0, 0};
-
-    // The G row-times from tau on are fast when, in lanes 0 .. LE: every row is >= 1 and every pos > 0 (lane 0, column 0 has the
-    // smallest); the highest row, lane 0's, is below the last; every pos < |a| (lane LE, column C-1 has the largest); and pos == end_a
-    // is in nobody's columns.  span = what the largest pos of the block is above the smallest of its first row-time.
-    constexpr int G = K_BLOCK;
-    const int span = G - 1 + (LE + 1) * (C - 1);
-    const int f_lo = max(LE + 1, 1 - t.A0);
-    const int f_hi = min(t.X - 1 - G, t.alen - t.A0 - span - 1);
-    const int64_t d_hi64 = (int64_t)t.ea - t.A0;
-    const int d_hi = (int)min(d_hi64, (int64_t)0x7fffffff), d_lo = (int)max(min(d_hi64 - span, (int64_t)0x7fffffff), (int64_t)-0x7fffffff);
-    auto fast = [&](const int tau) { return tau >= f_lo && tau <= f_hi && (tau < d_lo || tau > d_hi); };
-    const int T = t.X + LE;   // lane LE is at the last row at row-time X - 1 + LE
-    for (int tau = 0; tau < T;) {
-        if (fast(tau)) {
-            // a run of fast blocks: the bases of a block are fetched while the block before it is computed
-            SWin wa = load_win_uniform(t.a2, t.an, w.aidx + tau), wb = load_win_uniform(t.b2, t.bn, w.bidx + tau);
-            w.to_block(tau, lane);
-            int cur = (tau - lane) * K_XSHIFT + C * lane;   // the code of the lane's column 0 at this row-time
-            do {
-                const SWin na = load_win(t.a2, t.an, w.aidx + tau + G), nb = load_win(t.b2, t.bn, w.bidx + tau + G);   // (all lanes the same words)
-#pragma nounroll
-                for (int k = 0; k < G; ++k) {
-                    w.fast_step(wa, wb, k, cur);
-                    cur += K_XSHIFT;
-                }
-                wa.lo = (u32)__builtin_amdgcn_readfirstlane((int)na.lo); wa.hi = (u32)__builtin_amdgcn_readfirstlane((int)na.hi); wa.n = (u32)__builtin_amdgcn_readfirstlane((int)na.n);
-                wb.lo = (u32)__builtin_amdgcn_readfirstlane((int)nb.lo); wb.hi = (u32)__builtin_amdgcn_readfirstlane((int)nb.hi); wb.n = (u32)__builtin_amdgcn_readfirstlane((int)nb.n);
-                tau += G;
-            } while (fast(tau));
-            w.from_block(tau, lane);
-            w.sa = wa; w.sb = wb; w.used = 0;
-        } else {
-            w.slow_step(t, tau, lane);
-            ++tau;
-        }
-    }
-
-    // the winner of the end-cell search, and its summary from the lane that holds it (a scan position belongs to one cell, so to one lane)
-    int bv = w.bv, bk = w.bk;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int ov = __shfl_xor(bv, o, 64), ok = __shfl_xor(bk, o, 64);
-        if (ov > bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
-    }
-    bv = __builtin_amdgcn_readfirstlane(bv);
-    bk = __builtin_amdgcn_readfirstlane(bk);
-    DevResult res;
-    res.begin_a = res.begin_b = res.score = 0;
-    res.n_match = res.length = 0;
-    res.first_a = res.first_b = res.last_a = res.last_b = 0;
-    u32 status = S_ST_EMPTY;   // no end cell (:215)
-    u32 found = 0;
-    if (bk != S_KEY_NONE) {
-        const int x = bk < t.Y ? t.X - 1 : t.iA + (bk - t.Y);
-        const int pos = bk < t.Y ? t.A0 + x + bk : t.ea;
-        if (pos >= t.alen) status = S_ST_OUT_OF_RANGE;   // the traceback's a.at(pos) throws
-        else {
-            status = S_ST_OK;
-            const unsigned long long holders = __ballot(w.bk == bk);
-            const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)holders) - 1);
-            Sum e;
-            e.B = __builtin_amdgcn_readlane(w.bs.B, src); e.ln = __builtin_amdgcn_readlane(w.bs.ln, src); e.nm = __builtin_amdgcn_readlane(w.bs.nm, src);
-            e.F = __builtin_amdgcn_readlane(w.bs.F, src); e.Lc = __builtin_amdgcn_readlane(w.bs.Lc, src);
-            const int xb = e.B / K_XSHIFT, yb = e.B % K_XSHIFT - 1;
-            res.begin_a = t.A0 + xb + yb; res.begin_b = dt.begin_b + xb;   // :321
-            res.score = bv;
-            res.n_match = (u32)e.nm; res.length = (u32)e.ln;
-            if (e.nm > 0) {
-                res.first_a = t.A0 + e.F / K_XSHIFT + e.F % K_XSHIFT; res.first_b = dt.begin_b + e.F / K_XSHIFT;
-                res.last_a = t.A0 + e.Lc / K_XSHIFT + e.Lc % K_XSHIFT; res.last_b = dt.begin_b + e.Lc / K_XSHIFT;
-                found = 3;
-            } else {
-                // no MATCH: first_match_pos ends behind the last op (my_alignment.cc:167-193), last_match_pos keeps the begin (:228-262)
-                res.first_a = pos + 1; res.first_b = dt.begin_b + x + 1;
-                res.last_a = res.begin_a; res.last_b = res.begin_b;
-            }
-        }
-    }
-    res.flags = found | (status << 8) | ((u32)C << CARRY_COLS_SHIFT);   // (the instantiation, for gamdp_ctx_carry_info)
-    if (lane == 0) results[dt.res_idx] = res;
-}
+#include "gamdp_carry_task.inc"   // Sum, CWave<C>, carry_task<C>: shared with k_chain_c (gamdp_chain_carry.hip)
 
 // The task loop.  k_score (gamdp_score.hip) documents what went wrong there with the task inlined and nothing between the record
 // store that ends a task and the cursor fetch that begins the next (both `if (lane == 0)`): the compiler threaded lane 0 from the one
@@ -343,7 +50,9 @@ __global__ __launch_bounds__(64, C <= 3 ? 5 : C == 5 ? 4 : C == 9 ? 2 : 1) void 
         if (lane == 0) ti = atomicAdd(p.cursor, 1u);
         ti = __builtin_amdgcn_readfirstlane(ti);
         if (ti >= p.n_tasks) break;
-        carry_task<C>(p.tasks[ti], p.results, lane);
+        const DevTask& dt = p.tasks[ti];
+        const DevResult res = carry_task<C>(dt, lane);
+        if (lane == 0) p.results[dt.res_idx] = res;
     }
 }
 

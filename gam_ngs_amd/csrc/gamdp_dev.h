@@ -333,4 +333,13 @@ const char* carry_kernel_name(int cols);     // e.g. "k_carry<5>"; the instantia
 int carry_waves_per_cu(int cols);            // resident wavefronts per CU, from the occupancy the runtime reports
 int launch_carry(int cols, const CarryParams& p, unsigned n_wavefronts, void* stream);   // returns hipError_t as int
 
+// ---- the main chain of a merge block on carry_task (k_chain_c, gamdp_chain_carry.hip; GAMDP_L1_CHAIN_CARRY) ---------------------
+// One wavefront (a workgroup of 64) per merge block, both orientation attempts one after the other; any band up to 543, the
+// instantiation a band takes is score_cols(band).  The grid is one workgroup per merge block of the launch, in the list's order:
+// workgroup g takes merge block first_mb + g.  Same records at the same indices and the same hand-over as k_chain2 (ChainOut,
+// ChainWin, the pinned mirror, host_done); ChainWin::info bit 1 is 0 and state 3 does not occur.  Not read: scratch, ypad, sync,
+// n_twins, cursor, max_rows, n_margin, n_by_contig, and of a DevMB rows, has_n, npre_*, max_x and the slot fields.
+const char* chain_carry_kernel_name(int cols);   // e.g. "k_chain_c<5>"
+int launch_chain_carry(int cols, const ChainParams& p, unsigned n_workgroups, void* stream);   // returns hipError_t as int
+
 }  // namespace gamdp

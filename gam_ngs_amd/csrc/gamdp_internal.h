@@ -55,6 +55,7 @@ struct Tuning {
     int l1_cohorts = 0;                 // GAMDP_L1_COHORTS=k (1..16): cohorts of a merge-block call (0: by its size)
     size_t l1_cohort_min = 48;          // GAMDP_L1_COHORT_MIN=m (1 or more): merge blocks per cohort at least
     bool l1_device_hits = false;        // GAMDP_L1_DEVICE_HITS=1: new contexts start in GAMDP_L1_HITS_DEVICE mode (gamdp_ctx_set_l1_hits)
+    bool l1_chain_carry = false;        // GAMDP_L1_CHAIN_CARRY=1: new contexts start in GAMDP_L1_CHAIN_CARRY mode (gamdp_ctx_set_l1_chain)
 };
 const Tuning& tuning();
 
@@ -209,6 +210,10 @@ struct Ctx {
     int l1_hits_mode = GAMDP_L1_HITS_HOST;
     gamdp_l1_hits_stats last_l1_hits{};
     std::vector<gamdp_l1_tail_call> last_l1_tails;   // gamdp_ctx_l1_tail_calls
+    // which kernel runs the main chains of a merge-block call on the device (gamdp_ctx_set_l1_chain), and what the last call's
+    // chain launch was
+    int l1_chain = GAMDP_L1_CHAIN_WALK;
+    gamdp_l1_chain_stats last_l1_chain{};
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }

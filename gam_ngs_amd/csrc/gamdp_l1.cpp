@@ -393,8 +393,9 @@ namespace {
 // the round loop: a chain that ends copies its result records into a pinned mirror and raises a flag; the cohort that owns the
 // merge block then replays its own machine over those records (so every decision is taken twice: a difference is an internal
 // error, not a wrong answer) and sends what is left -- the tail alignments, at most two more calls -- through its next round,
-// while longer chains are still running.  Band 150 (the only band gam-merge runs); anything else, and GAMDP_L1_ROUNDS=1, keeps
-// the round loop for the whole call.
+// while longer chains are still running.  GAMDP_L1_CHAIN_WALK (k_chain2): band 150 (the only band gam-merge runs), scratch slots
+// from the arena; GAMDP_L1_CHAIN_CARRY (k_chain_c, gamdp_chain_carry.hip): any band up to GAMDP_MAX_TUNED_BAND, no scratch, one
+// launch, no twins.  Anything else, and GAMDP_L1_ROUNDS=1, keeps the round loop for the whole call.
 struct ChainRun {
     bool launched = false;
     size_t n_mb = 0;
@@ -410,6 +411,12 @@ struct ChainRun {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const ChainOut* dout = nullptr;   // device copy of the ChainOut list (progress markers in the diagnostics build)
     bool n_by_contig = false;         // the launch ran every call of a chain with N in its contigs on the N-aware cells
+    // which kernel the launch is (gamdp_l1_chain_stats): k_chain_c<cols> (carry; no choice of cell to compare, no scratch) or k_chain2
+    bool carry = false;
+    int cols = 0;
+    const char* kernel = "";
+    u64 scratch_bytes = 0;
+    u32 n_launches = 0, n_twins = 0;
     const SeqSet *ms = nullptr, *ss = nullptr;
     std::chrono::steady_clock::time_point t_launch;
 
@@ -657,8 +664,9 @@ bool plan_slots(const ChainSel& sel, DevMB* hmb, const u32 band, const u64 arena
 }
 
 // 6. Enqueue: the kernel's parameters, what the host keeps of the launch (`run`), upload, the launches, the two events.
+// `carry_cols`: 0 = k_chain2, else the instantiation of k_chain_c (one piece, no twins, no scratch).
 int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const ChainSlots& S, uint8_t* const dm, const u32 band,
-                   const SeqSet* ms, const SeqSet* ss, ChainRun& run)
+                   const SeqSet* ms, const SeqSet* ss, const int carry_cols, ChainRun& run)
 {
     uint8_t *const h = c->h_chain, *const d = c->d_chain, *const hm = c->h_mirror;
     ChainParams cp;
@@ -675,6 +683,11 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
     // the diagnostics build's GAMDP_DIAG_FORCE_N: by the contigs' flags, as in rounds 3-4
     cp.n_margin = (int32_t)(64 - diag().n_window_shrink); cp.n_by_contig = diag().force_n ? 1u : 0u;
     run.n_by_contig = cp.n_by_contig != 0;
+    const bool walk_n = sel.has_n || diag().force_n;
+    run.carry = carry_cols != 0;
+    run.cols = carry_cols ? carry_cols : 5;
+    run.kernel = carry_cols ? chain_carry_kernel_name(carry_cols) : (walk_n ? "k_chain2<true>" : "k_chain2<false>");
+    run.scratch_bytes = S.need_scratch * sizeof(u32); run.n_launches = (u32)S.pieces.size(); run.n_twins = (u32)S.n_tw;
     // (the events belong to `run` from here on: every path out leaves them to it)
     if (hipEventCreate(&run.e0) != hipSuccess || hipEventCreate(&run.e1) != hipSuccess) { c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
     if (diag().timing) std::fprintf(stderr, "gamdp chain: %zu merge blocks, %llu blocks, %zu piece(s), %.1f MB of scratch (slots of up to %llu words), %llu twins, has_n %d\n", (size_t)L.n_mb, (unsigned long long)sel.n_blk, S.pieces.size(), S.need_scratch * 4e-6, (unsigned long long)S.slotw_max, (unsigned long long)S.n_tw, (int)sel.has_n);
@@ -686,7 +699,8 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
     ok = ok && hipEventRecord(run.e0, c->chain_stream) == hipSuccess;
     for (size_t pc = 0; ok && pc < S.pieces.size(); pc++) {   // (one launch unless the arena is too small for all the slots at once)
         cp.first_mb = S.pieces[pc].first;
-        ok = launch_chain(cp, sel.has_n || diag().force_n, (unsigned)(S.pieces[pc].second + S.n_tw), c->chain_stream) == 0;
+        if (carry_cols) ok = launch_chain_carry(carry_cols, cp, (unsigned)S.pieces[pc].second, c->chain_stream) == 0;
+        else ok = launch_chain(cp, walk_n, (unsigned)(S.pieces[pc].second + S.n_tw), c->chain_stream) == 0;
     }
     ok = ok && hipEventRecord(run.e1, c->chain_stream) == hipSuccess;
     if (!ok) {
@@ -700,12 +714,15 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
 
 // Starts the launch (asynchronous).  `arena` = bytes its scratch slots may take.  Returns 0 (run.launched says whether there is
 // one: not for other bands, GAMDP_L1_ROUNDS=1, no merge block with a chain, or a frame too long for the arena) or an error code.
+// CARRY mode (Ctx::l1_chain): any band the carry kernels take, no slot plan and no scratch, no twins, one launch for all.
 int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const SeqSet* ss, const u32 band, const u64 arena, ChainRun& run)
 {
     run.launched = false;
-    if (tuning().l1_rounds || band != 150) return 0;
-    const ChainSel sel = select_chains(M, ms, ss);
+    const bool carry = c->l1_chain == GAMDP_L1_CHAIN_CARRY;
+    if (tuning().l1_rounds || (carry ? band > GAMDP_MAX_TUNED_BAND : band != 150)) return 0;
+    ChainSel sel = select_chains(M, ms, ss);
     if (sel.ch.empty()) return 0;
+    if (carry) sel.n_tw = 0;
     int rc_ = ss->ensure_rc(sel.need_rc, c);
     if (rc_) return rc_;
     const ChainLayout L(sel.ch.size(), sel.n_blk, sel.n_tw);
@@ -714,10 +731,19 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
     DevMB* const hmb = (DevMB*)(c->h_chain + L.mb);
     describe_chains(M, sel, ms, ss, hmb, (DevBlk*)(c->h_chain + L.blk), run.q_of);
     ChainSlots slots;
-    if (!plan_slots(sel, hmb, band, arena, slots)) return 0;
-    // (the slots themselves: exactly what the pieces need -- the arena is a budget, a quarter to spare would overdraw it)
-    if ((rc_ = grow(c, c->d_chain_scratch, c->cap_chain_scratch, slots.need_scratch, true))) return rc_;
-    if ((rc_ = enqueue_chains(c, sel, L, slots, d_mirror, band, ms, ss, run))) return rc_;
+    if (carry) {
+        // (k_chain_c reads none of the slot fields: zeroed, so that the upload does not carry what an earlier call left there)
+        for (size_t q = 0; q < sel.ch.size(); q++) {
+            DevMB& x = hmb[q];
+            x.max_x = 0; x.slot_off[0] = x.slot_off[1] = 0; x.slot_words = x.dir_words = x.ckpt_off = x.bnd_off = 0;
+        }
+        slots.pieces.emplace_back(0u, (u32)sel.ch.size());
+    } else {
+        if (!plan_slots(sel, hmb, band, arena, slots)) return 0;
+        // (the slots themselves: exactly what the pieces need -- the arena is a budget, a quarter to spare would overdraw it)
+        if ((rc_ = grow(c, c->d_chain_scratch, c->cap_chain_scratch, slots.need_scratch, true))) return rc_;
+    }
+    if ((rc_ = enqueue_chains(c, sel, L, slots, d_mirror, band, ms, ss, carry ? score_cols(band) : 0, run))) return rc_;
     for (const ChainPick& p : sel.ch) M[p.mi].on_device = true;
     return 0;
 }
@@ -727,11 +753,12 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
 // next call from the records so far (Machine::pending, PctgBuilder.cc:1652-1677) and runs its own pre-checks; the two must
 // agree in every number -- window, orientation, rows, status -- or the call fails with GAMDP_EHIP naming the merge block and the
 // call: a chain kernel that derived a different window can not hand back a plausible wrong answer.
-int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi)
+int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi, u64* calls_used)
 {
     const u32 q = run.q_of[mi];
     const DevMB& x = run.hmb[q];
     const u32 n_dp = run.hout[q].n_dp;
+    *calls_used = 0;
     if ((run.hout[q].state & 0xffu) == 3u) {   // a call did not fit the chain's scratch slots: nothing of the chain is used, the round loop takes the merge block
         m.on_device = false;
         return 0;
@@ -757,7 +784,7 @@ int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi)
         if ((w.info & 1u) != (t.b_rc ? 1u : 0u)) return differs("orientation", w.info & 1u, t.b_rc ? 1u : 0u);
         if ((w.info >> 8) != (u32)st) return differs("pre-check status", w.info >> 8, (u64)st);
         if (w.X != (u32)X) return differs("row count", w.X, X);
-        {   // the cell the device picked for this call (N by window): the host's own answer for the same window, with the full margin
+        if (!run.carry) {   // the cell the device picked for this call (N by window): the host's own answer for the same window, with the full margin (k_chain_c has one cell: nothing to compare)
             const bool want_n = st == GAMDP_ST_OK && x.has_n != 0 &&
                                 (run.n_by_contig || run.ms->window_has_n(t.a_id, false, 0, (int64_t)t.begin_a - (int64_t)run.band - 64, (int64_t)t.begin_a + (int64_t)X - 1 + (int64_t)run.band + 64) ||
                                  run.ss->window_has_n(t.b_id, t.b_rc, 0, (int64_t)t.begin_b - 64, (int64_t)t.begin_b + (int64_t)X - 1 + 64));
@@ -770,6 +797,7 @@ int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi)
         used++;
     }
     if (used != n_dp) { cc->set_error("internal: the device's chain of merge block " + std::to_string(mi) + " is longer than the host's"); return GAMDP_EHIP; }
+    *calls_used = used;
     return 0;
 }
 
@@ -777,6 +805,7 @@ struct CohortStats {
     int rounds = 0; double pending_ms = 0, align_ms = 0, feed_ms = 0; int rc = 0;
     gamdp_l1_hits_stats hits{};   // the findHits calls of this cohort
     std::vector<gamdp_l1_tail_call> tails;   // ... and the seed each gave its tail call
+    u64 chains = 0, chain_calls = 0;         // chains of the launch this cohort replayed and used, and their records (gamdp_l1_chain_stats)
 };
 
 inline auto now() { return std::chrono::steady_clock::now(); }
@@ -890,8 +919,10 @@ void run_cohort(Ctx* c, std::vector<Machine>& M, const std::vector<u32>& ids, Rc
             size_t keep = 0;
             for (u32 i : waiting) {
                 if (run.ended(run.q_of[i])) {
-                    st.rc = replay_chain(c, run, M[i], i);
+                    u64 calls_used = 0;
+                    st.rc = replay_chain(c, run, M[i], i, &calls_used);
                     if (st.rc) return;
+                    if (M[i].on_device) { st.chains++; st.chain_calls += calls_used; }
                 } else waiting[keep++] = i;
             }
             waiting.resize(keep);
@@ -1130,6 +1161,8 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
         if (hipEventRecord(c->ref_event, c->stream) != hipSuccess || hipEventSynchronize(c->ref_event) != hipSuccess) { c->set_error("hipEventRecord failed"); return GAMDP_EHIP; }
         // the main chains: one launch on the device, beside the round loops that take over what it hands back
         ChainRun run;
+        u64 n_main = 0;   // merge blocks with a main chain to run at all
+        for (const Machine& m : M) n_main += m.phase == Machine::MAIN ? 1u : 0u;
         if ((rc_ = launch_main_chains(c, M, ms, ss, band, arena.chain_arena, run))) return rc_;
         const bool chained = run.launched;
         if (!chained) arena.no_chains();
@@ -1147,6 +1180,18 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
             }
         if (rc_fin) return rc_fin;
         collect_stats(c, n, out, K, cst, intervals, chained, chain_at, chain_ms, k0_ms, k0_n);
+        {   // gamdp_ctx_l1_chain_stats
+            gamdp_l1_chain_stats& Q = c->last_l1_chain;
+            Q = gamdp_l1_chain_stats{};
+            Q.mode = (uint32_t)c->l1_chain;
+            for (const CohortStats& s : cst) { Q.chains += s.chains; Q.chain_calls += s.chain_calls; }
+            Q.round_loop_mbs = n_main - Q.chains;
+            if (chained) {
+                Q.scratch_bytes = run.scratch_bytes; Q.launches = run.n_launches; Q.twins = run.n_twins; Q.cols = (uint32_t)run.cols;
+                std::snprintf(Q.kernel, sizeof(Q.kernel), "%s", run.kernel);
+                Q.chain_ms = (double)chain_ms;
+            }
+        }
         gamdp_l1_stats& S = c->last_l1;
         S.wall_ms = msec(t_begin, now());
         if (gamdp::diag().timing)
@@ -1161,6 +1206,24 @@ extern "C" int gamdp_ctx_set_l1_hits(gamdp_ctx* ctx, int mode)
 {
     if (!ctx || (mode != GAMDP_L1_HITS_HOST && mode != GAMDP_L1_HITS_DEVICE)) return GAMDP_EINVAL;
     reinterpret_cast<Ctx*>(ctx)->l1_hits_mode = mode;
+    return 0;
+}
+
+static_assert(sizeof(gamdp_l1_chain_stats) == 80 && offsetof(gamdp_l1_chain_stats, scratch_bytes) == 24 && offsetof(gamdp_l1_chain_stats, mode) == 32 &&
+              offsetof(gamdp_l1_chain_stats, cols) == 44 && offsetof(gamdp_l1_chain_stats, kernel) == 48 && offsetof(gamdp_l1_chain_stats, chain_ms) == 72,
+              "gamdp_l1_chain_stats: the layout include/gamdp.h documents (gam_ngs_amd/lib.py L1ChainStats mirrors it)");
+
+extern "C" int gamdp_ctx_set_l1_chain(gamdp_ctx* ctx, int mode)
+{
+    if ((mode != GAMDP_L1_CHAIN_WALK && mode != GAMDP_L1_CHAIN_CARRY) || !ctx) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->l1_chain = mode;
+    return 0;
+}
+
+extern "C" int gamdp_ctx_l1_chain_stats(const gamdp_ctx* ctx, gamdp_l1_chain_stats* out)
+{
+    if (!ctx || !out) return GAMDP_EINVAL;
+    *out = reinterpret_cast<const Ctx*>(ctx)->last_l1_chain;
     return 0;
 }
 

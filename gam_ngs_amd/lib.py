@@ -24,11 +24,13 @@ SYMBOLS = [
     "gamdp_no_blocks_contigs", "gamdp_no_blocks_after_filter", "gamdp_pctgs_not_merged", "gamdp_fasta_write_selected",
     "gamdp_find_hits_batch", "gamdp_ctx_set_l1_hits", "gamdp_ctx_l1_hits_stats",
     "gamdp_ctx_l1_tail_calls", "gamdp_score_batch", "gamdp_ctx_score_info", "gamdp_carry_batch", "gamdp_ctx_carry_info",
+    "gamdp_ctx_set_l1_chain", "gamdp_ctx_l1_chain_stats",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
 ST_OK, ST_EMPTY, ST_OUT_OF_RANGE, ST_INVALID = 0, 1, 2, 3
 L1_HITS_HOST, L1_HITS_DEVICE = 0, 1   # gamdp_ctx_set_l1_hits
+L1_CHAIN_WALK, L1_CHAIN_CARRY = 0, 1   # gamdp_ctx_set_l1_chain
 ST_DIAG_RANGE = 9   # diagnostics build only: a packed-f16 block left the exact range (never expected)
 
 
@@ -120,6 +122,18 @@ class L1HitsStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class L1ChainStats(C.Structure):
+    """gamdp_l1_chain_stats: the chain launch of the last gamdp_align_merge_blocks (static_assert in gamdp_l1.cpp)."""
+    _fields_ = [("chains", C.c_uint64), ("chain_calls", C.c_uint64), ("round_loop_mbs", C.c_uint64), ("scratch_bytes", C.c_uint64),
+                ("mode", C.c_uint32), ("launches", C.c_uint32), ("twins", C.c_uint32), ("cols", C.c_uint32),
+                ("kernel", C.c_char * 24), ("chain_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = d["kernel"].decode()
+        return d
 
 
 class L1TailCall(C.Structure):
@@ -223,6 +237,10 @@ def load_library():
     lib.gamdp_ctx_l1_stats.argtypes = [vp, C.POINTER(L1Stats)]
     lib.gamdp_ctx_set_l1_hits.argtypes = [vp, C.c_int]
     lib.gamdp_ctx_set_l1_hits.restype = C.c_int
+    lib.gamdp_ctx_set_l1_chain.argtypes = [vp, C.c_int]
+    lib.gamdp_ctx_set_l1_chain.restype = C.c_int
+    lib.gamdp_ctx_l1_chain_stats.argtypes = [vp, C.POINTER(L1ChainStats)]
+    lib.gamdp_ctx_l1_chain_stats.restype = C.c_int
     lib.gamdp_ctx_l1_hits_stats.argtypes = [vp, C.POINTER(L1HitsStats)]
     lib.gamdp_ctx_l1_hits_stats.restype = C.c_int
     lib.gamdp_ctx_l1_tail_calls.argtypes = [vp, C.POINTER(L1TailCall), C.c_size_t, C.POINTER(C.c_size_t)]

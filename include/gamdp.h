@@ -355,6 +355,40 @@ typedef struct gamdp_l1_tail_call {
 } gamdp_l1_tail_call;
 int gamdp_ctx_l1_tail_calls(const gamdp_ctx* ctx, gamdp_l1_tail_call* out, size_t cap, size_t* n);
 
+/* Which kernel runs the main chains of gamdp_align_merge_blocks on the device (alignBlocks, PctgBuilder.cc:1617-1708, and the
+ * orientation retry of findBestAlignment, :1420-1509): one launch takes every merge block without an empty slave frame through its
+ * whole chain, and the host replays its own state machine over the records the chains leave (a difference is GAMDP_EHIP, never a
+ * wrong answer).
+ * WALK: k_chain2, a workgroup of three wavefronts per merge block (one fills, two walk), the long chains with a twin workgroup for
+ *   the other orientation.  Band 150 only, and only while three scratch slots per merge block, sized for its longest slave frame,
+ *   fit half of the arena (gamdp_ctx_set_arena_bytes): what does not fit goes in pieces, without twins, or through the round loop
+ *   (one launch and one host round trip per link of every chain), which is also what every other band takes.
+ * CARRY: k_chain_c<C>, one wavefront per merge block on gamdp_carry_batch's cell: the last match a chain's next call starts from
+ *   is in the end cell's summary when the fill ends, so there is no walk, no scratch slot (the arena does not matter), no twin, and
+ *   any band up to GAMDP_MAX_TUNED_BAND runs its chains on the device (C = 2, 3, 5, 9, 17 columns per lane by band, as
+ *   gamdp_carry_batch).  Wider bands keep the round loop.
+ * In either mode merge blocks with an empty slave frame, the tail alignments and everything under GAMDP_L1_ROUNDS=1 take the round
+ * loop.  Results, n_dp, cells and the audit trail do not depend on the mode; gamdp_l1_stats and gamdp_l1_hits_stats keep their
+ * layout and meaning.  A property of the context (gamdp_multi_align_merge_blocks honours what each gamdp_multi_ctx(m, i) was set
+ * to); GAMDP_L1_CHAIN_CARRY=1 in the environment (read once per process) makes CARRY the mode of new contexts. */
+#define GAMDP_L1_CHAIN_WALK  0   /* default: k_chain2 (band 150, scratch slots from the arena) */
+#define GAMDP_L1_CHAIN_CARRY 1   /* k_chain_c<C>: any band <= GAMDP_MAX_TUNED_BAND, no scratch */
+int gamdp_ctx_set_l1_chain(gamdp_ctx* ctx, int mode);     /* GAMDP_EINVAL for NULL / unknown mode (mode checked first) */
+/* The chain launch of the last gamdp_align_merge_blocks on this context, in either mode. */
+typedef struct gamdp_l1_chain_stats {
+    uint64_t chains;          /* merge blocks whose main chain a chain launch ran and whose records the replay used */
+    uint64_t chain_calls;     /* records replayed: the find_alignment calls of those chains */
+    uint64_t round_loop_mbs;  /* merge blocks whose main phase took the round loop instead */
+    uint64_t scratch_bytes;   /* scratch slots of the chain launch; 0 in CARRY mode and when there was no launch */
+    uint32_t mode;            /* GAMDP_L1_CHAIN_* the call ran in */
+    uint32_t launches;        /* kernel launches of the chains (WALK: one per piece); part of gamdp_l1_stats.launches as ONE */
+    uint32_t twins;           /* twin workgroups (WALK only) */
+    uint32_t cols;            /* band columns per lane of the instantiation (WALK: 5); 0 when there was no launch */
+    char kernel[24];          /* e.g. "k_chain_c<5>" or "k_chain2<true>"; "" when there was no launch */
+    double chain_ms;          /* HIP events around the launches */
+} gamdp_l1_chain_stats;       /* 80 bytes */
+int gamdp_ctx_l1_chain_stats(const gamdp_ctx* ctx, gamdp_l1_chain_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
+
 /* ---- several GPUs of one node ------------------------------------------------------------- */
 /* Replaces gam-merge's worker pool (lib/src/pctg/ThreadedBuildPctg.cc:143-197: N pthreads, mutex-guarded cursor
  * :50-74) for this path: one host thread + context + resident copy of the sequences per device; the task / merge-block
