@@ -64,6 +64,12 @@ class Context:
         The results do not depend on it."""
         _check(self, self.lib.gamdp_ctx_set_l1_chain(self.handle, mode), "gamdp_ctx_set_l1_chain")
 
+    def set_l1_walk_bands(self, which: int):
+        """Which bands the default chain mode (L.L1_CHAIN_WALK) has a chain kernel for: L.L1_WALK_BAND_150 (the default: k_chain2 at
+        band 150, the round loop elsewhere) or L.L1_WALK_ANY_BAND (k_chain2 at 150, k_chain2g<C> at every other band up to 543;
+        gamdp_ctx_set_l1_walk_bands).  Results do not depend on it; L.L1_CHAIN_CARRY ignores it."""
+        _check(self, self.lib.gamdp_ctx_set_l1_walk_bands(self.handle, which), "gamdp_ctx_set_l1_walk_bands")
+
     def l1_chain_stats(self):
         """The chain launch of the last alignMergeBlocks on this context, as a dict (gamdp_ctx_l1_chain_stats)."""
         st = L.L1ChainStats()
@@ -203,6 +209,12 @@ class MultiContext:
         for i in range(len(self.devices)):
             if self.lib.gamdp_ctx_set_l1_chain(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
                 raise L.GamdpError("gamdp_ctx_set_l1_chain(%r) failed on context %d" % (mode, i))
+
+    def set_l1_walk_bands(self, which: int):
+        """Context.set_l1_walk_bands on every context of the handle."""
+        for i in range(len(self.devices)):
+            if self.lib.gamdp_ctx_set_l1_walk_bands(self.lib.gamdp_multi_ctx(self.handle, i), which) != 0:
+                raise L.GamdpError("gamdp_ctx_set_l1_walk_bands(%r) failed on context %d" % (which, i))
 
     def l1_chain_stats(self):
         """Context.l1_chain_stats of every context of the handle (a list of dicts)."""

@@ -278,6 +278,12 @@ struct ChainParams {
 };
 int launch_chain(const ChainParams& p, bool has_n, unsigned n_workgroups, void* stream);   // returns hipError_t as int
 int chain_slots_per_workgroup();   // scratch slots a k_chain2 workgroup goes round (1 + its walker wavefronts)
+// k_chain2g<cols>: k_chain2's workgroup around the generic N-aware cell (any band up to 543, cols = score_cols(band)).  Same records,
+// twins and hand-over; every call that runs a DP runs the N-aware cell (ChainWin::info bit 1 set).  The slots of a DevMB are laid out
+// for kernel_info[chain_gen_kernel_id(cols)], the K_GEN_* row whose fill and walk the kernel runs.
+int chain_gen_kernel_id(int cols);
+const char* chain_gen_kernel_name(int cols);   // e.g. "k_chain2g<9>"
+int launch_chain_gen(int cols, const ChainParams& p, unsigned n_workgroups, void* stream);   // returns hipError_t as int
 
 // What the host needs to know of a kernel variant: one row per KernelId (kernel_info, gamdp_kernel.hip, next to the layout
 // constants the rows are built from).

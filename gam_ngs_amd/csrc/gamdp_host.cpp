@@ -86,6 +86,7 @@ const Tuning& tuning()
         if ((e = std::getenv("GAMDP_L1_COHORT_MIN"))) x.l1_cohort_min = (size_t)std::max(1L, std::atol(e));
         if ((e = std::getenv("GAMDP_L1_DEVICE_HITS"))) x.l1_device_hits = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_L1_CHAIN_CARRY"))) x.l1_chain_carry = std::atoi(e) == 1;
+        if ((e = std::getenv("GAMDP_L1_WALK_ANY_BAND"))) x.l1_walk_any_band = std::atoi(e) == 1;
         return x;
     }();
     return t;
@@ -305,6 +306,7 @@ int Ctx::init(int dev)
     device = dev;
     l1_hits_mode = tuning().l1_device_hits ? GAMDP_L1_HITS_DEVICE : GAMDP_L1_HITS_HOST;
     l1_chain = tuning().l1_chain_carry ? GAMDP_L1_CHAIN_CARRY : GAMDP_L1_CHAIN_WALK;
+    walk_bands = tuning().l1_walk_any_band ? GAMDP_L1_WALK_ANY_BAND : GAMDP_L1_WALK_BAND_150;
     if (hipSetDevice(dev) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("hipGetDeviceProperties failed"); return GAMDP_ENODEV; }

@@ -56,6 +56,7 @@ struct Tuning {
     size_t l1_cohort_min = 48;          // GAMDP_L1_COHORT_MIN=m (1 or more): merge blocks per cohort at least
     bool l1_device_hits = false;        // GAMDP_L1_DEVICE_HITS=1: new contexts start in GAMDP_L1_HITS_DEVICE mode (gamdp_ctx_set_l1_hits)
     bool l1_chain_carry = false;        // GAMDP_L1_CHAIN_CARRY=1: new contexts start in GAMDP_L1_CHAIN_CARRY mode (gamdp_ctx_set_l1_chain)
+    bool l1_walk_any_band = false;      // GAMDP_L1_WALK_ANY_BAND=1: new contexts start with GAMDP_L1_WALK_ANY_BAND (gamdp_ctx_set_l1_walk_bands)
 };
 const Tuning& tuning();
 
@@ -213,6 +214,7 @@ struct Ctx {
     // which kernel runs the main chains of a merge-block call on the device (gamdp_ctx_set_l1_chain), and what the last call's
     // chain launch was
     int l1_chain = GAMDP_L1_CHAIN_WALK;
+    int walk_bands = GAMDP_L1_WALK_BAND_150;   // WALK mode: the bands that have a chain kernel (gamdp_ctx_set_l1_walk_bands); CARRY ignores it
     gamdp_l1_chain_stats last_l1_chain{};
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 

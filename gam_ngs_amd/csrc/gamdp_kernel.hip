@@ -700,7 +700,8 @@ __global__ __launch_bounds__(64, GAMDP_WAVES_PER_SIMD) void k_align_q(const Laun
 }
 
 // ---- the main chain of a merge block, one filling and CH_NW walking wavefronts (structures and rationale: gamdp_dev.h) ------
-// Band 150 only (gam-merge's live band): the one-task kernel shape k_align<5, 0, HASN> run call after call.  Everything but the DP
+// k_chain2: band 150 (gam-merge's live band), the one-task kernel shape k_align<5, 0, HASN> run call after call; k_chain2g<C>: every
+// other band up to 543, the shape of k_align<C, -1, true> (opt-in, GAMDP_L1_WALK_ANY_BAND).  Everything but the DP
 // itself is wave-uniform integer arithmetic that restates gamdp_l1.cpp's Machine for the MAIN phase (PctgBuilder.cc:1420-1509,
 // 1617-1724); the host replays that machine over the audit list afterwards.
 // A lone wavefront issues one instruction every ~5 cycles whatever it does, and a fifth of a chain's instructions are the end-cell
@@ -709,7 +710,10 @@ __global__ __launch_bounds__(64, GAMDP_WAVES_PER_SIMD) void k_align_q(const Laun
 // the walk meets.  So the workgroup has two wavefronts and two scratch slots: wavefront 0 fills call k + 1 into one slot while
 // wavefront 1 walks call k in the other (ChainMail, kernel_finish.inc).  Same calls, same records, same order in the audit list.
 // role: 0 = the whole chain (both attempts, one after the other), 1 = the first attempt of a chain that has a twin, 2 = the twin
-template <bool HASN>
+// The cell is a template parameter: <5, 0, HASN> is band 150 (k_chain2: N by window, HASN = may a call of this chain need the N-aware
+// cell at all); <C, -1, true> is any other band up to 543 (k_chain2g<C>: the generic direction-keeping cell of k_align<C, -1, true>,
+// N-aware in every call as in the K_GEN_* batch kernels -- no choice by window, ChainWin::info bit 1 set for every call that runs a DP).
+template <int C, int CE, bool HASN>
 __device__ __forceinline__ void chain_filler(const ChainParams& cp, const LaunchParams& p, const u32 mi, u32* slots, const int lane, const int role)
 {
     u32 t_begin = diag_clock();
@@ -761,7 +765,8 @@ __device__ __forceinline__ void chain_filler(const ChainParams& cp, const Launch
             // do not touch its runs of N).  Same window as the batch path's (gamdp_host.cpp prepare_task); the host's replay derives
             // the answer once more and compares.
             bool call_n = false;
-            if constexpr (HASN)
+            if constexpr (CE < 0) call_n = st == 0;
+            else if constexpr (HASN)
                 call_n = st == 0 && (cp.n_by_contig != 0 || call_touches_n(unip(mb->npre_a), (int64_t)mlen, false, 0, unip(mb->npre_b), (int64_t)slen, try_rev, 0, (int64_t)band,
                                                                             (int64_t)begin_a, (int64_t)begin_b, (int64_t)X, (int64_t)cp.n_margin));
             if (lane == 0) { ChainWin w; w.begin_a = begin_a; w.end_a = end_a; w.begin_b = begin_b; w.end_b = end_b; w.X = (u32)X; w.info = (try_rev ? 1u : 0u) | (call_n ? 2u : 0u) | ((u32)st << 8); cp.win[idx] = w; }
@@ -789,10 +794,11 @@ __device__ __forceinline__ void chain_filler(const ChainParams& cp, const Launch
                 dt.flags = call_n ? TF_CALL_N : 0u; dt.res_idx = idx; dt.ops_off = 0; dt.ops_cap = 0;
                 Tk t;
                 t.cancel = role == 2 ? &sy->cancel : nullptr;
-                if constexpr (HASN) {
-                    if (call_n) fill_task<5, 0, true>(dt, p, slots + (u64)par * p.slot_words, lane, false, t);
-                    else fill_task<5, 0, false>(dt, p, slots + (u64)par * p.slot_words, lane, false, t);
-                } else fill_task<5, 0, false>(dt, p, slots + (u64)par * p.slot_words, lane, false, t);
+                if constexpr (CE < 0) fill_task<C, -1, true>(dt, p, slots + (u64)par * p.slot_words, lane, false, t);
+                else if constexpr (HASN) {
+                    if (call_n) fill_task<C, CE, true>(dt, p, slots + (u64)par * p.slot_words, lane, false, t);
+                    else fill_task<C, CE, false>(dt, p, slots + (u64)par * p.slot_words, lane, false, t);
+                } else fill_task<C, CE, false>(dt, p, slots + (u64)par * p.slot_words, lane, false, t);
                 if (lane == 0) { s_mail.tk[par] = t; s_mail.dt[par] = dt; }
                 ++sent;
                 mail_post(&s_mail.filled, sent, lane);   // (after the wavefront's stores: rows, directions, side buffers)
@@ -864,7 +870,7 @@ __device__ __forceinline__ void chain_filler(const ChainParams& cp, const Launch
     if (lane == 0) __hip_atomic_store(cp.host_done + mi, cp.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <bool HASN>
+template <int C, int CE, bool HASN>
 __device__ __forceinline__ void chain_walker(const LaunchParams& p, const int lane)
 {
     __builtin_amdgcn_s_setprio(3);   // few instructions, and the filler waits for the first of them
@@ -876,17 +882,20 @@ __device__ __forceinline__ void chain_walker(const LaunchParams& p, const int la
         if (uni(s_mail.quit) != 0 && w >= uni(s_mail.total)) break;   // (quit is posted with a count past every waiting walker's call)
         const int par = w % CH_NS;
         WalkCarry wc;
-        end_cell<5, true>(&s_mail.tk[par], lane, &wc);
+        end_cell<C, true>(&s_mail.tk[par], lane, &wc);
         wc.early_seq = w + 1;
-        if constexpr (HASN) {   // (the walk of a call filled with the N-aware cell counts N as a match; chain_filler says which it was)
-            if ((u32)uni((int)s_mail.dt[par].flags) & TF_CALL_N) finish_walk<5, 0, true, 64, false, true>(&s_mail.tk[par], &s_mail.dt[par], &p, lane, 0, 0, &wc);
-            else finish_walk<5, 0, false, 64, false, true>(&s_mail.tk[par], &s_mail.dt[par], &p, lane, 0, 0, &wc);
-        } else finish_walk<5, 0, false, 64, false, true>(&s_mail.tk[par], &s_mail.dt[par], &p, lane, 0, 0, &wc);
+        if constexpr (CE < 0) finish_walk<C, -1, true, 64, false, true>(&s_mail.tk[par], &s_mail.dt[par], &p, lane, 0, 0, &wc);
+        else if constexpr (HASN) {   // (the walk of a call filled with the N-aware cell counts N as a match; chain_filler says which it was)
+            if ((u32)uni((int)s_mail.dt[par].flags) & TF_CALL_N) finish_walk<C, CE, true, 64, false, true>(&s_mail.tk[par], &s_mail.dt[par], &p, lane, 0, 0, &wc);
+            else finish_walk<C, CE, false, 64, false, true>(&s_mail.tk[par], &s_mail.dt[par], &p, lane, 0, 0, &wc);
+        } else finish_walk<C, CE, false, 64, false, true>(&s_mail.tk[par], &s_mail.dt[par], &p, lane, 0, 0, &wc);
     }
 }
 
-template <bool HASN>
-__global__ __launch_bounds__(64 * (1 + CH_NW), GAMDP_WAVES_PER_SIMD) void k_chain2(const ChainParams cp)
+// The workgroup: which merge block and which role it has, its slots, the mailbox cleared; wavefront 0 fills, the others walk.
+// CE >= 0 (band 150): HASN = the launch holds a contig with N, and the merge block's own flag picks the instance of the pair.
+template <int C, int CE, bool HASN>
+__device__ __forceinline__ void chain_workgroup(const ChainParams& cp)
 {
     const int lane = threadIdx.x & 63;
     const int wave = uni((int)(threadIdx.x >> 6));
@@ -904,18 +913,40 @@ __global__ __launch_bounds__(64 * (1 + CH_NW), GAMDP_WAVES_PER_SIMD) void k_chai
         for (int k = 0; k < CH_NS; ++k) { s_mail.early_of[k] = 0; s_mail.done_of[k] = 0; }
     }
     __syncthreads();
-    const bool mb_n = HASN && uni((int)cp.mbs[mi].has_n) != 0;
-    if (wave == 0) {
-        if constexpr (HASN) {
-            if (mb_n) chain_filler<true>(cp, p, mi, slots, lane, role);
-            else chain_filler<false>(cp, p, mi, slots, lane, role);
-        } else chain_filler<false>(cp, p, mi, slots, lane, role);
+    if constexpr (CE < 0) {
+        if (wave == 0) chain_filler<C, -1, true>(cp, p, mi, slots, lane, role);
+        else chain_walker<C, -1, true>(p, lane);
     } else {
-        if constexpr (HASN) {
-            if (mb_n) chain_walker<true>(p, lane);
-            else chain_walker<false>(p, lane);
-        } else chain_walker<false>(p, lane);
+        const bool mb_n = HASN && uni((int)cp.mbs[mi].has_n) != 0;
+        if (wave == 0) {
+            if constexpr (HASN) {
+                if (mb_n) chain_filler<C, CE, true>(cp, p, mi, slots, lane, role);
+                else chain_filler<C, CE, false>(cp, p, mi, slots, lane, role);
+            } else chain_filler<C, CE, false>(cp, p, mi, slots, lane, role);
+        } else {
+            if constexpr (HASN) {
+                if (mb_n) chain_walker<C, CE, true>(p, lane);
+                else chain_walker<C, CE, false>(p, lane);
+            } else chain_walker<C, CE, false>(p, lane);
+        }
     }
+}
+
+template <bool HASN>
+__global__ __launch_bounds__(64 * (1 + CH_NW), GAMDP_WAVES_PER_SIMD) void k_chain2(const ChainParams cp)
+{
+    chain_workgroup<5, 0, HASN>(cp);
+}
+
+// Any other band up to 543: the same workgroup around the generic cell with C columns per lane (C = score_cols(band): 2, 3, 5, 9, 17).
+// C >= 9 fills its fast blocks without directions and the walkers re-create strips on demand (materialise): at LPT = 64, PK = false
+// that code keeps its state in registers and private memory and touches no LDS, so two walkers can be in it at once, for different
+// calls; the rings, the boundary staging and the capture scratch of kernel_common.inc are the filler's alone.
+template <int C>
+__global__ __launch_bounds__(64 * (1 + CH_NW), GAMDP_WAVES_PER_SIMD) void k_chain2g(const ChainParams cp)
+{
+    static_assert(C == 2 || C == 3 || C == 5 || C == 9 || C == 17, "the column counts of the generic kernels");
+    chain_workgroup<C, -1, true>(cp);
 }
 
 }  // namespace
@@ -927,6 +958,44 @@ int launch_chain(const ChainParams& p, bool has_n, unsigned n_slots, void* strea
     ChainParams cp = p;
     void* args[] = {&cp};
     const void* f = has_n ? (const void*)k_chain2<true> : (const void*)k_chain2<false>;
+    return (int)hipLaunchKernel(f, dim3(n_slots), dim3(64 * (1 + CH_NW)), args, 0, static_cast<hipStream_t>(stream));
+}
+
+int chain_gen_kernel_id(const int cols)
+{
+    switch (cols) {
+    case 2: return K_GEN_C2;
+    case 3: return K_GEN_C3;
+    case 5: return K_GEN_C5;
+    case 9: return K_GEN_C9;
+    default: return K_GEN_C17;
+    }
+}
+
+const char* chain_gen_kernel_name(const int cols)
+{
+    switch (cols) {
+    case 2: return "k_chain2g<2>";
+    case 3: return "k_chain2g<3>";
+    case 5: return "k_chain2g<5>";
+    case 9: return "k_chain2g<9>";
+    default: return "k_chain2g<17>";
+    }
+}
+
+int launch_chain_gen(const int cols, const ChainParams& p, unsigned n_slots, void* stream)
+{
+    ChainParams cp = p;
+    void* args[] = {&cp};
+    const void* f = nullptr;
+    switch (cols) {
+    case 2: f = (const void*)k_chain2g<2>; break;
+    case 3: f = (const void*)k_chain2g<3>; break;
+    case 5: f = (const void*)k_chain2g<5>; break;
+    case 9: f = (const void*)k_chain2g<9>; break;
+    case 17: f = (const void*)k_chain2g<17>; break;
+    default: return (int)hipErrorInvalidValue;
+    }
     return (int)hipLaunchKernel(f, dim3(n_slots), dim3(64 * (1 + CH_NW)), args, 0, static_cast<hipStream_t>(stream));
 }
 

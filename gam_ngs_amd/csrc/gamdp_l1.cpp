@@ -393,9 +393,10 @@ namespace {
 // the round loop: a chain that ends copies its result records into a pinned mirror and raises a flag; the cohort that owns the
 // merge block then replays its own machine over those records (so every decision is taken twice: a difference is an internal
 // error, not a wrong answer) and sends what is left -- the tail alignments, at most two more calls -- through its next round,
-// while longer chains are still running.  GAMDP_L1_CHAIN_WALK (k_chain2): band 150 (the only band gam-merge runs), scratch slots
-// from the arena; GAMDP_L1_CHAIN_CARRY (k_chain_c, gamdp_chain_carry.hip): any band up to GAMDP_MAX_TUNED_BAND, no scratch, one
-// launch, no twins.  Anything else, and GAMDP_L1_ROUNDS=1, keeps the round loop for the whole call.
+// while longer chains are still running.  GAMDP_L1_CHAIN_WALK: scratch slots from the arena; k_chain2 at band 150 (the only band
+// gam-merge runs) and, for a context set to GAMDP_L1_WALK_ANY_BAND, k_chain2g<C> at every other band up to GAMDP_MAX_TUNED_BAND (the
+// same workgroup around the generic cell).  GAMDP_L1_CHAIN_CARRY (k_chain_c, gamdp_chain_carry.hip): any band up to
+// GAMDP_MAX_TUNED_BAND, no scratch, one launch, no twins.  Anything else, and GAMDP_L1_ROUNDS=1, keeps the round loop for the whole call.
 struct ChainRun {
     bool launched = false;
     size_t n_mb = 0;
@@ -411,8 +412,9 @@ struct ChainRun {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const ChainOut* dout = nullptr;   // device copy of the ChainOut list (progress markers in the diagnostics build)
     bool n_by_contig = false;         // the launch ran every call of a chain with N in its contigs on the N-aware cells
-    // which kernel the launch is (gamdp_l1_chain_stats): k_chain_c<cols> (carry; no choice of cell to compare, no scratch) or k_chain2
-    bool carry = false;
+    // which kernel the launch is (gamdp_l1_chain_stats): k_chain_c<cols> (carry; no choice of cell to compare, no scratch), k_chain2, or
+    // k_chain2g<cols> (generic: every call that runs a DP runs the N-aware cell)
+    bool carry = false, generic = false;
     int cols = 0;
     const char* kernel = "";
     u64 scratch_bytes = 0;
@@ -619,13 +621,15 @@ struct ChainSlots {
     u64 need_scratch = 0, slotw_max = 0, n_tw = 0;   // u32 words; the twins that are left
     u32 ypad = 0;
 };
-bool plan_slots(const ChainSel& sel, DevMB* hmb, const u32 band, const u64 arena, ChainSlots& S)
+// `ki`: the kernel_info row of the one-task kernel whose fill and walk the chain kernel runs (K_C5_CE0_N: k_chain2; K_GEN_C*:
+// k_chain2g<cols>), `cols` its band columns per lane.  Block count, direction, checkpoint and boundary words as Ctx::align sizes a
+// slot of that kernel for a task of the chain's longest frame (gamdp_host.cpp: dir_words_for and the launch planner).
+bool plan_slots(const ChainSel& sel, DevMB* hmb, const KernelInfo& ki, const u64 cols, const u32 band, const u64 arena, ChainSlots& S)
 {
     const u64 n_mb = sel.ch.size();
-    const u64 Y = 2ull * band + 1, LE = (Y - 1) / 5;
+    const u64 Y = 2ull * band + 1, LE = (Y - 1) / cols;
     const u32 ypad = S.ypad = (u32)(((2 * band + 2 + 63) / 64) * 64);
-    const KernelInfo& ki = kernel_info[K_C5_CE0_N];
-    const bool df = ki.dirfree;   // (the chain kernels' 5-column shape keeps a direction per cell: no checkpoint / boundary stores)
+    const bool df = ki.dirfree;   // (the 5-column shapes keep a direction per cell: no checkpoint / boundary stores)
     const u64 per_wg = (u64)chain_slots_per_workgroup();
     const u64 arena_words = arena / sizeof(u32);
     S.n_tw = sel.n_tw;
@@ -634,7 +638,8 @@ bool plan_slots(const ChainSel& sel, DevMB* hmb, const u32 band, const u64 arena
         DevMB& x = hmb[q];
         const u64 nblk = ((u64)sel.ch[q].longest - 1 + LE) / 16 + 1;
         const u64 dirw = ((nblk * (u64)ki.dir_block_words + 63) / 64) * 64;
-        const u64 ckptw = df ? (nblk / 4 + 2) * (u64)ki.ckpt_words : 0, bndw = df ? (nblk + 4) * (u64)ki.bnd_words : 0;
+        const u64 nblk_df = dirw / (u64)ki.dir_block_words + 1;   // (the planner's count: from the rounded direction words)
+        const u64 ckptw = df ? (nblk_df / 4 + 2) * (u64)ki.ckpt_words : 0, bndw = df ? (nblk_df + 4) * (u64)ki.bnd_words : 0;
         x.max_x = sel.ch[q].longest;
         x.dir_words = dirw; x.slot_words = dirw + 4ull * ypad + ckptw + bndw;
         x.ckpt_off = df ? dirw + 4ull * ypad : 0; x.bnd_off = x.ckpt_off + ckptw;
@@ -664,9 +669,10 @@ bool plan_slots(const ChainSel& sel, DevMB* hmb, const u32 band, const u64 arena
 }
 
 // 6. Enqueue: the kernel's parameters, what the host keeps of the launch (`run`), upload, the launches, the two events.
-// `carry_cols`: 0 = k_chain2, else the instantiation of k_chain_c (one piece, no twins, no scratch).
+// `carry_cols`: else 0, the instantiation of k_chain_c (one piece, no twins, no scratch); `gen_cols`: else 0, the instantiation of
+// k_chain2g; both 0 = k_chain2.
 int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const ChainSlots& S, uint8_t* const dm, const u32 band,
-                   const SeqSet* ms, const SeqSet* ss, const int carry_cols, ChainRun& run)
+                   const SeqSet* ms, const SeqSet* ss, const int carry_cols, const int gen_cols, ChainRun& run)
 {
     uint8_t *const h = c->h_chain, *const d = c->d_chain, *const hm = c->h_mirror;
     ChainParams cp;
@@ -685,8 +691,9 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
     run.n_by_contig = cp.n_by_contig != 0;
     const bool walk_n = sel.has_n || diag().force_n;
     run.carry = carry_cols != 0;
-    run.cols = carry_cols ? carry_cols : 5;
-    run.kernel = carry_cols ? chain_carry_kernel_name(carry_cols) : (walk_n ? "k_chain2<true>" : "k_chain2<false>");
+    run.generic = gen_cols != 0;
+    run.cols = carry_cols ? carry_cols : (gen_cols ? gen_cols : 5);
+    run.kernel = carry_cols ? chain_carry_kernel_name(carry_cols) : (gen_cols ? chain_gen_kernel_name(gen_cols) : (walk_n ? "k_chain2<true>" : "k_chain2<false>"));
     run.scratch_bytes = S.need_scratch * sizeof(u32); run.n_launches = (u32)S.pieces.size(); run.n_twins = (u32)S.n_tw;
     // (the events belong to `run` from here on: every path out leaves them to it)
     if (hipEventCreate(&run.e0) != hipSuccess || hipEventCreate(&run.e1) != hipSuccess) { c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
@@ -700,6 +707,7 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
     for (size_t pc = 0; ok && pc < S.pieces.size(); pc++) {   // (one launch unless the arena is too small for all the slots at once)
         cp.first_mb = S.pieces[pc].first;
         if (carry_cols) ok = launch_chain_carry(carry_cols, cp, (unsigned)S.pieces[pc].second, c->chain_stream) == 0;
+        else if (gen_cols) ok = launch_chain_gen(gen_cols, cp, (unsigned)(S.pieces[pc].second + S.n_tw), c->chain_stream) == 0;
         else ok = launch_chain(cp, walk_n, (unsigned)(S.pieces[pc].second + S.n_tw), c->chain_stream) == 0;
     }
     ok = ok && hipEventRecord(run.e1, c->chain_stream) == hipSuccess;
@@ -715,11 +723,14 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
 // Starts the launch (asynchronous).  `arena` = bytes its scratch slots may take.  Returns 0 (run.launched says whether there is
 // one: not for other bands, GAMDP_L1_ROUNDS=1, no merge block with a chain, or a frame too long for the arena) or an error code.
 // CARRY mode (Ctx::l1_chain): any band the carry kernels take, no slot plan and no scratch, no twins, one launch for all.
+// WALK mode: band 150 on k_chain2; with Ctx::walk_bands == GAMDP_L1_WALK_ANY_BAND every other band up to GAMDP_MAX_TUNED_BAND on
+// k_chain2g<score_cols(band)>, its slots laid out for the K_GEN_* kernel of that column count.
 int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const SeqSet* ss, const u32 band, const u64 arena, ChainRun& run)
 {
     run.launched = false;
     const bool carry = c->l1_chain == GAMDP_L1_CHAIN_CARRY;
-    if (tuning().l1_rounds || (carry ? band > GAMDP_MAX_TUNED_BAND : band != 150)) return 0;
+    const bool generic = !carry && band != 150 && c->walk_bands == GAMDP_L1_WALK_ANY_BAND;
+    if (tuning().l1_rounds || ((carry || generic) ? band > GAMDP_MAX_TUNED_BAND : band != 150)) return 0;
     ChainSel sel = select_chains(M, ms, ss);
     if (sel.ch.empty()) return 0;
     if (carry) sel.n_tw = 0;
@@ -739,11 +750,12 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
         }
         slots.pieces.emplace_back(0u, (u32)sel.ch.size());
     } else {
-        if (!plan_slots(sel, hmb, band, arena, slots)) return 0;
+        const int cols = generic ? score_cols(band) : 5;
+        if (!plan_slots(sel, hmb, kernel_info[generic ? chain_gen_kernel_id(cols) : (int)K_C5_CE0_N], (u64)cols, band, arena, slots)) return 0;
         // (the slots themselves: exactly what the pieces need -- the arena is a budget, a quarter to spare would overdraw it)
         if ((rc_ = grow(c, c->d_chain_scratch, c->cap_chain_scratch, slots.need_scratch, true))) return rc_;
     }
-    if ((rc_ = enqueue_chains(c, sel, L, slots, d_mirror, band, ms, ss, carry ? score_cols(band) : 0, run))) return rc_;
+    if ((rc_ = enqueue_chains(c, sel, L, slots, d_mirror, band, ms, ss, carry ? score_cols(band) : 0, generic ? score_cols(band) : 0, run))) return rc_;
     for (const ChainPick& p : sel.ch) M[p.mi].on_device = true;
     return 0;
 }
@@ -784,8 +796,8 @@ int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi, u64* ca
         if ((w.info & 1u) != (t.b_rc ? 1u : 0u)) return differs("orientation", w.info & 1u, t.b_rc ? 1u : 0u);
         if ((w.info >> 8) != (u32)st) return differs("pre-check status", w.info >> 8, (u64)st);
         if (w.X != (u32)X) return differs("row count", w.X, X);
-        if (!run.carry) {   // the cell the device picked for this call (N by window): the host's own answer for the same window, with the full margin (k_chain_c has one cell: nothing to compare)
-            const bool want_n = st == GAMDP_ST_OK && x.has_n != 0 &&
+        if (!run.carry) {   // the cell the device picked for this call (N by window): the host's own answer for the same window, with the full margin (k_chain_c has one cell: nothing to compare; k_chain2g runs the N-aware cell in every call that runs a DP)
+            const bool want_n = run.generic ? st == GAMDP_ST_OK : st == GAMDP_ST_OK && x.has_n != 0 &&
                                 (run.n_by_contig || run.ms->window_has_n(t.a_id, false, 0, (int64_t)t.begin_a - (int64_t)run.band - 64, (int64_t)t.begin_a + (int64_t)X - 1 + (int64_t)run.band + 64) ||
                                  run.ss->window_has_n(t.b_id, t.b_rc, 0, (int64_t)t.begin_b - 64, (int64_t)t.begin_b + (int64_t)X - 1 + 64));
             if (((w.info >> 1) & 1u) != (want_n ? 1u : 0u)) return differs("choice of the N-aware cell", (w.info >> 1) & 1u, want_n ? 1u : 0u);
@@ -1217,6 +1229,13 @@ extern "C" int gamdp_ctx_set_l1_chain(gamdp_ctx* ctx, int mode)
 {
     if ((mode != GAMDP_L1_CHAIN_WALK && mode != GAMDP_L1_CHAIN_CARRY) || !ctx) return GAMDP_EINVAL;
     reinterpret_cast<Ctx*>(ctx)->l1_chain = mode;
+    return 0;
+}
+
+extern "C" int gamdp_ctx_set_l1_walk_bands(gamdp_ctx* ctx, int which)
+{
+    if ((which != GAMDP_L1_WALK_BAND_150 && which != GAMDP_L1_WALK_ANY_BAND) || !ctx) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->walk_bands = which;
     return 0;
 }
 

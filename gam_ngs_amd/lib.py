@@ -24,13 +24,14 @@ SYMBOLS = [
     "gamdp_no_blocks_contigs", "gamdp_no_blocks_after_filter", "gamdp_pctgs_not_merged", "gamdp_fasta_write_selected",
     "gamdp_find_hits_batch", "gamdp_ctx_set_l1_hits", "gamdp_ctx_l1_hits_stats",
     "gamdp_ctx_l1_tail_calls", "gamdp_score_batch", "gamdp_ctx_score_info", "gamdp_carry_batch", "gamdp_ctx_carry_info",
-    "gamdp_ctx_set_l1_chain", "gamdp_ctx_l1_chain_stats",
+    "gamdp_ctx_set_l1_chain", "gamdp_ctx_l1_chain_stats", "gamdp_ctx_set_l1_walk_bands",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
 ST_OK, ST_EMPTY, ST_OUT_OF_RANGE, ST_INVALID = 0, 1, 2, 3
 L1_HITS_HOST, L1_HITS_DEVICE = 0, 1   # gamdp_ctx_set_l1_hits
 L1_CHAIN_WALK, L1_CHAIN_CARRY = 0, 1   # gamdp_ctx_set_l1_chain
+L1_WALK_BAND_150, L1_WALK_ANY_BAND = 0, 1   # gamdp_ctx_set_l1_walk_bands
 ST_DIAG_RANGE = 9   # diagnostics build only: a packed-f16 block left the exact range (never expected)
 
 
@@ -239,6 +240,8 @@ def load_library():
     lib.gamdp_ctx_set_l1_hits.restype = C.c_int
     lib.gamdp_ctx_set_l1_chain.argtypes = [vp, C.c_int]
     lib.gamdp_ctx_set_l1_chain.restype = C.c_int
+    lib.gamdp_ctx_set_l1_walk_bands.argtypes = [vp, C.c_int]
+    lib.gamdp_ctx_set_l1_walk_bands.restype = C.c_int
     lib.gamdp_ctx_l1_chain_stats.argtypes = [vp, C.POINTER(L1ChainStats)]
     lib.gamdp_ctx_l1_chain_stats.restype = C.c_int
     lib.gamdp_ctx_l1_hits_stats.argtypes = [vp, C.POINTER(L1HitsStats)]

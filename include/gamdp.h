@@ -359,10 +359,18 @@ int gamdp_ctx_l1_tail_calls(const gamdp_ctx* ctx, gamdp_l1_tail_call* out, size_
  * orientation retry of findBestAlignment, :1420-1509): one launch takes every merge block without an empty slave frame through its
  * whole chain, and the host replays its own state machine over the records the chains leave (a difference is GAMDP_EHIP, never a
  * wrong answer).
- * WALK: k_chain2, a workgroup of three wavefronts per merge block (one fills, two walk), the long chains with a twin workgroup for
- *   the other orientation.  Band 150 only, and only while three scratch slots per merge block, sized for its longest slave frame,
- *   fit half of the arena (gamdp_ctx_set_arena_bytes): what does not fit goes in pieces, without twins, or through the round loop
- *   (one launch and one host round trip per link of every chain), which is also what every other band takes.
+ * WALK: a workgroup of three wavefronts per merge block (one fills, two walk), the long chains with a twin workgroup for the other
+ *   orientation, three scratch slots per merge block, sized for its longest slave frame, out of half of the arena
+ *   (gamdp_ctx_set_arena_bytes): what does not fit at once goes in pieces, without twins, or -- a frame too long for the arena --
+ *   through the round loop (one launch and one host round trip per link of every chain).  Which bands have such a kernel is the
+ *   context's gamdp_ctx_set_l1_walk_bands property:
+ *     GAMDP_L1_WALK_BAND_150 (the default): band 150 only, k_chain2 (the 5-column band-150 cell, N-aware by the window of each call);
+ *       every other band takes the round loop.
+ *     GAMDP_L1_WALK_ANY_BAND: band 150 takes k_chain2 unchanged; every other band up to GAMDP_MAX_TUNED_BAND takes k_chain2g<C>, the
+ *       same workgroup around the generic cell with C = 2, 3, 5, 9, 17 columns per lane by band (what gamdp_align_batch runs at
+ *       that band; C >= 9 fills without directions and re-creates them along the path).  Every call of such a chain runs the
+ *       N-aware cell.  gamdp_l1_chain_stats then reports mode = WALK, kernel = "k_chain2g<C>", cols = C, and scratch_bytes, twins
+ *       and launches as for k_chain2.  Wider bands keep the round loop.
  * CARRY: k_chain_c<C>, one wavefront per merge block on gamdp_carry_batch's cell: the last match a chain's next call starts from
  *   is in the end cell's summary when the fill ends, so there is no walk, no scratch slot (the arena does not matter), no twin, and
  *   any band up to GAMDP_MAX_TUNED_BAND runs its chains on the device (C = 2, 3, 5, 9, 17 columns per lane by band, as
@@ -370,10 +378,14 @@ int gamdp_ctx_l1_tail_calls(const gamdp_ctx* ctx, gamdp_l1_tail_call* out, size_
  * In either mode merge blocks with an empty slave frame, the tail alignments and everything under GAMDP_L1_ROUNDS=1 take the round
  * loop.  Results, n_dp, cells and the audit trail do not depend on the mode; gamdp_l1_stats and gamdp_l1_hits_stats keep their
  * layout and meaning.  A property of the context (gamdp_multi_align_merge_blocks honours what each gamdp_multi_ctx(m, i) was set
- * to); GAMDP_L1_CHAIN_CARRY=1 in the environment (read once per process) makes CARRY the mode of new contexts. */
-#define GAMDP_L1_CHAIN_WALK  0   /* default: k_chain2 (band 150, scratch slots from the arena) */
+ * to); GAMDP_L1_CHAIN_CARRY=1 in the environment (read once per process) makes CARRY the mode of new contexts,
+ * GAMDP_L1_WALK_ANY_BAND=1 makes GAMDP_L1_WALK_ANY_BAND their walk-bands property.  CARRY mode ignores that property. */
+#define GAMDP_L1_CHAIN_WALK  0   /* default: k_chain2 / k_chain2g<C> (scratch slots from the arena; bands: gamdp_ctx_set_l1_walk_bands) */
 #define GAMDP_L1_CHAIN_CARRY 1   /* k_chain_c<C>: any band <= GAMDP_MAX_TUNED_BAND, no scratch */
 int gamdp_ctx_set_l1_chain(gamdp_ctx* ctx, int mode);     /* GAMDP_EINVAL for NULL / unknown mode (mode checked first) */
+#define GAMDP_L1_WALK_BAND_150 0   /* default: WALK has a chain kernel at band 150 only */
+#define GAMDP_L1_WALK_ANY_BAND 1   /* WALK: k_chain2 at 150, k_chain2g<C> at every other band <= GAMDP_MAX_TUNED_BAND */
+int gamdp_ctx_set_l1_walk_bands(gamdp_ctx* ctx, int which);   /* GAMDP_EINVAL for NULL / unknown value (value checked first) */
 /* The chain launch of the last gamdp_align_merge_blocks on this context, in either mode. */
 typedef struct gamdp_l1_chain_stats {
     uint64_t chains;          /* merge blocks whose main chain a chain launch ran and whose records the replay used */
@@ -383,8 +395,8 @@ typedef struct gamdp_l1_chain_stats {
     uint32_t mode;            /* GAMDP_L1_CHAIN_* the call ran in */
     uint32_t launches;        /* kernel launches of the chains (WALK: one per piece); part of gamdp_l1_stats.launches as ONE */
     uint32_t twins;           /* twin workgroups (WALK only) */
-    uint32_t cols;            /* band columns per lane of the instantiation (WALK: 5); 0 when there was no launch */
-    char kernel[24];          /* e.g. "k_chain_c<5>" or "k_chain2<true>"; "" when there was no launch */
+    uint32_t cols;            /* band columns per lane of the instantiation (k_chain2: 5); 0 when there was no launch */
+    char kernel[24];          /* e.g. "k_chain_c<5>", "k_chain2<true>" or "k_chain2g<9>"; "" when there was no launch */
     double chain_ms;          /* HIP events around the launches */
 } gamdp_l1_chain_stats;       /* 80 bytes */
 int gamdp_ctx_l1_chain_stats(const gamdp_ctx* ctx, gamdp_l1_chain_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""A/B of the merge-block driver's chain mode (gamdp_ctx_set_l1_chain): gamdp_align_merge_blocks on the GAGE-shaped workloads of
-tests/_gage.py (2.9 Mb and 30 Mb genomes) with the main chains on k_chain2 (WALK) and on k_chain_c (CARRY).  At band 150 that is
-kernel against kernel; at any other band WALK means the round loop (one launch and one host round trip per link of every chain), so
-bands 100 and 300 compare the round loop with a chain launch.  The two modes alternate in ONE process, on one context and the same
-resident sequence sets; per mode the median and the min-max over the repeats of wall_ms, gpu_busy_ms, rounds, launches
-(gamdp_ctx_l1_stats) and chain_ms (gamdp_ctx_l1_chain_stats).  The outputs of the two modes (gamdp_mb_out and the audit arrays)
-must be identical byte for byte.
+"""A/B of the merge-block driver's chain modes (gamdp_ctx_set_l1_chain, gamdp_ctx_set_l1_walk_bands): gamdp_align_merge_blocks on the
+GAGE-shaped workloads of tests/_gage.py (2.9 Mb and 30 Mb genomes) with the main chains in three modes: "walk" (WALK, a chain kernel
+at band 150 only: the default), "carry" (CARRY: k_chain_c) and "walk-any" (WALK with GAMDP_L1_WALK_ANY_BAND: k_chain2 at band 150,
+k_chain2g<C> elsewhere).  At band 150 that is kernel against kernel (walk and walk-any are the same launch); at any other band "walk"
+means the round loop (one launch and one host round trip per link of every chain), so bands 100 and 300 compare the round loop
+with the two chain launches.  The three modes alternate in ONE process, on one context and the same resident sequence sets; per
+mode the median and the min-max over the repeats of wall_ms, gpu_busy_ms, rounds, launches (gamdp_ctx_l1_stats) and chain_ms
+(gamdp_ctx_l1_chain_stats).  The outputs of the three modes (gamdp_mb_out and the audit arrays) must be identical byte for byte.
 
     python tools/l1_chain_ab.py [--genomes 2900000,30000000] [--bands 150,100,300] [--repeats 7] [--json]
 """
@@ -35,7 +36,8 @@ def run(ctx, genome, bands, repeats, seed=1):
     slaves = gam.SequenceSet(ctx, [bytes(c["seq"]) for c in pb["slave"]], ascii=False)
     ins, keep = bench_l1.marshal(flat)
     n = len(flat)
-    modes = (("walk", L.L1_CHAIN_WALK), ("carry", L.L1_CHAIN_CARRY))
+    modes = (("walk", (L.L1_CHAIN_WALK, L.L1_WALK_BAND_150)), ("carry", (L.L1_CHAIN_CARRY, L.L1_WALK_BAND_150)),
+             ("walk-any", (L.L1_CHAIN_WALK, L.L1_WALK_ANY_BAND)))
     recs = []
     st = L.L1Stats()
     for band in bands:
@@ -43,8 +45,9 @@ def run(ctx, genome, bands, repeats, seed=1):
         last = {}
         first = None
         for rep in range(repeats + 1):   # (the first pass of each mode warms buffers and reverse complements up: not counted)
-            for name, mode in modes:
+            for name, (mode, walk_bands) in modes:
                 ctx.set_l1_chain(mode)
+                ctx.set_l1_walk_bands(walk_bands)
                 outs, aud = (L.MbOut * n)(), (L.Result * (n * AUDIT))()
                 rc = ctx.lib.gamdp_align_merge_blocks(ctx.handle, masters.handle, slaves.handle, ins, n, band, outs, aud, AUDIT)
                 if rc != 0:
@@ -70,6 +73,7 @@ def run(ctx, genome, bands, repeats, seed=1):
                 r[k] = last[name][k]
         recs.append(rec)
     ctx.set_l1_chain(L.L1_CHAIN_WALK)
+    ctx.set_l1_walk_bands(L.L1_WALK_BAND_150)
     masters.close()
     slaves.close()
     return recs
@@ -93,9 +97,9 @@ if __name__ == "__main__":
                 continue
             print("%.1f Mb genome, band %d, %d merge blocks, median (min-max) of %d calls per mode (outputs identical):" % (
                 rec["genome"] / 1e6, rec["band"], rec["merge_blocks"], rec["repeats"]))
-            print("  %-6s %-16s %7s %26s %26s %24s %7s %9s" % ("chains", "kernel", "chains", "wall_ms", "gpu_busy_ms", "chain_ms", "rounds", "launches"))
-            for name in ("walk", "carry"):
+            print("  %-8s %-16s %7s %26s %26s %24s %7s %9s" % ("chains", "kernel", "chains", "wall_ms", "gpu_busy_ms", "chain_ms", "rounds", "launches"))
+            for name in ("walk", "carry", "walk-any"):
                 r = rec[name]
                 span = lambda k: "%8.2f (%.2f-%.2f)" % (r[k], r[k + "_min"], r[k + "_max"])
-                print("  %-6s %-16s %7d %26s %26s %24s %7d %9d" % (name, r["kernel"] or "(round loop)", r["chains"], span("wall_ms"), span("gpu_busy_ms"),
+                print("  %-8s %-16s %7d %26s %26s %24s %7d %9d" % (name, r["kernel"] or "(round loop)", r["chains"], span("wall_ms"), span("gpu_busy_ms"),
                                                                   span("chain_ms"), r["rounds"], r["launches"]), flush=True)
