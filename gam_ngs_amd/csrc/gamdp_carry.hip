@@ -56,42 +56,15 @@ __global__ __launch_bounds__(64, C <= 3 ? 5 : C == 5 ? 4 : C == 9 ? 2 : 1) void 
     }
 }
 
-template <class F>
-auto with_carry_kernel(const int cols, F&& f)
-{
-    switch (cols) {
-    case 2: return f(k_carry<2>);
-    case 3: return f(k_carry<3>);
-    case 5: return f(k_carry<5>);
-    case 9: return f(k_carry<9>);
-    default: return f(k_carry<17>);
-    }
-}
-
 }  // namespace
 
-const char* carry_kernel_name(const int cols)
+const KernelFamily& carry_family()
 {
-    switch (cols) {
-    case 2: return "k_carry<2>";
-    case 3: return "k_carry<3>";
-    case 5: return "k_carry<5>";
-    case 9: return "k_carry<9>";
-    default: return "k_carry<17>";
-    }
-}
-
-int carry_waves_per_cu(const int cols)
-{
-    int n = 0;
-    const hipError_t e = with_carry_kernel(cols, [&](auto k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 64, 0); });
-    return (e == hipSuccess && n > 0) ? n : 4;
-}
-
-int launch_carry(const int cols, const CarryParams& p, const unsigned n_wavefronts, void* stream)
-{
-    with_carry_kernel(cols, [&](auto k) { hipLaunchKernelGGL(k, dim3(n_wavefronts), dim3(64), 0, (hipStream_t)stream, p); return 0; });
-    return (int)hipGetLastError();
+    static const KernelFamily f = {
+        {(const void*)k_carry<2>, (const void*)k_carry<3>, (const void*)k_carry<5>, (const void*)k_carry<9>, (const void*)k_carry<17>},
+        {"k_carry<2>", "k_carry<3>", "k_carry<5>", "k_carry<9>", "k_carry<17>"},
+        64};
+    return f;
 }
 
 }  // namespace gamdp

@@ -4,7 +4,7 @@
 // GAMDP_L1_NO_TWINS=1).  The next call of a chain needs one thing of this one: its last match (:1660-1667), and carry_task has it in
 // the end cell's summary the moment the fill ends.  So there is no walker, no mailbox, no scratch slot, no LDS and no wait loop; the
 // only traffic with anyone else is the hand-over to the host at the end.  Any band up to GAMDP_MAX_TUNED_BAND (the instantiations
-// of k_carry: C = score_cols(band)); N is always handled (ChainWin::info bit 1 is 0: there is no choice of cell to report).
+// of k_carry: C = band_cols(band)); N is always handled (ChainWin::info bit 1 is 0: there is no choice of cell to report).
 //
 // Everything but the DP is wave-uniform integer arithmetic that restates gamdp_l1.cpp's Machine for the MAIN phase, written here
 // anew: this file shares the structures of gamdp_dev.h (DevMB, DevBlk, ChainOut, ChainWin, ChainParams, preflight_hd) with k_chain2
@@ -152,35 +152,15 @@ __global__ __launch_bounds__(64, C <= 3 ? 5 : C == 5 ? 4 : C == 9 ? 2 : 1) void 
     if (lane == 0) __hip_atomic_store(cp.host_done + mi, cp.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <class F>
-auto with_chain_kernel(const int cols, F&& f)
-{
-    switch (cols) {
-    case 2: return f(k_chain_c<2>);
-    case 3: return f(k_chain_c<3>);
-    case 5: return f(k_chain_c<5>);
-    case 9: return f(k_chain_c<9>);
-    default: return f(k_chain_c<17>);
-    }
-}
-
 }  // namespace
 
-const char* chain_carry_kernel_name(const int cols)
+const KernelFamily& chain_carry_family()
 {
-    switch (cols) {
-    case 2: return "k_chain_c<2>";
-    case 3: return "k_chain_c<3>";
-    case 5: return "k_chain_c<5>";
-    case 9: return "k_chain_c<9>";
-    default: return "k_chain_c<17>";
-    }
-}
-
-int launch_chain_carry(const int cols, const ChainParams& p, const unsigned n_workgroups, void* stream)
-{
-    with_chain_kernel(cols, [&](auto k) { hipLaunchKernelGGL(k, dim3(n_workgroups), dim3(64), 0, (hipStream_t)stream, p); return 0; });
-    return (int)hipGetLastError();
+    static const KernelFamily f = {
+        {(const void*)k_chain_c<2>, (const void*)k_chain_c<3>, (const void*)k_chain_c<5>, (const void*)k_chain_c<9>, (const void*)k_chain_c<17>},
+        {"k_chain_c<2>", "k_chain_c<3>", "k_chain_c<5>", "k_chain_c<9>", "k_chain_c<17>"},
+        64};
+    return f;
 }
 
 }  // namespace gamdp

@@ -1,5 +1,8 @@
-// Structures shared between the host side of libgamdp (gamdp_host.cpp) and the gfx950 kernels
-// (gamdp_kernel.hip).  Internal -- the public boundary is include/gamdp.h.
+// What the host side of libgamdp (gamdp_host.cpp, gamdp_l1.cpp) and the gfx950 kernels (the .hip files) share: the structures a
+// launch passes, and the rules both sides must agree on, each written once -- the band's column count (band_cols), the layout of
+// a scratch slot (dir_words_for, slot_geom), the rows that describe a kernel (KernelInfo), a family of kernels by column count
+// (KernelFamily) and a chain kernel (ChainKernel).  No HIP header: the plain functions here are tested with g++
+// (tests/native/slot_geom_test.cpp).  Internal -- the public boundary is include/gamdp.h.
 #pragma once
 #include <stdint.h>
 
@@ -122,6 +125,23 @@ enum KernelId : int {
     K_WIDE,          // any band beyond that (gamdp_wide.hip): a workgroup per task, the band matrix as int32 in the scratch slot, no throughput target
     K_COUNT
 };
+
+// The band columns per lane of the kernels that take any band up to 543 (k_align<C,-1,true>, k_score, k_carry, k_chain_c, k_chain2g):
+// the smallest C of 2, 3, 5, 9, 17 with 2*band+1 <= 64*C.  A wider band still says 17: every caller has its own guard against one.
+constexpr int FAMILY_COLS[5] = {2, 3, 5, 9, 17};
+constexpr int band_cols(const u32 band)
+{
+    for (int k = 0; k < 4; k++) if (2 * (u64)band + 1 <= 64u * (u64)FAMILY_COLS[k]) return FAMILY_COLS[k];
+    return 17;
+}
+constexpr int cols_index(const int cols)   // the place of a column count in FAMILY_COLS (anything else: 17's)
+{
+    for (int k = 0; k < 4; k++) if (FAMILY_COLS[k] == cols) return k;
+    return 4;
+}
+static_assert(K_GEN_C3 == K_GEN_C2 + 1 && K_GEN_C5 == K_GEN_C2 + 2 && K_GEN_C9 == K_GEN_C2 + 3 && K_GEN_C17 == K_GEN_C2 + 4,
+              "K_GEN_C2 .. K_GEN_C17: contiguous, in the order of FAMILY_COLS");
+constexpr int gen_kernel_id(const int cols) { return (int)K_GEN_C2 + cols_index(cols); }
 
 // ---- the pre-checks of find_alignment on plain numbers (banded_smith_waterman.cc:90-132), shared by the host (every call is
 // validated and sized before it is launched) and the merge-block chain kernel (which derives the next call of a chain on
@@ -276,14 +296,7 @@ struct ChainParams {
     int32_t n_margin;              // bases added on either side of a call's window when it is tested for N (64; the diagnostics build can shrink it below zero: GAMDP_DIAG_N_WINDOW_SHRINK, the replay must notice)
     u32 n_by_contig;               // 1: every call of a chain whose contigs hold N runs the N-aware cells (diagnostics build: GAMDP_DIAG_FORCE_N)
 };
-int launch_chain(const ChainParams& p, bool has_n, unsigned n_workgroups, void* stream);   // returns hipError_t as int
-int chain_slots_per_workgroup();   // scratch slots a k_chain2 workgroup goes round (1 + its walker wavefronts)
-// k_chain2g<cols>: k_chain2's workgroup around the generic N-aware cell (any band up to 543, cols = score_cols(band)).  Same records,
-// twins and hand-over; every call that runs a DP runs the N-aware cell (ChainWin::info bit 1 set).  The slots of a DevMB are laid out
-// for kernel_info[chain_gen_kernel_id(cols)], the K_GEN_* row whose fill and walk the kernel runs.
-int chain_gen_kernel_id(int cols);
-const char* chain_gen_kernel_name(int cols);   // e.g. "k_chain2g<9>"
-int launch_chain_gen(int cols, const ChainParams& p, unsigned n_workgroups, void* stream);   // returns hipError_t as int
+int chain_slots_per_workgroup();   // scratch slots a k_chain2 / k_chain2g workgroup goes round (1 + its walker wavefronts)
 
 // What the host needs to know of a kernel variant: one row per KernelId (kernel_info, gamdp_kernel.hip, next to the layout
 // constants the rows are built from).
@@ -304,6 +317,79 @@ struct KernelInfo {
 };
 extern const KernelInfo kernel_info[K_COUNT];
 
+// ---- the layout of a scratch slot: the one statement of it.  The launch planner (Ctx::align_plan) sizes the slots of a batch
+// launch with it and the merge-block driver (plan_slots, gamdp_l1.cpp) the slots of a chain kernel, which runs the fill and the walk
+// of a one-task kernel inside them.
+// Words of a task's direction image in a slot of kernel `ki` (K_WIDE: the band matrix itself).  The multi-task kernels keep three
+// blocks more: the packed range of a wavefront ends behind its longest task, rounded up to a group, and a strip of the last group
+// writes the direction words of the whole group (run_octo, run_pair)
+inline u64 dir_words_for(const KernelInfo& ki, const u64 X, const u64 band)
+{
+    const u64 Y = 2 * band + 1;
+    if (ki.id == K_WIDE) return X * Y;
+    const u64 C = (u64)ki.cols, LE = (Y - 1) / C;
+    const u64 extra = ki.tasks_per_wave > 1 ? 3 : 0;
+    return ((X - 1 + LE) / 16 + 1 + extra) * (u64)ki.dir_block_words;
+}
+// A slot of kernel `ki` with room for a direction image of max_dir_words and a band of max_band, in u32 words:
+//   direction words (dir_words each; two images for the pairs of tasks / of quads) | four side buffers of ypad words per task of the
+//   wavefront | the live-row store | the boundary store
+// The last two only where the fast blocks can run without directions (the multi-task kernels and the dirfree rows): per 4 blocks one
+// live row, per block the boundary words (gamdp_kernel.hip, do_block_df); ckpt_off = bnd_off = 0 otherwise (LaunchParams).
+struct SlotGeom { u64 dir_words; u32 ypad; u64 slot_words, ckpt_off, bnd_off; };
+inline SlotGeom slot_geom(const KernelInfo& ki, const u64 max_dir_words, const u32 max_band)
+{
+    SlotGeom g;
+    g.ypad = ((2 * max_band + 2 + 63) / 64) * 64;
+    g.dir_words = ((max_dir_words + 63) / 64) * 64;
+    const u64 tpw = (u64)ki.tasks_per_wave;
+    u64 ckpt_words = 0, bnd_words = 0;
+    if (tpw > 1 || ki.dirfree) {
+        const u64 nblk = g.dir_words / (u64)ki.dir_block_words + 1;
+        ckpt_words = (nblk / 4 + 2) * (u64)ki.ckpt_words;
+        bnd_words = (nblk + 4) * (u64)ki.bnd_words;
+    }
+    const u64 sides_end = (ki.two_dir_images ? 2 * g.dir_words : g.dir_words) + 4ull * g.ypad * tpw;
+    g.slot_words = sides_end + ckpt_words + bnd_words;
+    g.ckpt_off = ckpt_words ? sides_end : 0;
+    g.bnd_off = g.ckpt_off + ckpt_words;
+    return g;
+}
+
+// ---- a family of kernels by band columns per lane: one instantiation per entry of FAMILY_COLS.  One constant row per family, next
+// to its kernels (inside a host function: a table of the host, not a variable of the device code); the host launches a member with
+// launch_kernel and asks its occupancy with family_waves_per_cu (gamdp_internal.h).
+struct KernelFamily {
+    const void* kernel[5];   // in the order of FAMILY_COLS
+    const char* name[5];     // as rocprofv3 prints them, e.g. "k_score<5>"
+    unsigned threads;        // per workgroup
+};
+const KernelFamily& score_family();         // k_score<C>    (gamdp_score.hip)
+const KernelFamily& carry_family();         // k_carry<C>    (gamdp_carry.hip)
+const KernelFamily& chain_carry_family();   // k_chain_c<C>  (gamdp_chain_carry.hip)
+const KernelFamily& chain_gen_family();     // k_chain2g<C>  (gamdp_kernel.hip)
+
+// ---- the kernel of a chain launch, as the merge-block driver reads it (gamdp_l1.cpp: pick_chain_kernel)
+enum ChainNBit : int {      // what ChainWin::info bit 1 says
+    CHAIN_N_UNREPORTED,     // nothing: the kernel has one cell (k_chain_c)
+    CHAIN_N_BY_WINDOW,      // the call ran the N-aware cell because its window may hold an N (k_chain2)
+    CHAIN_N_EVERY_DP        // set for every call that ran a DP (k_chain2g)
+};
+struct ChainKernel {
+    const char* name;         // gamdp_l1_chain_stats::kernel
+    const void* kernel;       // nullptr: no chain kernel, the round loop takes the call
+    int cols;                 // band columns per lane
+    unsigned threads;         // per workgroup
+    const KernelInfo* slots;  // the one-task kernel whose fill and walk it runs in its scratch slots; nullptr: no slots, no scratch
+    bool twins;               // takes twin workgroups (ChainSync)
+    ChainNBit n_bit;
+};
+const ChainKernel& chain2_kernel(bool has_n);   // k_chain2<true>: a launch that holds a contig with N; k_chain2<false>: none does (gamdp_kernel.hip)
+inline ChainKernel family_chain_kernel(const KernelFamily& f, const int cols, const KernelInfo* slots, const bool twins, const ChainNBit n_bit)
+{
+    return ChainKernel{f.name[cols_index(cols)], f.kernel[cols_index(cols)], cols, f.threads, slots, twins, n_bit};
+}
+
 // launches on `stream`; returns hipError_t as int
 int launch_align(int kid, const LaunchParams& p, unsigned n_slots, unsigned dyn_lds, void* stream);
 int launch_wide(const LaunchParams& p, unsigned n_slots, void* stream);   // K_WIDE (gamdp_wide.hip): n_slots workgroups
@@ -321,10 +407,7 @@ struct ScoreParams {
     u32* cursor;            // work-queue head (zeroed before the launch)
     ScoreRec* results;      // indexed by DevTask::res_idx
 };
-int score_cols(u32 band);                    // band columns per lane of the instantiation a band takes: the smallest of 2, 3, 5, 9, 17 with 2*band+1 <= 64*C
-const char* score_kernel_name(int cols);     // as rocprofv3 prints it, e.g. "k_score<5>"
-int score_waves_per_cu(int cols);            // resident wavefronts per CU, from the occupancy the runtime reports
-int launch_score(int cols, const ScoreParams& p, unsigned n_wavefronts, void* stream);   // returns hipError_t as int
+// (score_family(): the instantiation a band takes is band_cols(band); a grid of wavefronts)
 
 // ---- the whole result from a fill alone (k_carry, gamdp_carry.hip; gamdp_carry_batch) -----------------------------------
 // A wavefront leaves a task's DevResult; bits 16.. of its flags hold the band columns per lane of the instantiation that ran.
@@ -335,17 +418,17 @@ struct CarryParams {
     DevResult* results;     // indexed by DevTask::res_idx
 };
 constexpr u32 CARRY_COLS_SHIFT = 16;
-const char* carry_kernel_name(int cols);     // e.g. "k_carry<5>"; the instantiation a band takes is score_cols(band)
-int carry_waves_per_cu(int cols);            // resident wavefronts per CU, from the occupancy the runtime reports
-int launch_carry(int cols, const CarryParams& p, unsigned n_wavefronts, void* stream);   // returns hipError_t as int
+// (carry_family(): the instantiation a band takes is band_cols(band); a grid of wavefronts)
 
 // ---- the main chain of a merge block on carry_task (k_chain_c, gamdp_chain_carry.hip; GAMDP_L1_CHAIN_CARRY) ---------------------
 // One wavefront (a workgroup of 64) per merge block, both orientation attempts one after the other; any band up to 543, the
-// instantiation a band takes is score_cols(band).  The grid is one workgroup per merge block of the launch, in the list's order:
+// instantiation a band takes is band_cols(band) of chain_carry_family.  The grid is one workgroup per merge block of the launch, in the list's order:
 // workgroup g takes merge block first_mb + g.  Same records at the same indices and the same hand-over as k_chain2 (ChainOut,
 // ChainWin, the pinned mirror, host_done); ChainWin::info bit 1 is 0 and state 3 does not occur.  Not read: scratch, ypad, sync,
 // n_twins, cursor, max_rows, n_margin, n_by_contig, and of a DevMB rows, has_n, npre_*, max_x and the slot fields.
-const char* chain_carry_kernel_name(int cols);   // e.g. "k_chain_c<5>"
-int launch_chain_carry(int cols, const ChainParams& p, unsigned n_workgroups, void* stream);   // returns hipError_t as int
+//
+// k_chain2g<C> (chain_gen_family, gamdp_kernel.hip): k_chain2's workgroup around the generic N-aware cell (any band up to 543, C =
+// band_cols(band)).  Same records, twins and hand-over; every call that runs a DP runs the N-aware cell (ChainWin::info bit 1 set).
+// The slots of a DevMB are laid out for kernel_info[gen_kernel_id(C)], the K_GEN_* row whose fill and walk the kernel runs.
 
 }  // namespace gamdp

@@ -372,30 +372,13 @@ void Ctx::trim_scratch()
 
 // ---- task validation (same order as banded_smith_waterman.cc:90-132) -------------------------------
 
-// words of a task's direction image in a slot of kernel `kid` (K_WIDE: the band matrix itself).  The multi-task kernels keep
-// three blocks more: the packed range of a wavefront ends behind its longest task, rounded up to a group, and a strip of the last group
-// writes the direction words of the whole group (run_octo, run_pair)
-static u64 dir_words_for(int kid, u64 X, u64 band)
-{
-    const u64 Y = 2 * band + 1;
-    if (kid == K_WIDE) return X * Y;
-    const KernelInfo& ki = kernel_info[kid];
-    const u64 C = (u64)ki.cols, LE = (Y - 1) / C;
-    const u64 extra = ki.tasks_per_wave > 1 ? 3 : 0;
-    return ((X - 1 + LE) / 16 + 1 + extra) * (u64)ki.dir_block_words;
-}
-
+static_assert(2 * GAMDP_MAX_TUNED_BAND + 1 <= 64 * 17 && 2 * (GAMDP_MAX_TUNED_BAND + 1) + 1 > 64 * 17, "GAMDP_MAX_TUNED_BAND: the widest band of 17 columns per lane");
 static int pick_kernel(int band, bool has_n)
 {
     if (band == 512) return has_n ? K_C17_CE4_N : K_C17_CE4;
     if (band == 150) return has_n ? K_C5_CE0_N : K_C5_CE0;
-    const int Y = 2 * band + 1;
-    if (Y <= 2 * 64) return K_GEN_C2;
-    if (Y <= 3 * 64) return K_GEN_C3;
-    if (Y <= 5 * 64) return K_GEN_C5;
-    if (Y <= 9 * 64) return K_GEN_C9;
-    if (Y <= 17 * 64) return K_GEN_C17;
-    return K_WIDE;   // band > 543: gamdp_wide.hip
+    if (band > GAMDP_MAX_TUNED_BAND) return K_WIDE;   // gamdp_wide.hip
+    return gen_kernel_id(band_cols((u32)band));
 }
 
 // fn(lo, hi) over [0, n) on the process's host thread pool (gamdp_hostpool.h: HostPool); batches of a few thousand tasks are not worth a thread
@@ -440,7 +423,7 @@ static int prepare_task(const ITask& it, Prepared& pr)
                        it.sa->window_has_n(it.a_id, it.a_rc, it.a_off, (int64_t)it.begin_a - (int64_t)band - margin, (int64_t)it.begin_a + (int64_t)X - 1 + (int64_t)band + margin) ||
                        it.sb->window_has_n(it.b_id, it.b_rc, it.b_off, (int64_t)it.begin_b - margin, (int64_t)it.begin_b + (int64_t)X - 1 + margin);
     pr.kid = pick_kernel((int)band, has_n);
-    pr.dir_words = dir_words_for(pr.kid, X, band);   // (of the kernel picked here: the planner sizes a group that moves to a multi-task kernel by dir_words_for itself)
+    pr.dir_words = dir_words_for(kernel_info[pr.kid], X, band);   // (of the kernel picked here: the planner sizes a group that moves to a multi-task kernel by dir_words_for itself)
     DevTask& d = pr.dt;
     const DevSeq& da = it.a_rc ? it.sa->rc[it.a_id] : it.sa->fwd[it.a_id];
     const DevSeq& db = it.b_rc ? it.sb->rc[it.b_id] : it.sb->fwd[it.b_id];
@@ -741,7 +724,7 @@ int Ctx::align_plan(u64 arena_call)
             work.pop_back();
             u32 maxband = ki.band;
             u64 maxdir = 0;
-            if (ki.band != 0) maxdir = dir_words_for(kid, rowsv[cur[0]], ki.band);   // a one-band kernel: the list is sorted by rows, the longest task first
+            if (ki.band != 0) maxdir = dir_words_for(ki, rowsv[cur[0]], ki.band);   // a one-band kernel: the list is sorted by rows, the longest task first
             else {   // (a reduction over the descriptors in sorted -- i.e. random -- order: in parallel for big launches)
                 std::mutex red;
                 parallel_for(cur.size(), [&](size_t lo, size_t hi) {
@@ -751,25 +734,14 @@ int Ctx::align_plan(u64 arena_call)
                     maxband = std::max(maxband, mb); maxdir = std::max(maxdir, md);
                 });
             }
-            const u32 ypad = ((2 * maxband + 2 + 63) / 64) * 64;
-            const u64 dirw = ((maxdir + 63) / 64) * 64;
-            // the tuned N-free kernels fill their fast blocks without directions and keep, per 4 blocks, one live row
-            // (C*64 words) and, per block, 512 boundary words instead (gamdp_kernel.hip, do_block_df)
-            u64 ckpt_words = 0, bnd_words = 0;
-            const u32 tpw = (u32)ki.tasks_per_wave;  // tasks per wavefront: each has its own side buffers ...
-            if (tpw > 1 || ki.dirfree) {   // (the tuned band-512 kernels, the multi-task kernels, the generic kernels with 9 / 17 columns per lane)
-                const u64 cw = (u64)ki.dir_block_words, nblk = dirw / cw + 1;
-                ckpt_words = (nblk / 4 + 2) * (u64)ki.ckpt_words;
-                bnd_words = (nblk + 4) * (u64)ki.bnd_words;
-            }
-            const u64 dir_total = ki.two_dir_images ? 2 * dirw : dirw;   // ... and, for the pairs (of tasks / of quads), its own direction words
-            const u64 slotw = dir_total + 4ull * ypad * tpw + ckpt_words + bnd_words;
-            const u64 fit = arena_call / (slotw * sizeof(u32));
+            const SlotGeom geom = slot_geom(ki, maxdir, maxband);   // (gamdp_dev.h: the layout of a slot)
+            const u32 tpw = (u32)ki.tasks_per_wave;
+            const u64 fit = arena_call / (geom.slot_words * sizeof(u32));
             if (fit == 0) { set_error("scratch arena too small for one task"); return GAMDP_ENOMEM; }
             const u64 want = std::min<u64>((cur.size() + tpw - 1) / tpw, max_resident);
             if (fit < want && cur.size() > 1) {
                 std::vector<u32> big, small;
-                for (u32 i : cur) ((ki.band ? dir_words_for(kid, rowsv[i], ki.band) : w_prep[i].dir_words) * 2 >= maxdir ? big : small).push_back(i);
+                for (u32 i : cur) ((ki.band ? dir_words_for(ki, rowsv[i], ki.band) : w_prep[i].dir_words) * 2 >= maxdir ? big : small).push_back(i);
                 if (!small.empty()) {
                     work.push_back(std::move(small));
                     work.push_back(std::move(big));  // processed first (largest tasks first)
@@ -779,14 +751,13 @@ int Ctx::align_plan(u64 arena_call)
             Launch L;
             const size_t padded = (cur.size() + tpw - 1) / tpw * tpw;
             L.kid = kid; L.first = (u32)plan.n_host_tasks; L.count = (u32)padded;
-            L.slot_words = slotw; L.dir_words = dirw; L.ypad = ypad; L.band_max = maxband;
+            L.slot_words = geom.slot_words; L.dir_words = geom.dir_words; L.ypad = geom.ypad; L.band_max = maxband;
+            L.ckpt_off = geom.ckpt_off; L.bnd_off = geom.bnd_off;
             // (Measured and dropped: equalising the rounds of a launch -- 6 250 workgroups as 2 x 3 125 instead of 4 096 +
             // 2 154 -- and forcing an even spread over the CUs with unused dynamic LDS changed nothing: the hardware
             // dispatcher already spreads workgroups evenly, and what a short launch loses is per-SIMD occupancy.)
             L.n_slots = (u32)std::min<u64>(want, fit);
             L.dyn_lds = 0;
-            L.ckpt_off = ckpt_words ? dir_total + 4ull * ypad * tpw : 0;
-            L.bnd_off = L.ckpt_off + ckpt_words;
             plan.n_host_tasks += padded;
             plan.items.push_back(std::move(cur));
             plan.launches.push_back(L);
@@ -1100,15 +1071,9 @@ int Ctx::align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_op
 struct ScoreCall {
     typedef ScoreRec Rec;
     typedef gamdp_score_result Out;
+    typedef ScoreParams Params;
     static constexpr const char* api = "gamdp_score_batch";
-    static const char* kernel_name(int cols) { return score_kernel_name(cols); }
-    static int waves_per_cu(int cols) { return score_waves_per_cu(cols); }
-    static int launch(int cols, const DevTask* t, u32 n, u32* cursor, Rec* results, unsigned slots, void* stream)
-    {
-        ScoreParams p;
-        p.tasks = t; p.n_tasks = n; p.cursor = cursor; p.results = results;
-        return launch_score(cols, p, slots, stream);
-    }
+    static const KernelFamily& family() { return score_family(); }
     static u32 cols_of(const Rec& r) { return r.info >> 8; }
     static void collect(const Rec& r, u64 cells, Out& o)
     {
@@ -1122,15 +1087,9 @@ struct ScoreCall {
 struct CarryCall {
     typedef DevResult Rec;
     typedef gamdp_result Out;
+    typedef CarryParams Params;
     static constexpr const char* api = "gamdp_carry_batch";
-    static const char* kernel_name(int cols) { return carry_kernel_name(cols); }
-    static int waves_per_cu(int cols) { return carry_waves_per_cu(cols); }
-    static int launch(int cols, const DevTask* t, u32 n, u32* cursor, Rec* results, unsigned slots, void* stream)
-    {
-        CarryParams p;
-        p.tasks = t; p.n_tasks = n; p.cursor = cursor; p.results = results;
-        return launch_carry(cols, p, slots, stream);
-    }
+    static const KernelFamily& family() { return carry_family(); }
     static u32 cols_of(const Rec& r) { return r.flags >> CARRY_COLS_SHIFT; }
     static void collect(const Rec& r, u64 cells, Out& o) { fill_result(r, cells, o); }   // as align() makes a gamdp_result of a record
 };
@@ -1161,16 +1120,15 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
             out[i].status = (uint8_t)st;
             out[i].cells = w_prep[i].cells;
             w_prep[i].dt.res_idx = (u32)i;
-            colsv[i] = st != GAMDP_ST_OK ? (int8_t)-1 : (int8_t)score_cols((u32)w_prep[i].dt.band);
+            colsv[i] = st != GAMDP_ST_OK ? (int8_t)-1 : (int8_t)band_cols((u32)w_prep[i].dt.band);
             w_rows[i] = st != GAMDP_ST_OK ? 0u : (u32)w_prep[i].dt.X;
         }
     });
     // the launches: the tasks of every column count, longest first, one behind the other in the staged list
-    static const int COLS[] = {2, 3, 5, 9, 17};
     struct SLaunch { int cols; u32 first, count, band_max; };
     std::vector<SLaunch> launches;
     std::vector<u32> order, g;
-    for (const int cols : COLS) {
+    for (const int cols : FAMILY_COLS) {
         g.clear();
         u32 band_max = 0;
         for (size_t i = 0; i < n; i++) if (colsv[i] == cols) { g.push_back((u32)i); band_max = std::max(band_max, (u32)w_prep[i].dt.band); }
@@ -1199,9 +1157,11 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
     std::vector<u32> slots(launches.size());
     for (size_t li = 0; li < launches.size(); li++) {
         const SLaunch& L = launches[li];
-        slots[li] = (u32)std::min<u64>(L.count, (u64)n_cu * (u64)K::waves_per_cu(L.cols));
+        slots[li] = (u32)std::min<u64>(L.count, (u64)n_cu * (u64)family_waves_per_cu(K::family(), L.cols));
         HIPCHK(this, hipEventRecord(events[li].first, stream));
-        const int e = K::launch(L.cols, d_tasks + L.first, L.count, d_cursor + li, d_rec, slots[li], stream);
+        typename K::Params p;
+        p.tasks = d_tasks + L.first; p.n_tasks = L.count; p.cursor = d_cursor + li; p.results = d_rec;
+        const int e = launch_kernel(K::family().kernel[cols_index(L.cols)], K::family().threads, p, slots[li], stream);
         if (e != 0) { set_error(std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)e)); return GAMDP_EHIP; }
         HIPCHK(this, hipEventRecord(events[li].second, stream));
     }
@@ -1219,7 +1179,7 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
         if (hipEventElapsedTime(&ms, events[li].first, events[li].second) == hipSuccess) { kernel_launches++; kernel_ms += ms; }
         gamdp_score_launch_info r;
         std::memset(&r, 0, sizeof(r));
-        std::snprintf(r.kernel, sizeof(r.kernel), "%s", K::kernel_name(L.cols));
+        std::snprintf(r.kernel, sizeof(r.kernel), "%s", K::family().name[cols_index(L.cols)]);
         // the column count as the wavefronts wrote it into their records (0: they do not all say the same)
         r.cols = K::cols_of(h_rec[order[L.first]]);
         for (u32 k = 0; k < L.count; k++) if (K::cols_of(h_rec[order[L.first + k]]) != r.cols) r.cols = 0;

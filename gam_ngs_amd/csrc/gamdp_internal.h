@@ -343,6 +343,23 @@ inline int grow_pinned(Ctx* ctx, uint8_t*& ptr, u64& cap, u64 need, unsigned fla
     return 0;
 }
 
+// Launches a kernel that takes its parameters as one struct, by value: `grid` workgroups of `threads` on `stream`, no dynamic LDS.
+// Returns hipError_t as int.
+template <class P>
+int launch_kernel(const void* kernel, unsigned threads, const P& p, unsigned grid, void* stream)
+{
+    P copy = p;
+    void* args[] = {&copy};
+    return (int)hipLaunchKernel(kernel, dim3(grid), dim3(threads), args, 0, static_cast<hipStream_t>(stream));
+}
+// resident workgroups per CU of a family's instantiation, from the occupancy the runtime reports (4 if it does not say)
+inline int family_waves_per_cu(const KernelFamily& f, int cols)
+{
+    int n = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f.kernel[cols_index(cols)], (int)f.threads, 0);
+    return (e == hipSuccess && n > 0) ? n : 4;
+}
+
 // DevResult record + the cell count of its call -> the C ABI's result (gamdp_host.cpp)
 void fill_result(const DevResult& r, u64 cells, gamdp_result& o);
 

@@ -938,7 +938,7 @@ __global__ __launch_bounds__(64 * (1 + CH_NW), GAMDP_WAVES_PER_SIMD) void k_chai
     chain_workgroup<5, 0, HASN>(cp);
 }
 
-// Any other band up to 543: the same workgroup around the generic cell with C columns per lane (C = score_cols(band): 2, 3, 5, 9, 17).
+// Any other band up to 543: the same workgroup around the generic cell with C columns per lane (C = band_cols(band): 2, 3, 5, 9, 17).
 // C >= 9 fills its fast blocks without directions and the walkers re-create strips on demand (materialise): at LPT = 64, PK = false
 // that code keeps its state in registers and private memory and touches no LDS, so two walkers can be in it at once, for different
 // calls; the rings, the boundary staging and the capture scratch of kernel_common.inc are the filler's alone.
@@ -953,50 +953,20 @@ __global__ __launch_bounds__(64 * (1 + CH_NW), GAMDP_WAVES_PER_SIMD) void k_chai
 
 int chain_slots_per_workgroup() { return CH_NS; }
 
-int launch_chain(const ChainParams& p, bool has_n, unsigned n_slots, void* stream)
+const ChainKernel& chain2_kernel(const bool has_n)
 {
-    ChainParams cp = p;
-    void* args[] = {&cp};
-    const void* f = has_n ? (const void*)k_chain2<true> : (const void*)k_chain2<false>;
-    return (int)hipLaunchKernel(f, dim3(n_slots), dim3(64 * (1 + CH_NW)), args, 0, static_cast<hipStream_t>(stream));
+    static const ChainKernel with_n = {"k_chain2<true>", (const void*)k_chain2<true>, 5, 64 * (1 + CH_NW), &kernel_info[K_C5_CE0_N], true, CHAIN_N_BY_WINDOW};
+    static const ChainKernel without = {"k_chain2<false>", (const void*)k_chain2<false>, 5, 64 * (1 + CH_NW), &kernel_info[K_C5_CE0_N], true, CHAIN_N_BY_WINDOW};
+    return has_n ? with_n : without;
 }
 
-int chain_gen_kernel_id(const int cols)
+const KernelFamily& chain_gen_family()
 {
-    switch (cols) {
-    case 2: return K_GEN_C2;
-    case 3: return K_GEN_C3;
-    case 5: return K_GEN_C5;
-    case 9: return K_GEN_C9;
-    default: return K_GEN_C17;
-    }
-}
-
-const char* chain_gen_kernel_name(const int cols)
-{
-    switch (cols) {
-    case 2: return "k_chain2g<2>";
-    case 3: return "k_chain2g<3>";
-    case 5: return "k_chain2g<5>";
-    case 9: return "k_chain2g<9>";
-    default: return "k_chain2g<17>";
-    }
-}
-
-int launch_chain_gen(const int cols, const ChainParams& p, unsigned n_slots, void* stream)
-{
-    ChainParams cp = p;
-    void* args[] = {&cp};
-    const void* f = nullptr;
-    switch (cols) {
-    case 2: f = (const void*)k_chain2g<2>; break;
-    case 3: f = (const void*)k_chain2g<3>; break;
-    case 5: f = (const void*)k_chain2g<5>; break;
-    case 9: f = (const void*)k_chain2g<9>; break;
-    case 17: f = (const void*)k_chain2g<17>; break;
-    default: return (int)hipErrorInvalidValue;
-    }
-    return (int)hipLaunchKernel(f, dim3(n_slots), dim3(64 * (1 + CH_NW)), args, 0, static_cast<hipStream_t>(stream));
+    static const KernelFamily f = {
+        {(const void*)k_chain2g<2>, (const void*)k_chain2g<3>, (const void*)k_chain2g<5>, (const void*)k_chain2g<9>, (const void*)k_chain2g<17>},
+        {"k_chain2g<2>", "k_chain2g<3>", "k_chain2g<5>", "k_chain2g<9>", "k_chain2g<17>"},
+        64 * (1 + CH_NW)};
+    return f;
 }
 
 // One row per kernel variant.  Waves per CU: what the kernels are register-budgeted for (K_WIDE: workgroups).  Direction-block

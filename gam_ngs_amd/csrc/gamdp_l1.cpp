@@ -412,11 +412,7 @@ struct ChainRun {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const ChainOut* dout = nullptr;   // device copy of the ChainOut list (progress markers in the diagnostics build)
     bool n_by_contig = false;         // the launch ran every call of a chain with N in its contigs on the N-aware cells
-    // which kernel the launch is (gamdp_l1_chain_stats): k_chain_c<cols> (carry; no choice of cell to compare, no scratch), k_chain2, or
-    // k_chain2g<cols> (generic: every call that runs a DP runs the N-aware cell)
-    bool carry = false, generic = false;
-    int cols = 0;
-    const char* kernel = "";
+    ChainKernel kernel{};             // which kernel the launch is (pick_chain_kernel; gamdp_l1_chain_stats)
     u64 scratch_bytes = 0;
     u32 n_launches = 0, n_twins = 0;
     const SeqSet *ms = nullptr, *ss = nullptr;
@@ -611,9 +607,10 @@ void describe_chains(const std::vector<Machine>& M, const ChainSel& sel, const S
     }
 }
 
-// 5. Slots and pieces.  Every workgroup goes round its own scratch slots (chain_slots_per_workgroup(): k_chain2 has a filling
-//    and two walking wavefronts per merge block), sized for the longest call ITS chain can make (x_size <= its longest slave
-//    frame) -- a call of a 30 Mb genome has a few chains with frames of 100 kb and two thousand with frames of a few kb.  What
+// 5. Slots and pieces.  Every workgroup of a kernel with slots (ChainKernel::slots) goes round its own scratch slots
+//    (chain_slots_per_workgroup(): k_chain2 has a filling and two walking wavefronts per merge block), sized for the longest call
+//    ITS chain can make (x_size <= its longest slave frame) -- a call of a 30 Mb genome has a few chains with frames of 100 kb
+//    and two thousand with frames of a few kb.  What
 //    does not fit the arena at once goes in pieces, one launch after the other over the same memory; twins only when everything
 //    fits at once.  Returns false when a frame is too long for the arena: the round loop peels such calls off by itself.
 struct ChainSlots {
@@ -621,28 +618,32 @@ struct ChainSlots {
     u64 need_scratch = 0, slotw_max = 0, n_tw = 0;   // u32 words; the twins that are left
     u32 ypad = 0;
 };
-// `ki`: the kernel_info row of the one-task kernel whose fill and walk the chain kernel runs (K_C5_CE0_N: k_chain2; K_GEN_C*:
-// k_chain2g<cols>), `cols` its band columns per lane.  Block count, direction, checkpoint and boundary words as Ctx::align sizes a
-// slot of that kernel for a task of the chain's longest frame (gamdp_host.cpp: dir_words_for and the launch planner).
-bool plan_slots(const ChainSel& sel, DevMB* hmb, const KernelInfo& ki, const u64 cols, const u32 band, const u64 arena, ChainSlots& S)
+// `ki`: the kernel_info row of the one-task kernel whose fill and walk the chain kernel runs (ChainKernel::slots).  A chain's slots are
+// that kernel's slots for a task of the chain's longest frame: slot_geom (gamdp_dev.h), which also sizes the slots of a batch launch.
+// nullptr: a kernel without slots -- the slot fields cleared (so that the upload does not carry what an earlier call left there), one
+// piece, no twins, no scratch.
+bool plan_slots(const ChainSel& sel, DevMB* hmb, const KernelInfo* ki, const u32 band, const u64 arena, ChainSlots& S)
 {
     const u64 n_mb = sel.ch.size();
-    const u64 Y = 2ull * band + 1, LE = (Y - 1) / cols;
-    const u32 ypad = S.ypad = (u32)(((2 * band + 2 + 63) / 64) * 64);
-    const bool df = ki.dirfree;   // (the 5-column shapes keep a direction per cell: no checkpoint / boundary stores)
+    if (ki == nullptr) {
+        for (size_t q = 0; q < n_mb; q++) {
+            DevMB& x = hmb[q];
+            x.max_x = 0; x.slot_off[0] = x.slot_off[1] = 0; x.slot_words = x.dir_words = x.ckpt_off = x.bnd_off = 0;
+        }
+        S.pieces.emplace_back(0u, (u32)n_mb);
+        return true;
+    }
     const u64 per_wg = (u64)chain_slots_per_workgroup();
     const u64 arena_words = arena / sizeof(u32);
     S.n_tw = sel.n_tw;
     u64 words_all = 0, words_twins = 0;
     for (size_t q = 0; q < n_mb; q++) {
         DevMB& x = hmb[q];
-        const u64 nblk = ((u64)sel.ch[q].longest - 1 + LE) / 16 + 1;
-        const u64 dirw = ((nblk * (u64)ki.dir_block_words + 63) / 64) * 64;
-        const u64 nblk_df = dirw / (u64)ki.dir_block_words + 1;   // (the planner's count: from the rounded direction words)
-        const u64 ckptw = df ? (nblk_df / 4 + 2) * (u64)ki.ckpt_words : 0, bndw = df ? (nblk_df + 4) * (u64)ki.bnd_words : 0;
+        const SlotGeom g = slot_geom(*ki, dir_words_for(*ki, sel.ch[q].longest, band), band);
+        S.ypad = g.ypad;
         x.max_x = sel.ch[q].longest;
-        x.dir_words = dirw; x.slot_words = dirw + 4ull * ypad + ckptw + bndw;
-        x.ckpt_off = df ? dirw + 4ull * ypad : 0; x.bnd_off = x.ckpt_off + ckptw;
+        x.dir_words = g.dir_words; x.slot_words = g.slot_words;
+        x.ckpt_off = g.ckpt_off; x.bnd_off = g.bnd_off;
         S.slotw_max = std::max(S.slotw_max, x.slot_words);
         words_all += per_wg * x.slot_words;
         if (q < S.n_tw) words_twins += per_wg * x.slot_words;
@@ -668,11 +669,9 @@ bool plan_slots(const ChainSel& sel, DevMB* hmb, const KernelInfo& ki, const u64
     return true;
 }
 
-// 6. Enqueue: the kernel's parameters, what the host keeps of the launch (`run`), upload, the launches, the two events.
-// `carry_cols`: else 0, the instantiation of k_chain_c (one piece, no twins, no scratch); `gen_cols`: else 0, the instantiation of
-// k_chain2g; both 0 = k_chain2.
+// 6. Enqueue: the kernel's parameters, what the host keeps of the launch (`run`), upload, the launches of kernel `ck`, the two events.
 int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const ChainSlots& S, uint8_t* const dm, const u32 band,
-                   const SeqSet* ms, const SeqSet* ss, const int carry_cols, const int gen_cols, ChainRun& run)
+                   const SeqSet* ms, const SeqSet* ss, const ChainKernel& ck, ChainRun& run)
 {
     uint8_t *const h = c->h_chain, *const d = c->d_chain, *const hm = c->h_mirror;
     ChainParams cp;
@@ -689,11 +688,7 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
     // the diagnostics build's GAMDP_DIAG_FORCE_N: by the contigs' flags, as in rounds 3-4
     cp.n_margin = (int32_t)(64 - diag().n_window_shrink); cp.n_by_contig = diag().force_n ? 1u : 0u;
     run.n_by_contig = cp.n_by_contig != 0;
-    const bool walk_n = sel.has_n || diag().force_n;
-    run.carry = carry_cols != 0;
-    run.generic = gen_cols != 0;
-    run.cols = carry_cols ? carry_cols : (gen_cols ? gen_cols : 5);
-    run.kernel = carry_cols ? chain_carry_kernel_name(carry_cols) : (gen_cols ? chain_gen_kernel_name(gen_cols) : (walk_n ? "k_chain2<true>" : "k_chain2<false>"));
+    run.kernel = ck;
     run.scratch_bytes = S.need_scratch * sizeof(u32); run.n_launches = (u32)S.pieces.size(); run.n_twins = (u32)S.n_tw;
     // (the events belong to `run` from here on: every path out leaves them to it)
     if (hipEventCreate(&run.e0) != hipSuccess || hipEventCreate(&run.e1) != hipSuccess) { c->set_error("hipEventCreate failed"); return GAMDP_EHIP; }
@@ -706,9 +701,7 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
     ok = ok && hipEventRecord(run.e0, c->chain_stream) == hipSuccess;
     for (size_t pc = 0; ok && pc < S.pieces.size(); pc++) {   // (one launch unless the arena is too small for all the slots at once)
         cp.first_mb = S.pieces[pc].first;
-        if (carry_cols) ok = launch_chain_carry(carry_cols, cp, (unsigned)S.pieces[pc].second, c->chain_stream) == 0;
-        else if (gen_cols) ok = launch_chain_gen(gen_cols, cp, (unsigned)(S.pieces[pc].second + S.n_tw), c->chain_stream) == 0;
-        else ok = launch_chain(cp, walk_n, (unsigned)(S.pieces[pc].second + S.n_tw), c->chain_stream) == 0;
+        ok = launch_kernel(ck.kernel, ck.threads, cp, (unsigned)(S.pieces[pc].second + S.n_tw), c->chain_stream) == 0;   // (a workgroup per merge block of the piece, the twins' in front)
     }
     ok = ok && hipEventRecord(run.e1, c->chain_stream) == hipSuccess;
     if (!ok) {
@@ -720,20 +713,31 @@ int enqueue_chains(Ctx* c, const ChainSel& sel, const ChainLayout& L, const Chai
     return 0;
 }
 
-// Starts the launch (asynchronous).  `arena` = bytes its scratch slots may take.  Returns 0 (run.launched says whether there is
-// one: not for other bands, GAMDP_L1_ROUNDS=1, no merge block with a chain, or a frame too long for the arena) or an error code.
-// CARRY mode (Ctx::l1_chain): any band the carry kernels take, no slot plan and no scratch, no twins, one launch for all.
+// The chain kernel of a call (kernel == nullptr: none, the round loop takes every merge block).  `has_n`: a contig of the launch holds
+// an N.  `rounds`: GAMDP_L1_ROUNDS=1.
+// CARRY mode (Ctx::l1_chain): k_chain_c at any band the carry kernels take -- no slots, no twins, one cell.
 // WALK mode: band 150 on k_chain2; with Ctx::walk_bands == GAMDP_L1_WALK_ANY_BAND every other band up to GAMDP_MAX_TUNED_BAND on
-// k_chain2g<score_cols(band)>, its slots laid out for the K_GEN_* kernel of that column count.
+// k_chain2g<band_cols(band)>, its slots laid out for the K_GEN_* kernel of that column count.
+ChainKernel pick_chain_kernel(const int l1_chain, const int walk_bands, const u32 band, const bool has_n, const bool rounds)
+{
+    const bool carry = l1_chain == GAMDP_L1_CHAIN_CARRY;
+    const bool generic = !carry && band != 150 && walk_bands == GAMDP_L1_WALK_ANY_BAND;
+    if (rounds || ((carry || generic) ? band > GAMDP_MAX_TUNED_BAND : band != 150)) return ChainKernel{};
+    const int cols = band_cols(band);
+    if (carry) return family_chain_kernel(chain_carry_family(), cols, nullptr, false, CHAIN_N_UNREPORTED);
+    if (generic) return family_chain_kernel(chain_gen_family(), cols, &kernel_info[gen_kernel_id(cols)], true, CHAIN_N_EVERY_DP);
+    return chain2_kernel(has_n);
+}
+
+// Starts the launch (asynchronous).  `arena` = bytes its scratch slots may take.  Returns 0 (run.launched says whether there is
+// one: not when the call has no chain kernel, no merge block has a chain, or a frame is too long for the arena) or an error code.
 int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const SeqSet* ss, const u32 band, const u64 arena, ChainRun& run)
 {
     run.launched = false;
-    const bool carry = c->l1_chain == GAMDP_L1_CHAIN_CARRY;
-    const bool generic = !carry && band != 150 && c->walk_bands == GAMDP_L1_WALK_ANY_BAND;
-    if (tuning().l1_rounds || ((carry || generic) ? band > GAMDP_MAX_TUNED_BAND : band != 150)) return 0;
     ChainSel sel = select_chains(M, ms, ss);
-    if (sel.ch.empty()) return 0;
-    if (carry) sel.n_tw = 0;
+    const ChainKernel ck = pick_chain_kernel(c->l1_chain, c->walk_bands, band, sel.has_n || diag().force_n, tuning().l1_rounds);
+    if (!ck.kernel || sel.ch.empty()) return 0;
+    if (!ck.twins) sel.n_tw = 0;
     int rc_ = ss->ensure_rc(sel.need_rc, c);
     if (rc_) return rc_;
     const ChainLayout L(sel.ch.size(), sel.n_blk, sel.n_tw);
@@ -742,20 +746,11 @@ int launch_main_chains(Ctx* c, std::vector<Machine>& M, const SeqSet* ms, const 
     DevMB* const hmb = (DevMB*)(c->h_chain + L.mb);
     describe_chains(M, sel, ms, ss, hmb, (DevBlk*)(c->h_chain + L.blk), run.q_of);
     ChainSlots slots;
-    if (carry) {
-        // (k_chain_c reads none of the slot fields: zeroed, so that the upload does not carry what an earlier call left there)
-        for (size_t q = 0; q < sel.ch.size(); q++) {
-            DevMB& x = hmb[q];
-            x.max_x = 0; x.slot_off[0] = x.slot_off[1] = 0; x.slot_words = x.dir_words = x.ckpt_off = x.bnd_off = 0;
-        }
-        slots.pieces.emplace_back(0u, (u32)sel.ch.size());
-    } else {
-        const int cols = generic ? score_cols(band) : 5;
-        if (!plan_slots(sel, hmb, kernel_info[generic ? chain_gen_kernel_id(cols) : (int)K_C5_CE0_N], (u64)cols, band, arena, slots)) return 0;
-        // (the slots themselves: exactly what the pieces need -- the arena is a budget, a quarter to spare would overdraw it)
-        if ((rc_ = grow(c, c->d_chain_scratch, c->cap_chain_scratch, slots.need_scratch, true))) return rc_;
-    }
-    if ((rc_ = enqueue_chains(c, sel, L, slots, d_mirror, band, ms, ss, carry ? score_cols(band) : 0, generic ? score_cols(band) : 0, run))) return rc_;
+    if (!plan_slots(sel, hmb, ck.slots, band, arena, slots)) return 0;
+    // (the slots themselves: exactly what the pieces need -- the arena is a budget, a quarter to spare would overdraw it; none for a
+    // kernel without slots)
+    if ((rc_ = grow(c, c->d_chain_scratch, c->cap_chain_scratch, slots.need_scratch, true))) return rc_;
+    if ((rc_ = enqueue_chains(c, sel, L, slots, d_mirror, band, ms, ss, ck, run))) return rc_;
     for (const ChainPick& p : sel.ch) M[p.mi].on_device = true;
     return 0;
 }
@@ -796,8 +791,8 @@ int replay_chain(Ctx* cc, const ChainRun& run, Machine& m, const u32 mi, u64* ca
         if ((w.info & 1u) != (t.b_rc ? 1u : 0u)) return differs("orientation", w.info & 1u, t.b_rc ? 1u : 0u);
         if ((w.info >> 8) != (u32)st) return differs("pre-check status", w.info >> 8, (u64)st);
         if (w.X != (u32)X) return differs("row count", w.X, X);
-        if (!run.carry) {   // the cell the device picked for this call (N by window): the host's own answer for the same window, with the full margin (k_chain_c has one cell: nothing to compare; k_chain2g runs the N-aware cell in every call that runs a DP)
-            const bool want_n = run.generic ? st == GAMDP_ST_OK : st == GAMDP_ST_OK && x.has_n != 0 &&
+        if (run.kernel.n_bit != CHAIN_N_UNREPORTED) {   // the cell the device picked for this call: every call that runs a DP, or (N by window) the host's own answer for the same window, with the full margin
+            const bool want_n = run.kernel.n_bit == CHAIN_N_EVERY_DP ? st == GAMDP_ST_OK : st == GAMDP_ST_OK && x.has_n != 0 &&
                                 (run.n_by_contig || run.ms->window_has_n(t.a_id, false, 0, (int64_t)t.begin_a - (int64_t)run.band - 64, (int64_t)t.begin_a + (int64_t)X - 1 + (int64_t)run.band + 64) ||
                                  run.ss->window_has_n(t.b_id, t.b_rc, 0, (int64_t)t.begin_b - 64, (int64_t)t.begin_b + (int64_t)X - 1 + 64));
             if (((w.info >> 1) & 1u) != (want_n ? 1u : 0u)) return differs("choice of the N-aware cell", (w.info >> 1) & 1u, want_n ? 1u : 0u);
@@ -1199,8 +1194,8 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
             for (const CohortStats& s : cst) { Q.chains += s.chains; Q.chain_calls += s.chain_calls; }
             Q.round_loop_mbs = n_main - Q.chains;
             if (chained) {
-                Q.scratch_bytes = run.scratch_bytes; Q.launches = run.n_launches; Q.twins = run.n_twins; Q.cols = (uint32_t)run.cols;
-                std::snprintf(Q.kernel, sizeof(Q.kernel), "%s", run.kernel);
+                Q.scratch_bytes = run.scratch_bytes; Q.launches = run.n_launches; Q.twins = run.n_twins; Q.cols = (uint32_t)run.kernel.cols;
+                std::snprintf(Q.kernel, sizeof(Q.kernel), "%s", run.kernel.name);
                 Q.chain_ms = (double)chain_ms;
             }
         }

@@ -273,49 +273,15 @@ __global__ __launch_bounds__(64, C <= 5 ? 5 : 4) void k_score(const ScoreParams 
     }
 }
 
-template <class F>
-auto with_score_kernel(const int cols, F&& f)
-{
-    switch (cols) {
-    case 2: return f(k_score<2>);
-    case 3: return f(k_score<3>);
-    case 5: return f(k_score<5>);
-    case 9: return f(k_score<9>);
-    default: return f(k_score<17>);
-    }
-}
-
 }  // namespace
 
-int score_cols(const u32 band)
+const KernelFamily& score_family()
 {
-    const u32 Y = 2 * band + 1;
-    for (const int c : {2, 3, 5, 9}) if (Y <= 64u * (u32)c) return c;
-    return 17;
-}
-
-const char* score_kernel_name(const int cols)
-{
-    switch (cols) {
-    case 2: return "k_score<2>";
-    case 3: return "k_score<3>";
-    case 5: return "k_score<5>";
-    case 9: return "k_score<9>";
-    default: return "k_score<17>";
-    }
-}
-
-int score_waves_per_cu(const int cols)
-{
-    int n = 0;
-    const hipError_t e = with_score_kernel(cols, [&](auto k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 64, 0); });
-    return (e == hipSuccess && n > 0) ? n : 4;
-}
-
-int launch_score(const int cols, const ScoreParams& p, const unsigned n_wavefronts, void* stream)
-{
-    with_score_kernel(cols, [&](auto k) { hipLaunchKernelGGL(k, dim3(n_wavefronts), dim3(64), 0, (hipStream_t)stream, p); return 0; });
-    return (int)hipGetLastError();
+    static const KernelFamily f = {
+        {(const void*)k_score<2>, (const void*)k_score<3>, (const void*)k_score<5>, (const void*)k_score<9>, (const void*)k_score<17>},
+        {"k_score<2>", "k_score<3>", "k_score<5>", "k_score<9>", "k_score<17>"},
+        64};
+    return f;
 }
 
 }  // namespace gamdp
