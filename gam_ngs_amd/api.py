@@ -76,6 +76,18 @@ class Context:
         _check(self, self.lib.gamdp_ctx_l1_chain_stats(self.handle, C.byref(st)), "gamdp_ctx_l1_chain_stats")
         return st.as_dict()
 
+    def set_walk_skip(self, mode: int):
+        """How the walks of the eight-task band-150 kernel cross rows without directions: L.WALK_STRIPS (the default: a strip call per
+        stretch of the path) or L.WALK_SKIP_DIAG (groups of 64 rows that provably hold diagonal steps only are jumped over;
+        gamdp_ctx_set_walk_skip).  The results do not depend on it."""
+        _check(self, self.lib.gamdp_ctx_set_walk_skip(self.handle, mode), "gamdp_ctx_set_walk_skip")
+
+    def walk_skip_stats(self):
+        """What the eight-task launches of the last gamdp_align_batch on this context counted, as a dict (gamdp_ctx_walk_skip_stats)."""
+        st = L.WalkSkipStats()
+        _check(self, self.lib.gamdp_ctx_walk_skip_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_stats")
+        return st.as_dict()
+
     def l1_tail_calls(self):
         """The tail alignments of the last alignMergeBlocks on this context and the seed each was given, as
         (merge_block, right, begin_a, source) tuples ordered by merge block, left before right (gamdp_ctx_l1_tail_calls)."""
@@ -215,6 +227,22 @@ class MultiContext:
         for i in range(len(self.devices)):
             if self.lib.gamdp_ctx_set_l1_walk_bands(self.lib.gamdp_multi_ctx(self.handle, i), which) != 0:
                 raise L.GamdpError("gamdp_ctx_set_l1_walk_bands(%r) failed on context %d" % (which, i))
+
+    def set_walk_skip(self, mode: int, which=None):
+        """Context.set_walk_skip on every context of the handle, or on context `which` alone."""
+        for i in (range(len(self.devices)) if which is None else (which,)):
+            if self.lib.gamdp_ctx_set_walk_skip(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
+                raise L.GamdpError("gamdp_ctx_set_walk_skip(%r) failed on context %d" % (mode, i))
+
+    def walk_skip_stats(self):
+        """Context.walk_skip_stats of every context of the handle (a list of dicts)."""
+        out = []
+        for i in range(len(self.devices)):
+            st = L.WalkSkipStats()
+            if self.lib.gamdp_ctx_walk_skip_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
+                raise L.GamdpError("gamdp_ctx_walk_skip_stats failed on context %d" % i)
+            out.append(st.as_dict())
+        return out
 
     def l1_chain_stats(self):
         """Context.l1_chain_stats of every context of the handle (a list of dicts)."""

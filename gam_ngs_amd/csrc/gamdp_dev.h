@@ -89,7 +89,13 @@ struct LaunchParams {
     // (gamdp_ctx_launch_info).  nullptr = not counted (the chain kernels).
     u32* stats;
 };
-enum : int { LS_UNITS = 0, LS_DIRFREE, LS_PACKED_TOP, LS_PACKED_TOP_MIXED, LS_STRIPS, LS_TOP_WANTED, LS_COUNT = 8 };
+// (LS_SKIP_*: the eight-task kernel's walks in LP_WALK_SKIP_DIAG launches -- tests made, groups whose equality was evaluated, groups
+// jumped over, and the rows by which the jumped-over spans fall short of 64 each (the span below a walk's end cell ends on the next
+// checkpoint row: 1 .. 64 rows) -- rows = 64 groups - short, which keeps the words 32 bits wide; gamdp_ctx_walk_skip_stats)
+enum : int { LS_UNITS = 0, LS_DIRFREE, LS_PACKED_TOP, LS_PACKED_TOP_MIXED, LS_STRIPS, LS_TOP_WANTED, LS_SKIP_TESTS, LS_SKIP_TESTED, LS_SKIP_GROUPS, LS_SKIP_SHORT, LS_COUNT = 12 };
+// the eight-task kernel's walks test for indel-free groups before they ask for a strip (kernel_walk.inc, walk_many<..., SKIP>):
+// set by the host for contexts in GAMDP_WALK_SKIP_DIAG mode; every other kernel ignores it
+constexpr u32 LP_WALK_SKIP_DIAG = 32;
 // the two-task kernel walks its two tasks side by side (kernel_walk.inc) instead of one after the other: set by the host for
 // launches of at most two rounds, where the wavefronts of a SIMD walk at the same time and the scalar unit is the bottleneck
 constexpr u32 LP_WALK_SIDE_BY_SIDE = 1;

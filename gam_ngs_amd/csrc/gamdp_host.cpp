@@ -87,6 +87,7 @@ const Tuning& tuning()
         if ((e = std::getenv("GAMDP_L1_DEVICE_HITS"))) x.l1_device_hits = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_L1_CHAIN_CARRY"))) x.l1_chain_carry = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_L1_WALK_ANY_BAND"))) x.l1_walk_any_band = std::atoi(e) == 1;
+        if ((e = std::getenv("GAMDP_WALK_SKIP"))) x.walk_skip = std::atoi(e) == 1;
         return x;
     }();
     return t;
@@ -307,6 +308,7 @@ int Ctx::init(int dev)
     l1_hits_mode = tuning().l1_device_hits ? GAMDP_L1_HITS_DEVICE : GAMDP_L1_HITS_HOST;
     l1_chain = tuning().l1_chain_carry ? GAMDP_L1_CHAIN_CARRY : GAMDP_L1_CHAIN_WALK;
     walk_bands = tuning().l1_walk_any_band ? GAMDP_L1_WALK_ANY_BAND : GAMDP_L1_WALK_BAND_150;
+    walk_skip = tuning().walk_skip ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
     if (hipSetDevice(dev) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("hipGetDeviceProperties failed"); return GAMDP_ENODEV; }
@@ -849,13 +851,14 @@ int Ctx::align_scratch(u64 arena_call)
 }
 
 // LaunchParams::flags / prio_* of a launch
-static void launch_policy(const Launch& L, LaunchParams& p)
+static void launch_policy(const Launch& L, LaunchParams& p, const int walk_skip)
 {
     const Tuning& tu = tuning();
     const u64 tpw = (u64)kernel_info[L.kid].tasks_per_wave, units = L.count / tpw;
     p.flags = (L.kid == K_P17_CE4 && (u64)L.count / 2 <= tu.side_walk_rounds * L.n_slots) ? LP_WALK_SIDE_BY_SIDE : 0u;
     if (tu.no_packed_top) p.flags |= LP_NO_PACKED_TOP;
     if (tu.no_packed_top_mixed) p.flags |= LP_NO_PACKED_TOP_MIXED;
+    if (L.kid == K_O19_CE15 && walk_skip == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_DIAG;   // (gamdp_ctx_set_walk_skip; the eight-task kernel alone has the test)
     // the end-cell / strip / walk phase of the two- and eight-task kernels issues one level above a steady-state fill in
     // launches of more than two rounds (gamdp_dev.h; GAMDP_WALK_PRIO=0..3 overrides, A/B)
     p.flags |= (tu.walk_prio >= 0 ? (u32)tu.walk_prio : (units > 2ull * L.n_slots ? 1u : 0u)) << LP_WALK_PRIO_SHIFT;
@@ -913,7 +916,7 @@ int Ctx::align_run(AlignCall& a)
         p.scratch = d_scratch + L.scratch_off; p.slot_words = L.slot_words; p.dir_words = L.dir_words; p.ypad = L.ypad;
         p.ckpt_off = L.ckpt_off; p.bnd_off = L.bnd_off;
         p.stats = d_stats + li * LS_COUNT;
-        launch_policy(L, p);
+        launch_policy(L, p, walk_skip);
         hipStream_t const on = L.aux ? aux_stream : stream;
         HIPCHK(this, hipEventRecord(events[li].first, on));
         const int e = launch_align(L.kid, p, L.n_slots, L.dyn_lds, on);
@@ -975,6 +978,12 @@ void Ctx::align_collect(AlignCall& a)
             const u32* st = a.hstats.data() + li * LS_COUNT;
             r.units_dirfree = st[LS_DIRFREE]; r.units_packed_top = st[LS_PACKED_TOP]; r.units_packed_top_mixed = st[LS_PACKED_TOP_MIXED];
             r.strips = st[LS_STRIPS]; r.units_top_wanted = st[LS_TOP_WANTED];
+            if (L.kid == K_O19_CE15) {   // gamdp_ctx_walk_skip_stats: the eight-task launches of the call
+                gamdp_walk_skip_stats& W = last_walk_skip;
+                W.tests += st[LS_SKIP_TESTS]; W.groups_tested += st[LS_SKIP_TESTED]; W.groups_skipped += st[LS_SKIP_GROUPS];
+                W.rows_skipped += 64ull * st[LS_SKIP_GROUPS] - st[LS_SKIP_SHORT];
+                W.strips += st[LS_STRIPS];
+            }
             r.piece = log_piece;
             r.rounds = L.n_slots ? (double)r.units / (double)L.n_slots : 0.0;
             r.kernel_ms = (double)ms;
@@ -1332,6 +1341,23 @@ int gamdp_ctx_launch_info(const gamdp_ctx* ctx, gamdp_launch_info* out, size_t c
     return 0;
 }
 
+static_assert(sizeof(gamdp_walk_skip_stats) == 48 && offsetof(gamdp_walk_skip_stats, strips) == 32 && offsetof(gamdp_walk_skip_stats, mode) == 40,
+              "gamdp_walk_skip_stats: the layout include/gamdp.h documents (gam_ngs_amd/lib.py WalkSkipStats mirrors it)");
+
+int gamdp_ctx_set_walk_skip(gamdp_ctx* ctx, int mode)
+{
+    if ((mode != GAMDP_WALK_STRIPS && mode != GAMDP_WALK_SKIP_DIAG) || !ctx) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->walk_skip = mode;
+    return 0;
+}
+
+int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out)
+{
+    if (!ctx || !out) return GAMDP_EINVAL;
+    *out = reinterpret_cast<const Ctx*>(ctx)->last_walk_skip;
+    return 0;
+}
+
 int gamdp_seqset_create(gamdp_ctx* ctx, const uint8_t* const* seqs, const uint64_t* lens, uint32_t n, int is_ascii,
                         gamdp_seqset** out)
 {
@@ -1370,6 +1396,8 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     const SeqSet* sa = reinterpret_cast<const SeqSet*>(set_a);
     const SeqSet* sb = reinterpret_cast<const SeqSet*>(set_b);
     c->launch_log.clear();
+    c->last_walk_skip = gamdp_walk_skip_stats{};
+    c->last_walk_skip.mode = (uint32_t)c->walk_skip;
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; for (Ctx* h : c->helpers) h->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {
@@ -1404,6 +1432,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     cc[0]->trim_scratch(); cc[1]->trim_scratch();
     cc[1]->kernel_ms = 0; cc[1]->kernel_launches = 0;
     cc[1]->launch_log.clear(); cc[1]->log_launches = true;
+    cc[1]->walk_skip = c->walk_skip; cc[1]->last_walk_skip = gamdp_walk_skip_stats{};
     int rc[2] = {0, 0};
     auto worker = [&](int t) noexcept {
         for (size_t k = (size_t)t; k < 4 && rc[t] == 0; k += 2) {
@@ -1419,6 +1448,11 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     }
     c->kernel_ms += cc[1]->kernel_ms; c->kernel_launches += cc[1]->kernel_launches;
     c->launch_log.insert(c->launch_log.end(), cc[1]->launch_log.begin(), cc[1]->launch_log.end());
+    {
+        gamdp_walk_skip_stats& W = c->last_walk_skip;
+        const gamdp_walk_skip_stats& H = cc[1]->last_walk_skip;
+        W.tests += H.tests; W.groups_tested += H.groups_tested; W.groups_skipped += H.groups_skipped; W.rows_skipped += H.rows_skipped; W.strips += H.strips;
+    }
     std::stable_sort(c->launch_log.begin(), c->launch_log.end(), [](const gamdp_launch_info& x, const gamdp_launch_info& y) { return x.piece < y.piece; });
     if (rc[1]) c->set_error(cc[1]->err);
     return rc[0] ? rc[0] : rc[1];

@@ -57,6 +57,7 @@ struct Tuning {
     bool l1_device_hits = false;        // GAMDP_L1_DEVICE_HITS=1: new contexts start in GAMDP_L1_HITS_DEVICE mode (gamdp_ctx_set_l1_hits)
     bool l1_chain_carry = false;        // GAMDP_L1_CHAIN_CARRY=1: new contexts start in GAMDP_L1_CHAIN_CARRY mode (gamdp_ctx_set_l1_chain)
     bool l1_walk_any_band = false;      // GAMDP_L1_WALK_ANY_BAND=1: new contexts start with GAMDP_L1_WALK_ANY_BAND (gamdp_ctx_set_l1_walk_bands)
+    bool walk_skip = false;             // GAMDP_WALK_SKIP=1: new contexts start in GAMDP_WALK_SKIP_DIAG mode (gamdp_ctx_set_walk_skip)
 };
 const Tuning& tuning();
 
@@ -216,6 +217,10 @@ struct Ctx {
     int l1_chain = GAMDP_L1_CHAIN_WALK;
     int walk_bands = GAMDP_L1_WALK_BAND_150;   // WALK mode: the bands that have a chain kernel (gamdp_ctx_set_l1_walk_bands); CARRY ignores it
     gamdp_l1_chain_stats last_l1_chain{};
+    // whether the eight-task kernel's walks jump over indel-free groups (gamdp_ctx_set_walk_skip -> LP_WALK_SKIP_DIAG), and what the
+    // eight-task launches of the last gamdp_align_batch counted (align_collect adds while log_launches is set)
+    int walk_skip = GAMDP_WALK_STRIPS;
+    gamdp_walk_skip_stats last_walk_skip{};
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }

@@ -364,8 +364,15 @@ __device__ __forceinline__ void finish_many(const LaunchParams& p, const u32 fir
     // keeps its bookkeeping on the scalar unit: measured 6 % slower on 98 304 x 50 kb; eight packed tasks: 4 % faster)
     if constexpr (NT == 8 || LPT == 64) {
         if (side_by_side && skip != (1 << NT) - 1) {
+            // (eight-task kernel, LP_WALK_SKIP_DIAG: the instance whose walks jump over indel-free groups -- wave-uniform, per launch)
+            bool skip_diag = false;
+            if constexpr (PK && NT == 8 && LPT == QL) skip_diag = (p.flags & LP_WALK_SKIP_DIAG) != 0;
             for (;;) {
-                const u32 need = (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
+                u32 need;
+                if constexpr (PK && NT == 8 && LPT == QL) {
+                    need = skip_diag ? (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT, true>(&ta, &tb, wcs, skip, lane, lds_tk, p.stats))
+                                     : (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
+                } else need = (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
                 if (need == 0) break;
                 if constexpr (LPT != 64) {
                     // the strips the walks wait for, one task at a time with the whole wavefront on it -- inlined HERE, where nothing

@@ -26,9 +26,14 @@
 // inlined and calls again.  Nothing of the walks is in registers while a strip is made, so nobody saves registers around it
 // (as a call from in here: 28 callee-saved registers stored and re-loaded per strip call, 14 KB of scratch each time).  The
 // two-task kernel (LPT = 64: carries in the caller's frame, one copy per lane) keeps the call in here and always returns 0.
-template <int C, int CE, bool HASN, bool PK, int NT, int LPT = QL>
-__device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* wcs, const int skip_mask_, const int lane, const Tk* tks = nullptr)
+// SKIP (eight-task kernel only, LP_WALK_SKIP_DIAG; a second instance, the default one holds none of it): a walk that stands on
+// a block without directions first asks whether the groups below it hold nothing but diagonal steps, and jumps over those that do
+// (the test sits where the inner loop finds `need`) before it is reported as waiting for a strip.  skip_stats: the launch's
+// statistics words (LS_SKIP_*), nullptr = not counted.
+template <int C, int CE, bool HASN, bool PK, int NT, int LPT = QL, bool SKIP = false>
+__device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* wcs, const int skip_mask_, const int lane, const Tk* tks = nullptr, u32* skip_stats = nullptr)
 {
+    static_assert(!SKIP || (PK && LPT == QL && NT == 8), "the diagonal test reads the eight-task kernel's checkpoint rows (PairFmt::GRP)");
     static_assert(DIRFREE_OK<CE, C, HASN>, "the multi-task kernels are direction-free kernels");
     static_assert((LPT == QL && (NT == 4 || NT == 8)) || (LPT == 64 && NT == 2 && PK), "one or two quads, or the pair of the two-task kernel");
     static_assert(!HASN, "only the N-free kernels use it (the N planes would be two more word pairs per lane and iteration)");
@@ -60,6 +65,8 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
     gptr const dir = (gptr)pick64((u64)tap->dir, (u64)tbq->dir);
     const int df_lo = pick(tap->df_lo, tbq->df_lo), df_hi = pick(tap->df_hi, tbq->df_hi);
     const int sshift = uni(tap->sshift);   // the same for every task of the wavefront
+    gptr ckpt = nullptr;                   // SKIP: the slot's checkpoint rows
+    if constexpr (SKIP) ckpt = (gptr)pick64((u64)tap->ckpt, (u64)tbq->ckpt);
 
     const WalkCarry w0 = wcs[gt];
     int x = w0.x, y = w0.y, pos = w0.pos;
@@ -69,6 +76,19 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
     int mat_calls = w0.mat_calls;
     int l = y / C, c = y - l * C;
     bool active = g < NT && w0.status == 2 && !((skip_mask >> gt) & 1);
+    // SKIP: a task whose test found no passing group waits for its strip (no second test before it has one); what this call counted
+    [[maybe_unused]] bool stuck = false;
+    [[maybe_unused]] u32 sk_tests = 0, sk_tested = 0, sk_groups = 0, sk_short = 0;
+    [[maybe_unused]] auto count_skips = [&]() {
+        if constexpr (SKIP) {
+            if (skip_stats != nullptr && j == 0 && g < NT && sk_tests != 0) {
+                atomicAdd(skip_stats + LS_SKIP_TESTS, sk_tests);
+                atomicAdd(skip_stats + LS_SKIP_TESTED, sk_tested);
+                atomicAdd(skip_stats + LS_SKIP_GROUPS, sk_groups);
+                if (sk_short != 0) atomicAdd(skip_stats + LS_SKIP_SHORT, sk_short);
+            }
+        }
+    };
 
     // Outer loop: strips on demand; inner loop: the walk proper, left as soon as some task stands on a block without
     // directions (the call sits outside the inner loop so that the walk's registers are not spilled around it in there)
@@ -95,6 +115,92 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
             vlo = (mat_lo == df_lo) ? 0 : mat_lo;   // below df_lo the tagged blocks are all there
         }
         m_need = __ballot(active && need);
+        if constexpr (SKIP) {
+            // ---- no directions for blk0: are the groups below nothing but diagonal steps?
+            // The reference's traceback tests diag first and steps diagonally iff sw[x][y] == sw[x-1][y] + S
+            // (banded_smith_waterman.cc:265-285), and its fill makes sw[x][y] >= sw[x-1][y] + S in every cell with pos >= 1, x >= 1
+            // (:158-168).  So when H(x, y) - H(x - n, y) equals the sum of S over the n base pairs between them, the sum
+            // telescopes into n non-negative terms that add to zero: all n steps are diagonal, no direction word needed.  Both
+            // values are in memory: checkpoint G holds every lane's row after row-time 64 G - 1 (materialise_impl starts from it),
+            // and a walk runs out of directions exactly there (tau = 64 G - 1: the block below a tagged range or a used-up strip)
+            // or at its end cell, whose H is the score.  In the fill's tilt G = H + 16 x + 8 y a diagonal step adds S + 16 (12 or
+            // 21), so the stored values are compared as they are.  Lane j of the task's 8 tests the j-th span below the walk (the
+            // first one down to the next checkpoint row, 64 rows each after that); the walk jumps over the passing prefix.
+            // (A strip change inside materialised groups -- blk0 within [mat_lo, mat_hi] -- is left to the strips.)
+            const bool cand = active && need && !stuck && !(blk0 >= mat_lo && blk0 <= mat_hi);
+            if (__ballot(cand) != 0) {
+                typedef PairFmt<C, LPT> FMT;
+                const int gi = blk0 >> 2, d0 = (tau & 63) + 1;             // checkpoint gi: d0 steps below the walk
+                const int g_lo = df_lo >> 2, g_top = (df_hi >> 2) - 1;     // the groups whose checkpoint rows the fill stored
+                const int off = (j == 0) ? 0 : d0 + 64 * (j - 1), cnt = (j == 0) ? d0 : 64;   // this lane's span: steps [off, off + cnt) from the top
+                const int gb = gi - j;                                     // the checkpoint at its lower end, gb + 1 at its upper end
+                const int cc = min(max(c, 0), C - 1);
+                auto ck_val = [&](const int gidx) -> int {
+                    gptr rp = ckpt + (u64)min(max(gidx, g_lo), g_top) * (u64)FMT::CK_WORDS + (u32)(lane_base + ll) * FMT::CK_LANE;
+                    const u32 v = rp[cc];
+                    return (int)(float)(half ? hi_of(v) : lo_of(v)) + (int)rp[C + half];   // as materialise_impl's unpack(row[c], grp_base), in units of G
+                };
+                const int g_bot = ck_val(gb), g_up = ck_val(gb + 1);
+                const int ia_lo = a_base + pos - off - 63, ib_lo = bb_base + x - off - 63;   // base p of the span's 64 (0 = lowest row)
+                u32 aw[5], bw[5];
+#pragma unroll
+                for (int k = 0; k < 5; ++k) { aw[k] = a2[(ia_lo >> 4) + k]; bw[k] = b2[(ib_lo >> 4) + k]; }
+                // the upper value: the score at the end cell, else the checkpoint row the walk stands on (a full span of 64)
+                const bool at_start = len == 0u;
+                const bool up_ok = (j == 0) ? (at_start || (d0 == 64 && gi + 1 <= g_top)) : true;
+                const int g_top_val = (j == 0 && at_start) ? w0.best + 16 * x + 8 * y : g_up;
+                const int p0 = 64 - cnt;                                    // lane 0: the top d0 bases only
+                u32 eq[4];
+                int m = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const u32 a16 = __builtin_amdgcn_alignbit(aw[k + 1], aw[k], (u32)(ia_lo & 15) * 2u), b16 = __builtin_amdgcn_alignbit(bw[k + 1], bw[k], (u32)(ib_lo & 15) * 2u);
+                    const u32 xr = a16 ^ b16, ne = (xr | (xr >> 1)) & 0x55555555u;
+                    const int q0 = p0 - 16 * k;
+                    const u32 msk = (q0 <= 0) ? 0x55555555u : ((q0 >= 16) ? 0u : (0x55555555u << (2 * q0)));
+                    eq[k] = ~ne & msk;
+                    m += __builtin_popcount(eq[k]);
+                }
+                // every cell of the span is an else-branch cell of the fill (x >= 2, pos >= 2 above the cell it ends on, which
+                // keeps x >= 1, pos >= 1: row 0 and pos == 0 stay with finish_walk), both checkpoint rows exist
+                const bool tested = cand && up_ok && gb >= g_lo && x - (off + cnt) >= 1 && pos - (off + cnt) >= 1;
+                const bool pass = tested && g_top_val - g_bot == 12 * cnt + 9 * m;
+                const u32 gm_pass = (u32)(__ballot(pass) >> (8 * g)) & 0xFFu, gm_tested = (u32)(__ballot(tested) >> (8 * g)) & 0xFFu;
+                const int k = __builtin_ctz(~gm_pass | 0x100u);            // the passing prefix
+                const bool inc = j < k;
+                {
+                    int cnt_m = inc ? m : 0;
+                    cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0xB1, 0xf, 0xf, true);
+                    cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0x4E, 0xf, 0xf, true);
+                    cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0x141, 0xf, 0xf, true);
+                    nm += (u32)cnt_m;
+                }
+                {
+                    int ptop = 0, pbot = 0;
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) if (eq[kk]) ptop = 16 * kk + ((31 - __builtin_clz(eq[kk])) >> 1);
+#pragma unroll
+                    for (int kk = 3; kk >= 0; --kk) if (eq[kk]) pbot = 16 * kk + (__builtin_ctz(eq[kk]) >> 1);
+                    const u32 gm_eq = (u32)(__ballot(inc && m > 0) >> (8 * g)) & 0xFFu;
+                    const int Ltop = gm_eq ? __builtin_ctz(gm_eq) : 0, Lbot = gm_eq ? 31 - __builtin_clz(gm_eq) : 0;
+                    const int off_hi = __builtin_amdgcn_ds_bpermute(4 * (8 * g + Ltop), off + 63 - ptop);   // steps below the walk
+                    const int off_lo = __builtin_amdgcn_ds_bpermute(4 * (8 * g + Lbot), off + 63 - pbot);
+                    if (gm_eq) {
+                        if (!(have & 2)) { have |= 2; la = pos - off_hi; lb = begin_b + x - off_hi; }
+                        have |= 1; fa = pos - off_lo; fb = begin_b + x - off_lo;
+                    }
+                }
+                if (cand) {
+                    sk_tests++; sk_tested += (u32)__builtin_popcount(gm_tested); sk_groups += (u32)k;
+                    if (k > 0) {
+                        const int n = d0 + 64 * (k - 1);
+                        x -= n; pos -= n; len += (u32)n;
+                        sk_short += (u32)(64 - d0);
+                    } else stuck = true;
+                }
+                if (__ballot(cand && k > 0) != 0) continue;   // round again: the next test, directions, or a task that has dropped out
+            }
+        }
         if (m_need != 0 || __ballot(active) == 0) break;
         // ---- this lane's direction word and the packed bases of its 16 steps: all loads in flight together
         const int myblk = blk0 - j;
@@ -175,6 +281,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
             w.mat_calls = mat_calls;
             w.need_q = strip; w.need_ghi = blk0 >> 2;
         }
+        count_skips();
         u32 need = 0;
 #pragma unroll
         for (int s = 0; s < NT; ++s) need |= ((m_need >> (8 * s)) & 0xFFull) ? (1u << s) : 0u;
@@ -209,6 +316,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
             w.mat_q = mat_q; w.mat_lo = mat_lo; w.mat_hi = mat_hi; w.old_q = old_q; w.old_lo = old_lo; w.old_hi = old_hi;
             w.mat_calls = mat_calls;
         }
+        count_skips();
         return 0u;
     }
 #pragma unroll

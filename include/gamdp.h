@@ -172,6 +172,31 @@ typedef struct gamdp_launch_info {
 /* copies up to `cap` records to out (may be NULL when cap == 0); *n = how many launches the call made */
 int gamdp_ctx_launch_info(const gamdp_ctx* ctx, gamdp_launch_info* out, size_t cap, size_t* n);
 
+/* How the walks of the eight-task band-150 kernel ("k_align_o<19,15>") cross the rows whose directions the fill did not keep.
+ *   GAMDP_WALK_STRIPS     the default: the directions of every group of 64 rows on the path are re-created (a strip call).
+ *   GAMDP_WALK_SKIP_DIAG  opt-in: a walk that stands on a block without directions first compares H(x, y) - H(x - 64, y), two
+ *       values the fill stored, with the score sum of the 64 base pairs between them.  The reference's traceback tests diag first
+ *       (banded_smith_waterman.cc:265-285) and its fill makes every cell >= its diag candidate (:158-168), so equality proves 64
+ *       diagonal steps: the walk takes them at once, eight groups per test, and asks for a strip only where the test fails.
+ * Results do not depend on the mode.  Every other kernel (one-, two-, four-task, generic, the merge-block chains) ignores it.
+ * gamdp_multi_* honours each context's own setting (gamdp_multi_ctx); GAMDP_WALK_SKIP=1 in the environment (read once per
+ * process) makes SKIP_DIAG the mode of new contexts. */
+#define GAMDP_WALK_STRIPS     0   /* default */
+#define GAMDP_WALK_SKIP_DIAG  1
+int gamdp_ctx_set_walk_skip(gamdp_ctx* ctx, int mode);   /* GAMDP_EINVAL for NULL / unknown mode (mode checked first) */
+/* What the eight-task launches of the last gamdp_align_batch on this context counted on the device, summed over the call's
+ * launches and pieces; all counters 0 when the call made no eight-task launch, everything 0 before the first call. */
+typedef struct gamdp_walk_skip_stats {
+    uint64_t tests;            /* times a walk ran the test (one test looks at up to 8 groups below the walk) */
+    uint64_t groups_tested;    /* groups whose equality was evaluated (both stored rows exist, the span stays in x >= 1, pos >= 1) */
+    uint64_t groups_skipped;   /* groups a walk jumped over */
+    uint64_t rows_skipped;     /* rows of those (64 each; the span below a walk's end cell ends on the next stored row: 1..64) */
+    uint64_t strips;           /* strip re-creations of those launches (the sum of their gamdp_launch_info.strips) */
+    uint32_t mode;             /* GAMDP_WALK_* the call ran in */
+    uint32_t pad_;
+} gamdp_walk_skip_stats;       /* 48 bytes */
+int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
+
 /* ---- sequences ---------------------------------------------------------------------------- */
 /* seqs[i] points to lens[i] bytes: ASCII bases when is_ascii!=0 (normalised like Nucleotide(char)),
  * else base codes A=0 T=1 C=2 G=3 N=4.  Packs to 2 bit + N mask and uploads to the ctx's GPU. */

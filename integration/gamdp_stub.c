@@ -14,3 +14,6 @@ void gamdp_multi_seqset_destroy(gamdp_multi_seqset* s) { (void)s; }
 int gamdp_multi_align_merge_blocks(gamdp_multi* m, const gamdp_multi_seqset* master, const gamdp_multi_seqset* slave, const gamdp_mb_in* in,
                                    size_t n, uint32_t band, gamdp_mb_out* out, gamdp_result* audit, uint32_t audit_stride)
 { (void)m; (void)master; (void)slave; (void)in; (void)n; (void)band; (void)out; (void)audit; (void)audit_stride; return GAMDP_ENODEV; }
+/* (a bridge that opts in to GAMDP_WALK_SKIP_DIAG on the contexts of its handle links against these two; there is no context here) */
+int gamdp_ctx_set_walk_skip(gamdp_ctx* ctx, int mode) { (void)ctx; (void)mode; return GAMDP_ENODEV; }
+int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out) { (void)ctx; (void)out; return GAMDP_ENODEV; }

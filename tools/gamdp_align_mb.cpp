@@ -3,13 +3,15 @@
 //
 //   gamdp-align-mb <master.fasta> <slave.fasta> <mergeblocks.tsv> <out.tsv> [--band N] [--device D | --devices D0,D1,..]
 //                  [--repeat K] [--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]]
-//                  [--device-hits] [--carry-chains] [--walk-any-band]
+//                  [--device-hits] [--carry-chains] [--walk-any-band] [--walk-skip]
 //
 // --device-hits seeds the tail alignments with findHits on the GPU (gamdp_ctx_set_l1_hits; the output does not change).
 // --carry-chains runs the main chains on the one-wavefront carry kernel (gamdp_ctx_set_l1_chain: any band up to 543 on the device,
 // no scratch; the output does not change).
 // --walk-any-band gives the default chain mode a chain kernel at every band up to 543 (gamdp_ctx_set_l1_walk_bands: k_chain2 at 150,
 // k_chain2g<C> elsewhere; the output does not change).
+// --walk-skip lets the walks of the eight-task band-150 kernel jump over groups of rows that provably hold diagonal steps only
+// (gamdp_ctx_set_walk_skip; it matters for the big batches of the round loop; the output does not change).
 // --devices runs the step on several GPUs of the node (gamdp_multi_*: merge blocks partitioned statically by predicted
 // cells, one host thread + context per device, no collective); a device may be listed twice.  The output is the same
 // whatever the device list -- unlike gam-merge --threads N, whose paired-contig order depends on thread timing.
@@ -55,16 +57,17 @@ static int region_vote(void*, int32_t, int32_t, int32_t, int32_t, int32_t, int32
 int main(int argc, char** argv)
 {
     if (argc < 5) die("usage: gamdp-align-mb <master.fasta> <slave.fasta> <mergeblocks.tsv> <out.tsv> [--band N] [--device D] [--repeat K] "
-                      "[--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]] [--device-hits] [--carry-chains] [--walk-any-band]");
+                      "[--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]] [--device-hits] [--carry-chains] [--walk-any-band] [--walk-skip]");
     unsigned band = GAMDP_DEFAULT_BAND;
     int device = 0, repeat = 1;
     std::vector<int> devices;
     std::string pctg_prefix, blocks_path, filtered_path;
-    bool device_hits = false, carry_chains = false, walk_any_band = false;
+    bool device_hits = false, carry_chains = false, walk_any_band = false, walk_skip = false;
     for (int i = 5; i < argc; i += 2) {
         if (!std::strcmp(argv[i], "--device-hits")) { device_hits = true; i--; continue; }   // (a flag: no value follows)
         if (!std::strcmp(argv[i], "--carry-chains")) { carry_chains = true; i--; continue; }
         if (!std::strcmp(argv[i], "--walk-any-band")) { walk_any_band = true; i--; continue; }
+        if (!std::strcmp(argv[i], "--walk-skip")) { walk_skip = true; i--; continue; }
         if (i + 1 >= argc) die(std::string("option ") + argv[i] + " needs a value");
         if (!std::strcmp(argv[i], "--band")) band = (unsigned)std::atoi(argv[i + 1]);
         else if (!std::strcmp(argv[i], "--device")) device = std::atoi(argv[i + 1]);
@@ -161,6 +164,11 @@ int main(int argc, char** argv)
         if (ctx && gamdp_ctx_set_l1_walk_bands(ctx, GAMDP_L1_WALK_ANY_BAND)) die("gamdp_ctx_set_l1_walk_bands failed");
         for (int d = 0; multi && d < gamdp_multi_size(multi); d++)
             if (gamdp_ctx_set_l1_walk_bands(gamdp_multi_ctx(multi, d), GAMDP_L1_WALK_ANY_BAND)) die("gamdp_ctx_set_l1_walk_bands failed");
+    }
+    if (walk_skip) {   // the eight-task kernel's walks jump over indel-free groups (identical results)
+        if (ctx && gamdp_ctx_set_walk_skip(ctx, GAMDP_WALK_SKIP_DIAG)) die("gamdp_ctx_set_walk_skip failed");
+        for (int d = 0; multi && d < gamdp_multi_size(multi); d++)
+            if (gamdp_ctx_set_walk_skip(gamdp_multi_ctx(multi, d), GAMDP_WALK_SKIP_DIAG)) die("gamdp_ctx_set_walk_skip failed");
     }
 
     std::vector<gamdp_mb_out> out(in.size());
