@@ -3,9 +3,10 @@
 // cell's value and on its three neighbours' values only (:229-308) -- what the fill holds when it computes the cell.  So every cell
 // carries the summary of the traceback that would start in it, made from the summary of the cell that step leads to: where the
 // traceback ends (:321), its number of ops, its number of MATCH ops and its first and last MATCH (my_alignment.cc:167-193, :228-262).
-// The summary of the end cell (:173-215) is the result.  No directions, no rows of the matrix, no scratch arena, no walk: a third
-// implementation that shares the sequence windows and the scoring rows with k_score (gamdp_score_common.inc) and nothing with the
-// alignment kernels (gamdp_kernel.hip, kernel_*.inc, gamdp_wide.hip), whose walks it is there to check.
+// The summary of the end cell (:173-215) is the result.  No directions, no rows of the matrix, no scratch arena, no walk.  The
+// wavefront's state, the task as the wavefront knows it, the candidacy of a cell in the end-cell search and the fast range are
+// k_score's, stated once in gamdp_score_common.inc (which says what carry_task keeps its own text of, and why); nothing is shared
+// with the alignment kernels (gamdp_kernel.hip, kernel_*.inc, gamdp_wide.hip), whose walks this kernel is there to check.
 //
 // Lane layout as in k_score: one task per wavefront, lane l owns band columns [C*l, C*l + C) and is at row i = tau - l at row-time
 // tau.  A cell is (value, summary); both go through the two lane shifts of a row-time (left of column 0: the lane below's last column

@@ -36,19 +36,13 @@ __device__ __forceinline__ Sum step_on(Sum t, const bool match, const int cur)
     return t;
 }
 
+// the wavefront's state: WaveBase (gamdp_score_common.inc) holds the values, this the summaries
 template <int C>
-struct CWave {
-    int h[C];        // the lane's cells of the row it was at last: value ...
-    int sB[C], sln[C], snm[C], sF[C], sLc[C];   // ... and summary, a register array per field
-    int a5[C];       // 5 * code of the a bases its columns meet at this row-time (pos = A0 + tau + (C-1) * lane + c)
-    int dead[C];     // fast blocks: 0, or -32 for a column beyond the band's last (the lane holds C columns whatever the band)
-    int leftadd;     // fast blocks: what column 0's `left` adds: 0, or S_NEG in lane 0 (no column left of it)
-    u32 row;         // the scoring-matrix row (fields S + 16) of the lane's b base (comes up from the lane below)
-    SWin sa, sb;     // slow_step's bases (wave-uniform): the a bases lane 63 takes and the b bases lane 0 takes, from row-time tau - used on
-    int used;
-    int64_t aidx, bidx;   // index of the a base lane 63 takes at row-time 0 / of the b base of row 0
-    int bv, bk;           // best candidate of the end-cell search so far: value, scan position ...
-    Sum bs;               // ... and its summary
+struct CWave : WaveBase<C, K_DEAD> {
+    using B = WaveBase<C, K_DEAD>;
+    using B::h; using B::a5; using B::dead; using B::leftadd; using B::row;
+    int sB[C], sln[C], snm[C], sF[C], sLc[C];   // the summaries of the cells h[], a register array per field
+    Sum bs;                                     // the summary of the end-cell search's best candidate (bv, bk)
 
     __device__ __forceinline__ Sum sum(const int c) const { return {sB[c], sln[c], snm[c], sF[c], sLc[c]}; }
     __device__ __forceinline__ void set_sum(const int c, const Sum& t) { sB[c] = t.B; sln[c] = t.ln; snm[c] = t.nm; sF[c] = t.F; sLc[c] = t.Lc; }
@@ -71,7 +65,7 @@ struct CWave {
     }
     __device__ __forceinline__ void fast_step(const SWin& wa, const SWin& wb, const int k, const int cur0)
     {
-        row = (u32)shift_in_from_below((int)score_row16(win_code(wb, k), win_isn(wb, k)), (int)row);
+        this->take_row(wb, k);
         const int L = from_lane_below(h[C - 1]) + leftadd;
         const Sum Ls = sum_from_lane_below(sum(C - 1));
         fast_cell(0, h[1], sum(1), L, Ls, cur0);
@@ -80,34 +74,15 @@ struct CWave {
 #pragma unroll
         for (int c = 1; c < C - 1; ++c) fast_cell(c, h[c + 1], sum(c + 1), h[c - 1], sum(c - 1), cur0 + c);
         fast_cell(C - 1, U, Us, h[C - 2], sum(C - 2), cur0 + C - 1);
-        const int enters = shift_in_from_above(a_field(win_code(wa, k), win_isn(wa, k)), a5[1]);
-#pragma unroll
-        for (int c = 0; c < C - 1; ++c) a5[c] = a5[c + 1];
-        a5[C - 1] = enters;
-    }
-    // into / out of the fast blocks' form in front of row-time tau: the lane's cells are those of row tau - 1 - lane
-    __device__ __forceinline__ void to_block(const int tau, const int lane)
-    {
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] = dead[c] ? S_NEG : h[c] + 16 * (tau - 1 - lane) + 8 * (C * lane + c);
-    }
-    __device__ __forceinline__ void from_block(const int tau, const int lane)
-    {
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] -= 16 * (tau - 1 - lane) + 8 * (C * lane + c);
+        this->advance(wa, k);
     }
 
-    // One row-time by the reference's rules, cell by cell: the value as in k_score's slow_step (:112-168), then the step the traceback
-    // takes from the cell (:229-308) and the summary it leaves.  Lanes that are not at a row of the matrix, and cells outside a,
-    // compute along: a traceback never enters them (pos does not grow along it, and a cell with x < 0, y < 0 or pos < 0 ends it).
+    // One row-time by the reference's rules, cell by cell: the value (:112-168), then the step the traceback takes from
+    // the cell (:229-308) and the summary it leaves.  Lanes that are not at a row of the matrix, and cells outside a, compute along:
+    // a traceback never enters them (pos does not grow along it, and a cell with x < 0, y < 0 or pos < 0 ends it).
     __device__ __forceinline__ void slow_step(const STask& t, const int tau, const int lane)
     {
-        if (used == 32) {
-            sa = load_win_uniform(t.a2, t.an, aidx + tau);
-            sb = load_win_uniform(t.b2, t.bn, bidx + tau);
-            used = 0;
-        }
-        row = (u32)shift_in_from_below((int)score_row16(win_code(sb, used), win_isn(sb, used)), (int)row);
+        this->slow_take_row(t, tau);
         const int i = tau - lane;
         const int p0 = t.A0 + tau + (C - 1) * lane, j0 = C * lane;
         const bool row0 = i == 0;
@@ -119,20 +94,21 @@ struct CWave {
         for (int c = 0; c < C; ++c) {
             const int pos = p0 + c, j = j0 + c;
             const int sc = cell_score16(row, a5[c]) - 16;
-            const bool in_a = (u32)pos < (u32)t.alen;
             const int leftv = c > 0 ? h[c > 0 ? c - 1 : 0] : L;
             const int upv = c < C - 1 ? h[c < C - 1 ? c + 1 : 0] : U;
             const Sum lefts = c > 0 ? sum(c > 0 ? c - 1 : 0) : Ls;
             const Sum ups = c < C - 1 ? sum(c < C - 1 ? c + 1 : 0) : Us;
             const int dold = h[c];
-            // row 0 (:112-132): `left` is the neighbour itself, without a gap
+            // The value, by the rules of slow_value (gamdp_score_common.inc, where each is explained), in this kernel's own text: why
+            // it is not the call is in that file's header.  row 0 (:112-132) ...
+            const bool in_a = (u32)pos < (u32)t.alen;
             const bool has_left = pos > 0 && j > 0;
             const bool r0_gap = t.fs ? (u32)pos <= (u32)S_MAXGAP : in_a;                 // :116
             const bool r0_forced = t.fs && pos > S_MAXGAP && pos < t.alen;               // :125
             const int v_gap = has_left ? max3i(sc, S_GAP, leftv) : max(S_GAP, sc);
             const int v_forced = has_left ? max(sc, leftv) : sc;
             const int v0 = r0_gap ? v_gap : (r0_forced ? v_forced : 0);
-            // rows >= 1 (:141-168)
+            // ... rows >= 1 (:141-168)
             const int up = j < t.Y - 1 ? upv + S_GAP : S_NEG;
             const int left = pos == 0 ? ((t.fs && i > S_MAXGAP) ? S_NEG : S_GAP) : (j > 0 ? leftv + S_GAP : S_NEG);
             const int vn = in_a ? max3i(dold + sc, up, left) : 0;
@@ -155,28 +131,8 @@ struct CWave {
             h[c] = v;
             if (c == 0) { U = from_lane_above(h[0]); Us = sum_from_lane_above(sum(0)); }
         }
-        // the end-cell search (:174-212) as in k_score: the larger value, then the smaller scan position
-        const bool active = i >= 0 && i < t.X;
-        const bool last_row = active && !t.fe && i == t.X - 1;
-        const bool on_diag = active && t.ea >= p0 && t.ea <= p0 + C - 1 &&
-                             (!t.fe || (t.X >= S_MAXGAP + 1 && i >= t.X - 1 - S_MAXGAP));   // :201, an unsigned compare there
-        if (__any(last_row || on_diag)) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int pos = p0 + c, j = j0 + c;
-                const bool ok_row = last_row && j < t.Y && pos >= 0 && pos <= t.ea;
-                const bool ok_diag = on_diag && j < t.Y && pos == t.ea;
-                const int key = ok_row ? j : t.Y + (i - t.iA);
-                const int v = h[c];   // (a cell outside a holds 0, as the reference's matrix does)
-                if ((ok_row || ok_diag) && (v > bv || (v == bv && key < bk))) { bv = v; bk = key; bs = sum(c); }
-            }
-        }
-        // the window moves on by one base
-        const int enters = shift_in_from_above(a_field(win_code(sa, used), win_isn(sa, used)), a5[1]);
-#pragma unroll
-        for (int c = 0; c < C - 1; ++c) a5[c] = a5[c + 1];
-        a5[C - 1] = enters;
-        ++used;
+        this->search_end_cell(t, i, p0, j0, [&](const int c) { bs = sum(c); });
+        this->slow_advance();
     }
 };
 
@@ -185,51 +141,20 @@ struct CWave {
 template <int C>
 __device__ __forceinline__ DevResult carry_task(const DevTask& dt, const int lane)
 {
-    STask t;
-    t.a2 = (splane)dt.a2; t.an = (splane)dt.an; t.b2 = (splane)dt.b2; t.bn = (splane)dt.bn;
-    const int band = dt.band;
-    t.A0 = dt.begin_a - band;
-    t.alen = dt.alen; t.X = dt.X; t.Y = 2 * band + 1;
-    t.ea = (int)min(dt.end_a, (int64_t)S_POS_MAX);
-    const int64_t over = dt.end_a - ((int64_t)dt.begin_a + band);
-    t.iA = over >= 0 ? (int)min(over, (int64_t)(1 << 30)) : 0;
-    t.fs = (dt.flags & TF_FORCE_START) != 0; t.fe = (dt.flags & TF_FORCE_END) != 0;
-    const int LE = (t.Y - 1) / C;   // the lane that holds the band's last column
-
+    const STask t = stask_of(dt);
     CWave<C> w;
-    const int64_t ap = dt.a_base + t.A0 + (int64_t)(C - 1) * lane;
+    w.seed(t, dt, lane);
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int64_t k = ap + c;
-        w.h[c] = 0;
-        w.set_sum(c, {0, 0, 0, 0, 0});
-        w.a5[c] = a_field((t.a2[k >> 4] >> ((u32)(k & 15) * 2u)) & 3u, ((t.an[k >> 5] >> (u32)(k & 31)) & 1u) != 0);
-        w.dead[c] = (C * lane + c >= t.Y) ? K_DEAD : 0;
-    }
-    w.leftadd = lane == 0 ? S_NEG : 0;
-    w.aidx = dt.a_base + t.A0 + 63 * (C - 1) + C;
-    w.bidx = dt.b_base + dt.begin_b;
-    w.sa = load_win_uniform(t.a2, t.an, w.aidx);
-    w.sb = load_win_uniform(t.b2, t.bn, w.bidx);
-    w.used = 0;
-    w.row = 0;
-    w.bv = S_NEG; w.bk = S_KEY_NONE;
+    for (int c = 0; c < C; ++c) w.set_sum(c, {0, 0, 0, 0, 0});
     w.bs = {0, 0, 0, 0, 0};
-
-    // The G row-times from tau on are fast when, in lanes 0 .. LE: every row is >= 1 and every pos > 0 (lane 0, column 0 has the
-    // smallest); the highest row, lane 0's, is below the last; every pos < |a| (lane LE, column C-1 has the largest); and pos == end_a
-    // is in nobody's columns.  span = what the largest pos of the block is above the smallest of its first row-time.
+    // The task's row-times: runs of fast blocks (the bases of a block are fetched while the block before it is computed) where
+    // FastRange allows them, slow_step for all others.  Written out here and not shared: see gamdp_score_common.inc.
     constexpr int G = K_BLOCK;
-    const int span = G - 1 + (LE + 1) * (C - 1);
-    const int f_lo = max(LE + 1, 1 - t.A0);
-    const int f_hi = min(t.X - 1 - G, t.alen - t.A0 - span - 1);
-    const int64_t d_hi64 = (int64_t)t.ea - t.A0;
-    const int d_hi = (int)min(d_hi64, (int64_t)0x7fffffff), d_lo = (int)max(min(d_hi64 - span, (int64_t)0x7fffffff), (int64_t)-0x7fffffff);
-    auto fast = [&](const int tau) { return tau >= f_lo && tau <= f_hi && (tau < d_lo || tau > d_hi); };
+    const int LE = (t.Y - 1) / C;
+    const FastRange fast(t, C, G, LE);
     const int T = t.X + LE;   // lane LE is at the last row at row-time X - 1 + LE
     for (int tau = 0; tau < T;) {
         if (fast(tau)) {
-            // a run of fast blocks: the bases of a block are fetched while the block before it is computed
             SWin wa = load_win_uniform(t.a2, t.an, w.aidx + tau), wb = load_win_uniform(t.b2, t.bn, w.bidx + tau);
             w.to_block(tau, lane);
             int cur = (tau - lane) * K_XSHIFT + C * lane;   // the code of the lane's column 0 at this row-time
@@ -240,8 +165,7 @@ __device__ __forceinline__ DevResult carry_task(const DevTask& dt, const int lan
                     w.fast_step(wa, wb, k, cur);
                     cur += K_XSHIFT;
                 }
-                wa.lo = (u32)__builtin_amdgcn_readfirstlane((int)na.lo); wa.hi = (u32)__builtin_amdgcn_readfirstlane((int)na.hi); wa.n = (u32)__builtin_amdgcn_readfirstlane((int)na.n);
-                wb.lo = (u32)__builtin_amdgcn_readfirstlane((int)nb.lo); wb.hi = (u32)__builtin_amdgcn_readfirstlane((int)nb.hi); wb.n = (u32)__builtin_amdgcn_readfirstlane((int)nb.n);
+                wa = win_uniform(na); wb = win_uniform(nb);
                 tau += G;
             } while (fast(tau));
             w.from_block(tau, lane);
@@ -252,7 +176,8 @@ __device__ __forceinline__ DevResult carry_task(const DevTask& dt, const int lan
         }
     }
 
-    // the winner of the end-cell search, and its summary from the lane that holds it (a scan position belongs to one cell, so to one lane)
+    // the winner of the end-cell search (best_of_wave and end_of_key of gamdp_score_common.inc in this kernel's own text, see that
+    // file's header), and its summary from the lane that holds it (a scan position belongs to one cell, so to one lane)
     int bv = w.bv, bk = w.bk;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -287,7 +212,6 @@ __device__ __forceinline__ DevResult carry_task(const DevTask& dt, const int lan
                 res.last_a = t.A0 + e.Lc / K_XSHIFT + e.Lc % K_XSHIFT; res.last_b = dt.begin_b + e.Lc / K_XSHIFT;
                 found = 3;
             } else {
-                // no MATCH: first_match_pos ends behind the last op (my_alignment.cc:167-193), last_match_pos keeps the begin (:228-262)
                 res.first_a = pos + 1; res.first_b = dt.begin_b + x + 1;
                 res.last_a = res.begin_a; res.last_b = res.begin_b;
             }

@@ -23,7 +23,7 @@
 namespace gamdp {
 namespace {
 
-#include "gamdp_score_common.inc"   // constants, sequence windows, scoring rows, lane shifts, STask: shared with k_carry (gamdp_carry.hip)
+#include "gamdp_score_common.inc"   // shared with k_carry / k_chain_c: windows, scoring rows, WaveBase, slow_value, the end-cell search, FastRange
 
 constexpr int S_DEAD = -32;            // what a column beyond the band's last adds on its diagonal in the fast blocks (see fast_step)
 // fast_step's argument: a value that leaves the band's last column through the columns beyond it comes back n rows lower having lost
@@ -40,21 +40,11 @@ static_assert(543 + 64 <= SEQ_PAD_BASES && 63 * 16 + 17 + 63 + 64 + 64 <= SEQ_PA
 template <int C>
 constexpr int S_BLOCK = C == 2 ? 16 : (C == 3 || C == 5) ? 15 : C;
 
+// the wavefront's state (WaveBase, gamdp_score_common.inc) and the two kinds of row-time
 template <int C>
-struct SWave {
-    int h[C];        // the lane's cells of the row it was at last
-    int a5[C];       // 5 * code of the a bases its columns meet at this row-time (pos = A0 + tau + (C-1) * lane + c)
-    int dead[C];     // fast blocks: 0, or -32 for a column beyond the band's last (the lane holds C columns whatever the band)
-    int leftadd;     // fast blocks: what column 0's `left` adds: 0, or S_NEG in lane 0 (no column left of it)
-    // The two sequences move through the wavefront one lane per row-time, so only its end lanes take new bases, and those are the
-    // same for all lanes (scalar work): lane l's row at row-time tau is lane l-1's of tau-1 (`row` comes up from the lane below,
-    // lane 0 takes b[begin_b + tau]), and the a base that enters lane l's window is the one lane l+1 has in column 1 (it comes down
-    // from the lane above, lane 63 takes a[A0 + tau + 63 (C-1) + C]).
-    u32 row;         // the scoring-matrix row (fields S + 16) of the lane's b base
-    SWin sa, sb;     // slow_step's bases (wave-uniform): the a bases lane 63 takes and the b bases lane 0 takes, from row-time tau - used on
-    int used;
-    int64_t aidx, bidx;   // index of the a base lane 63 takes at row-time 0 / of the b base of row 0
-    int bv, bk;           // best candidate of the end-cell search so far: value, scan position
+struct SWave : WaveBase<C, S_DEAD> {
+    using B = WaveBase<C, S_DEAD>;
+    using B::h; using B::a5; using B::dead; using B::leftadd; using B::row;
 
     // Row-time K of a fast block: nothing special happens in any lane that holds band columns, so every cell is
     //     sw[i][j] = max(sw[i-1][j] + S, sw[i-1][j+1] + gap, sw[i][j-1] + gap)                              (:160-164)
@@ -70,7 +60,7 @@ struct SWave {
     template <int K>
     __device__ __forceinline__ void fast_step(const SWin& wa, const SWin& wb)
     {
-        row = (u32)shift_in_from_below((int)score_row16(win_code(wb, K), win_isn(wb, K)), (int)row);
+        this->take_row(wb, K);
         const int L = from_lane_below(h[C - 1]);
         h[0] = max3i(h[0] + cell_score16(row, a5[K % C]) + dead[0], h[1], L + leftadd);
         const int U = from_lane_above(h[0]);   // (lane 63 gets 0, for a column that is always dead: 2*band+1 is odd, 64*C even)
@@ -78,17 +68,6 @@ struct SWave {
         for (int c = 1; c < C - 1; ++c) h[c] = max3i(h[c] + cell_score16(row, a5[(c + K) % C]) + dead[c], h[c + 1], h[c - 1]);
         h[C - 1] = max3i(h[C - 1] + cell_score16(row, a5[(C - 1 + K) % C]) + dead[C - 1], U, h[C - 2]);
         a5[K % C] = shift_in_from_above(a_field(win_code(wa, K), win_isn(wa, K)), a5[(1 + K) % C]);
-    }
-    // into / out of the fast blocks' form in front of row-time tau: the lane's cells are those of row tau - 1 - lane
-    __device__ __forceinline__ void to_block(const int tau, const int lane)
-    {
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] = dead[c] ? S_NEG : h[c] + 16 * (tau - 1 - lane) + 8 * (C * lane + c);
-    }
-    __device__ __forceinline__ void from_block(const int tau, const int lane)
-    {
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] -= 16 * (tau - 1 - lane) + 8 * (C * lane + c);
     }
     template <int K>
     __device__ __forceinline__ void fast_block(const SWin& wa, const SWin& wb)
@@ -99,67 +78,25 @@ struct SWave {
         }
     }
 
-    // One row-time by the reference's rules, cell by cell.  Lanes that are not at a row of the matrix compute along (nothing reads
-    // what they make: see the header) and offer no candidates.  No branch depends on the lane except around the candidates: the
-    // lane shifts need every lane.
+    // One row-time by the reference's rules, cell by cell (slow_value).  Lanes that are not at a row of the matrix compute along
+    // (nothing reads what they make: see the header) and offer no candidates.  No branch depends on the lane except around the
+    // candidates: the lane shifts need every lane.
     __device__ __forceinline__ void slow_step(const STask& t, const int tau, const int lane)
     {
-        if (used == 32) {
-            sa = load_win_uniform(t.a2, t.an, aidx + tau);
-            sb = load_win_uniform(t.b2, t.bn, bidx + tau);
-            used = 0;
-        }
-        row = (u32)shift_in_from_below((int)score_row16(win_code(sb, used), win_isn(sb, used)), (int)row);
+        this->slow_take_row(t, tau);
         const int i = tau - lane;
         const int p0 = t.A0 + tau + (C - 1) * lane, j0 = C * lane;
-        const bool row0 = i == 0;
         const int L = from_lane_below(h[C - 1]);   // (lane 0: unused, its column 0 has no left neighbour)
         int U = 0;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-            const int pos = p0 + c, j = j0 + c;
-            const int s = cell_score16(row, a5[c]) - 16;
-            const bool in_a = (u32)pos < (u32)t.alen;
             const int leftv = c > 0 ? h[c > 0 ? c - 1 : 0] : L;
             const int upv = c < C - 1 ? h[c < C - 1 ? c + 1 : 0] : U;
-            // row 0 (:112-132): `left` is the neighbour itself, without a gap
-            const bool has_left = pos > 0 && j > 0;
-            const bool r0_gap = t.fs ? (u32)pos <= (u32)S_MAXGAP : in_a;                 // :116
-            const bool r0_forced = t.fs && pos > S_MAXGAP && pos < t.alen;               // :125
-            const int v_gap = has_left ? max3i(s, S_GAP, leftv) : max(S_GAP, s);
-            const int v_forced = has_left ? max(s, leftv) : s;
-            const int v0 = r0_gap ? v_gap : (r0_forced ? v_forced : 0);
-            // rows >= 1 (:141-168).  At pos == 0 the cell above is outside a and holds 0, so `diag` is the plain form; `left` is the gap
-            // score whatever the column (:147), or nothing once a forced start is more than FORCE_MAXGAP_LEN rows away (:151-156)
-            const int up = j < t.Y - 1 ? upv + S_GAP : S_NEG;
-            const int left = pos == 0 ? ((t.fs && i > S_MAXGAP) ? S_NEG : S_GAP) : (j > 0 ? leftv + S_GAP : S_NEG);
-            const int vn = in_a ? max3i(h[c] + s, up, left) : 0;
-            h[c] = row0 ? v0 : vn;
+            h[c] = slow_value(t, i, j0 + c, p0 + c, cell_score16(row, a5[c]) - 16, h[c], leftv, upv);
             if (c == 0) U = from_lane_above(h[0]);
         }
-        // the end-cell search (:174-212): last-row cells with 0 <= pos <= end_a in column order, then the cells with pos == end_a by
-        // rows; `!found || value > max`, i.e. the larger value, then the smaller scan position
-        const bool active = i >= 0 && i < t.X;
-        const bool last_row = active && !t.fe && i == t.X - 1;
-        const bool on_diag = active && t.ea >= p0 && t.ea <= p0 + C - 1 &&
-                             (!t.fe || (t.X >= S_MAXGAP + 1 && i >= t.X - 1 - S_MAXGAP));   // :201, an unsigned compare there
-        if (__any(last_row || on_diag)) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int pos = p0 + c, j = j0 + c;
-                const bool ok_row = last_row && j < t.Y && pos >= 0 && pos <= t.ea;
-                const bool ok_diag = on_diag && j < t.Y && pos == t.ea;
-                const int key = ok_row ? j : t.Y + (i - t.iA);
-                const int v = h[c];   // (a cell outside a holds 0, as the reference's matrix does)
-                if ((ok_row || ok_diag) && (v > bv || (v == bv && key < bk))) { bv = v; bk = key; }
-            }
-        }
-        // the window moves on by one base
-        const int enters = shift_in_from_above(a_field(win_code(sa, used), win_isn(sa, used)), a5[1]);
-#pragma unroll
-        for (int c = 0; c < C - 1; ++c) a5[c] = a5[c + 1];
-        a5[C - 1] = enters;
-        ++used;
+        this->search_end_cell(t, i, p0, j0, [](int) {});
+        this->slow_advance();
     }
 };
 
@@ -168,56 +105,23 @@ struct SWave {
 template <int C>
 __device__ __noinline__ void score_task(const DevTask& dt, ScoreRec* results, const int lane)
 {
-    STask t;
-    t.a2 = (splane)dt.a2; t.an = (splane)dt.an; t.b2 = (splane)dt.b2; t.bn = (splane)dt.bn;
-    const int band = dt.band;
-    t.A0 = dt.begin_a - band;
-    t.alen = dt.alen; t.X = dt.X; t.Y = 2 * band + 1;
-    t.ea = (int)min(dt.end_a, (int64_t)S_POS_MAX);
-    const int64_t over = dt.end_a - ((int64_t)dt.begin_a + band);
-    t.iA = over >= 0 ? (int)min(over, (int64_t)(1 << 30)) : 0;
-    t.fs = (dt.flags & TF_FORCE_START) != 0; t.fe = (dt.flags & TF_FORCE_END) != 0;
-    const int LE = (t.Y - 1) / C;   // the lane that holds the band's last column
-
+    const STask t = stask_of(dt);
     SWave<C> w;
-    const int64_t ap = dt.a_base + t.A0 + (int64_t)(C - 1) * lane;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int64_t k = ap + c;
-        w.h[c] = 0;
-        w.a5[c] = a_field((t.a2[k >> 4] >> ((u32)(k & 15) * 2u)) & 3u, ((t.an[k >> 5] >> (u32)(k & 31)) & 1u) != 0);
-        w.dead[c] = (C * lane + c >= t.Y) ? S_DEAD : 0;
-    }
-    w.leftadd = lane == 0 ? S_NEG : 0;
-    w.aidx = dt.a_base + t.A0 + 63 * (C - 1) + C;
-    w.bidx = dt.b_base + dt.begin_b;
-    w.sa = load_win_uniform(t.a2, t.an, w.aidx);
-    w.sb = load_win_uniform(t.b2, t.bn, w.bidx);
-    w.used = 0;
-    w.row = 0;
-    w.bv = S_NEG; w.bk = S_KEY_NONE;
-
-    // The G row-times from tau on are fast when, in lanes 0 .. LE: every row is >= 1 and every pos > 0 (lane 0, column 0 has the
-    // smallest); the highest row, lane 0's, is below the last; every pos < |a| (lane LE, column C-1 has the largest); and pos == end_a
-    // is in nobody's columns.  span = what the largest pos of the block is above the smallest of its first row-time.
+    w.seed(t, dt, lane);
+    // The task's row-times: runs of fast blocks (the bases of a block are fetched while the block before it is computed) where
+    // FastRange allows them, slow_step for all others.  Written out here and not shared: see gamdp_score_common.inc.
     constexpr int G = S_BLOCK<C>;
-    const int span = G - 1 + (LE + 1) * (C - 1);
-    const int f_lo = max(LE + 1, 1 - t.A0);
-    const int f_hi = min(t.X - 1 - G, t.alen - t.A0 - span - 1);
-    const int64_t d_hi64 = (int64_t)t.ea - t.A0;
-    const int d_hi = (int)min(d_hi64, (int64_t)0x7fffffff), d_lo = (int)max(min(d_hi64 - span, (int64_t)0x7fffffff), (int64_t)-0x7fffffff);
-    auto fast = [&](const int tau) { return tau >= f_lo && tau <= f_hi && (tau < d_lo || tau > d_hi); };
+    const int LE = (t.Y - 1) / C;
+    const FastRange fast(t, C, G, LE);
     const int T = t.X + LE;   // lane LE is at the last row at row-time X - 1 + LE
     for (int tau = 0; tau < T;) {
         if (fast(tau)) {
-            // a run of fast blocks: the bases of a block are fetched while the block before it is computed
             SWin wa = load_win_uniform(t.a2, t.an, w.aidx + tau), wb = load_win_uniform(t.b2, t.bn, w.bidx + tau);
             w.to_block(tau, lane);
             do {
                 const SWin na = load_win(t.a2, t.an, w.aidx + tau + G), nb = load_win(t.b2, t.bn, w.bidx + tau + G);   // (all lanes the same words)
                 w.template fast_block<0>(wa, wb);
-                wa.lo = (u32)__builtin_amdgcn_readfirstlane((int)na.lo); wa.hi = (u32)__builtin_amdgcn_readfirstlane((int)na.hi); wa.n = (u32)__builtin_amdgcn_readfirstlane((int)na.n);
-                wb.lo = (u32)__builtin_amdgcn_readfirstlane((int)nb.lo); wb.hi = (u32)__builtin_amdgcn_readfirstlane((int)nb.hi); wb.n = (u32)__builtin_amdgcn_readfirstlane((int)nb.n);
+                wa = win_uniform(na); wb = win_uniform(nb);
                 tau += G;
             } while (fast(tau));
             w.from_block(tau, lane);
@@ -229,24 +133,12 @@ __device__ __noinline__ void score_task(const DevTask& dt, ScoreRec* results, co
     }
 
     int bv = w.bv, bk = w.bk;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int ov = __shfl_xor(bv, o, 64), ok = __shfl_xor(bk, o, 64);
-        if (ov > bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
-    }
-    bv = __builtin_amdgcn_readfirstlane(bv);
-    bk = __builtin_amdgcn_readfirstlane(bk);
-    u32 status = S_ST_EMPTY;   // no end cell (:215)
-    int score = 0, end_a = 0, end_b = 0;
-    if (bk != S_KEY_NONE) {
-        const int x = bk < t.Y ? t.X - 1 : t.iA + (bk - t.Y);
-        const int pos = bk < t.Y ? t.A0 + x + bk : t.ea;
-        if (pos >= t.alen) status = S_ST_OUT_OF_RANGE;   // the traceback's a.at(pos) throws
-        else { status = S_ST_OK; score = bv; end_a = pos; end_b = dt.begin_b + x; }
-    }
+    best_of_wave(bv, bk);
+    const SEnd e = end_of_key(t, bk);
+    const bool ok = e.status == S_ST_OK;
     if (lane == 0) {
         typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 rec = {(u32)score, (u32)end_a, (u32)end_b, status | ((u32)C << 8)};
+        const u32x4 rec = {(u32)(ok ? bv : 0), (u32)(ok ? e.pos : 0), (u32)(ok ? dt.begin_b + e.x : 0), e.status | ((u32)C << 8)};
         *reinterpret_cast<u32x4*>(&results[dt.res_idx]) = rec;
     }
 }
