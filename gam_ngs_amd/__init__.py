@@ -9,7 +9,8 @@ without a GPU so its symbols can be checked), but creating a context without a g
 """
 from .lib import GamdpError, load_library, library_path  # noqa: F401
 from .api import (ABlast, BandedSmithWaterman, Block, Context, MergeBlock, MultiContext, MultiSequenceSet,  # noqa: F401
-                  MyAlignment, PctgBuilder, SequenceSet, GAP_A, GAP_B, MATCH, MISMATCH)
+                  MyAlignment, PctgBuilder, SequenceSet, GAP_A, GAP_B, MATCH, MISMATCH, ops_fingerprint)
 
 __all__ = ["GamdpError", "load_library", "library_path", "Context", "SequenceSet", "BandedSmithWaterman",
-           "MyAlignment", "ABlast", "MultiContext", "MultiSequenceSet", "PctgBuilder", "MergeBlock", "Block", "GAP_A", "GAP_B", "MATCH", "MISMATCH"]
+           "MyAlignment", "ABlast", "MultiContext", "MultiSequenceSet", "PctgBuilder", "MergeBlock", "Block", "GAP_A", "GAP_B", "MATCH", "MISMATCH",
+           "ops_fingerprint"]

@@ -126,6 +126,14 @@ class Context:
         self.lib.gamdp_ctx_carry_info(self.handle, arr, n.value, C.byref(n))
         return [arr[i].as_dict() for i in range(n.value)]
 
+    def carry_ops_info(self):
+        """The launches of the last gamdp_carry_ops_batch call on this context, as dicts (gamdp_ctx_carry_ops_info)."""
+        n = C.c_size_t()
+        self.lib.gamdp_ctx_carry_ops_info(self.handle, None, 0, C.byref(n))
+        arr = (L.ScoreLaunchInfo * max(1, n.value))()
+        self.lib.gamdp_ctx_carry_ops_info(self.handle, arr, n.value, C.byref(n))
+        return [arr[i].as_dict() for i in range(n.value)]
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.gamdp_ctx_destroy(self.handle)
@@ -449,6 +457,21 @@ class BandedSmithWaterman:
         _check(self.ctx, self.ctx.lib.gamdp_carry_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out), "gamdp_carry_batch")
         return [MyAlignment.from_result(r, None) for r in out]
 
+    def find_results_with_ops_fingerprints(self, calls, bands=None):
+        """find_results with the fingerprint of every call's edit string (gamdp_carry_ops_batch: the carry kernel with the
+        fingerprint as a sixth field of a cell's summary): (results, fingerprints).  fingerprints[i] equals
+        ops_fingerprint(find_alignments(calls, want_ops=True)[i].ops) for a call whose status is OK and is 0 otherwise."""
+        n = len(calls)
+        if n == 0:
+            return [], []
+        if isinstance(self.ctx, MultiContext):
+            raise L.GamdpError("find_results_with_ops_fingerprints is a single-context call")
+        tasks, sa, sb = self._tasks(calls, bands)
+        out = (L.Result * n)()
+        fp = (C.c_uint32 * n)()
+        _check(self.ctx, self.ctx.lib.gamdp_carry_ops_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out, fp), "gamdp_carry_ops_batch")
+        return [MyAlignment.from_result(r, None) for r in out], list(fp)
+
     def find_alignments(self, calls, want_ops=False, bands=None) -> List[MyAlignment]:
         """calls: list of (a, begin_a, end_a, b, begin_b, end_b[, force_start[, force_end]]); all a's
         must come from one SequenceSet and all b's from one SequenceSet."""
@@ -584,6 +607,16 @@ def load_fasta(path: str):
         return names, codes
     finally:
         lib.gamdp_fasta_close(h)
+
+
+def ops_fingerprint(ops) -> int:
+    """gamdp_ops_fingerprint of an edit string: a str over OPS_CHARS ("ABMX", as MyAlignment.ops), or bytes / a sequence of op codes
+    (GAMDP_OP_*: GAP_A 0, GAP_B 1, MATCH 2, MISMATCH 3; any byte value is taken)."""
+    if isinstance(ops, str):
+        ops = bytes(OPS_CHARS.index(ch) for ch in ops)
+    else:
+        ops = bytes(ops)
+    return int(L.load_library().gamdp_ops_fingerprint(ops, len(ops)))
 
 
 def encode(s) -> bytes:

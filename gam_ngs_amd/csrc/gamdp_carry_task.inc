@@ -1,7 +1,8 @@
 // The DP of one find_alignment call as k_carry runs it (gamdp_carry.hip has the argument): a cell's summary, the wavefront's state and
 // carry_task<C>, which takes one task from its descriptor to its DevResult.  Included inside namespace gamdp { namespace {, behind
-// gamdp_score_common.inc, by gamdp_carry.hip (k_carry: a batch of tasks) and gamdp_chain_carry.hip (k_chain_c: the calls of a merge
-// block's main chain, one after the other); nothing of the alignment kernels is used here.
+// gamdp_score_common.inc, by gamdp_carry.hip (k_carry: a batch of tasks), gamdp_chain_carry.hip (k_chain_c: the calls of a merge
+// block's main chain, one after the other) and gamdp_carry_ops.hip (k_carry_f: k_carry with the edit string's fingerprint as a sixth
+// field of the summary, FP = true below; with FP = false nothing of it exists); nothing of the alignment kernels is used here.
 constexpr int K_DEAD = -32;            // what a column beyond the band's last adds on its diagonal in the fast blocks
 // The dead-column argument of k_score (gamdp_score.hip), here needed in its strict form: what comes back into the band's last column
 // through `up` from the columns beyond it is at least 12 below that column's own diagonal candidate, so the last column's value never
@@ -19,33 +20,72 @@ static_assert(543 * 2 + 2 < K_XSHIFT && (int64_t)500001 * K_XSHIFT + K_XSHIFT < 
 
 enum : int { OP_DIAG = 0, OP_UP = 1, OP_LEFT = 2 };   // MATCH or MISMATCH (x--), GAP_A (x--, y++), GAP_B (y--)
 
-struct Sum { int B, ln, nm, F, Lc; };
-__device__ __forceinline__ Sum sum_from_lane_below(const Sum& s) { return {from_lane_below(s.B), from_lane_below(s.ln), from_lane_below(s.nm), from_lane_below(s.F), from_lane_below(s.Lc)}; }
-__device__ __forceinline__ Sum sum_from_lane_above(const Sum& s) { return {from_lane_above(s.B), from_lane_above(s.ln), from_lane_above(s.nm), from_lane_above(s.F), from_lane_above(s.Lc)}; }
-__device__ __forceinline__ Sum pick(const bool d, const Sum& sd, const bool u, const Sum& su, const Sum& sl)
+// The summary of a cell.  FP: with the fingerprint of the forward edit string of the traceback that starts in the cell
+// (gamdp_ops_fingerprint, include/gamdp.h: F(s . e) = F(s) * K_FP_MULT + e + 1 mod 2^32, F(empty) = 0).  The forward string of a cell
+// is that of the cell its step leads to plus the step's op, so the field is updated as the others are: one step per cell.  Five
+// initialisers leave it 0, the fingerprint of the empty string.
+template <bool FP> struct SumT;
+template <> struct SumT<false> { int B, ln, nm, F, Lc; };
+template <> struct SumT<true> { int B, ln, nm, F, Lc; u32 fp; };
+typedef SumT<false> Sum;
+constexpr u32 K_FP_MULT = 0x9E3779B1u;   // GAMDP_OPS_FP_MULT
+template <bool FP>
+__device__ __forceinline__ SumT<FP> sum_from_lane_below(const SumT<FP>& s)
 {
-    return {d ? sd.B : (u ? su.B : sl.B), d ? sd.ln : (u ? su.ln : sl.ln), d ? sd.nm : (u ? su.nm : sl.nm), d ? sd.F : (u ? su.F : sl.F), d ? sd.Lc : (u ? su.Lc : sl.Lc)};
+    SumT<FP> r = {from_lane_below(s.B), from_lane_below(s.ln), from_lane_below(s.nm), from_lane_below(s.F), from_lane_below(s.Lc)};
+    if constexpr (FP) r.fp = (u32)from_lane_below((int)s.fp);
+    return r;
 }
-// one more op in front of the traceback t; `match`: it is a MATCH (:239, :274) at the cell with code `cur`
-__device__ __forceinline__ Sum step_on(Sum t, const bool match, const int cur)
+template <bool FP>
+__device__ __forceinline__ SumT<FP> sum_from_lane_above(const SumT<FP>& s)
+{
+    SumT<FP> r = {from_lane_above(s.B), from_lane_above(s.ln), from_lane_above(s.nm), from_lane_above(s.F), from_lane_above(s.Lc)};
+    if constexpr (FP) r.fp = (u32)from_lane_above((int)s.fp);
+    return r;
+}
+template <bool FP>
+__device__ __forceinline__ SumT<FP> pick(const bool d, const SumT<FP>& sd, const bool u, const SumT<FP>& su, const SumT<FP>& sl)
+{
+    SumT<FP> r = {d ? sd.B : (u ? su.B : sl.B), d ? sd.ln : (u ? su.ln : sl.ln), d ? sd.nm : (u ? su.nm : sl.nm), d ? sd.F : (u ? su.F : sl.F), d ? sd.Lc : (u ? su.Lc : sl.Lc)};
+    if constexpr (FP) r.fp = d ? sd.fp : (u ? su.fp : sl.fp);
+    return r;
+}
+// one more op in front of the traceback t: `op` at the cell with code `cur`; `match`: it is a MATCH (:239, :274), which only an
+// OP_DIAG is.  The fingerprint takes the op's public code + 1: GAP_A 0 (OP_UP), GAP_B 1 (OP_LEFT), MATCH 2, MISMATCH 3.
+static_assert(OP_UP == 0 + 1 && OP_LEFT == 1 + 1, "a gap's OP_ is its GAMDP_OP_ code + 1");
+template <bool FP>
+__device__ __forceinline__ SumT<FP> step_on(SumT<FP> t, const bool match, const int cur, const int op)
 {
     t.F = (match && t.nm == 0) ? cur : t.F;
     t.Lc = match ? cur : t.Lc;
     t.nm += match ? 1 : 0;
     t.ln += 1;
+    if constexpr (FP) t.fp = t.fp * K_FP_MULT + (u32)(match ? 2 + 1 : (op == OP_DIAG ? 3 + 1 : op));
     return t;
 }
 
 // the wavefront's state: WaveBase (gamdp_score_common.inc) holds the values, this the summaries
-template <int C>
-struct CWave : WaveBase<C, K_DEAD> {
+template <int C, bool FP> struct FpCols { u32 sfp[C]; };   // the sixth field's register array ...
+template <int C> struct FpCols<C, false> {};              // ... which a kernel without it does not have
+template <int C, bool FP = false>
+struct CWave : WaveBase<C, K_DEAD>, FpCols<C, FP> {
+    typedef SumT<FP> Sum;
     using B = WaveBase<C, K_DEAD>;
     using B::h; using B::a5; using B::dead; using B::leftadd; using B::row;
     int sB[C], sln[C], snm[C], sF[C], sLc[C];   // the summaries of the cells h[], a register array per field
     Sum bs;                                     // the summary of the end-cell search's best candidate (bv, bk)
 
-    __device__ __forceinline__ Sum sum(const int c) const { return {sB[c], sln[c], snm[c], sF[c], sLc[c]}; }
-    __device__ __forceinline__ void set_sum(const int c, const Sum& t) { sB[c] = t.B; sln[c] = t.ln; snm[c] = t.nm; sF[c] = t.F; sLc[c] = t.Lc; }
+    __device__ __forceinline__ Sum sum(const int c) const
+    {
+        Sum r = {sB[c], sln[c], snm[c], sF[c], sLc[c]};
+        if constexpr (FP) r.fp = this->sfp[c];
+        return r;
+    }
+    __device__ __forceinline__ void set_sum(const int c, const Sum& t)
+    {
+        sB[c] = t.B; sln[c] = t.ln; snm[c] = t.nm; sF[c] = t.F; sLc[c] = t.Lc;
+        if constexpr (FP) this->sfp[c] = t.fp;
+    }
 
     // Row-time k of a fast block (every lane that holds band columns is at a row >= 1 below the last, every pos inside (0, |a|), no
     // candidate of the end-cell search goes by): every cell is sw[i][j] = max(sw[i-1][j] + S, sw[i-1][j+1] + gap, sw[i][j-1] + gap)
@@ -60,7 +100,7 @@ struct CWave : WaveBase<C, K_DEAD> {
         const int dv = h[c] + f + dead[c];
         const int v = max3i(dv, uv, lv);
         const bool isd = v == dv, isu = v == uv;
-        set_sum(c, step_on(pick(isd, sum(c), isu, su, sl), isd && f != S_MIN_SCORE + 16, cur));
+        set_sum(c, step_on(pick(isd, sum(c), isu, su, sl), isd && f != S_MIN_SCORE + 16, cur, isd ? OP_DIAG : (isu ? OP_UP : OP_LEFT)));
         h[c] = v;
     }
     __device__ __forceinline__ void fast_step(const SWin& wa, const SWin& wb, const int k, const int cur0)
@@ -127,7 +167,7 @@ struct CWave : WaveBase<C, K_DEAD> {
             const int bcode = op == OP_DIAG ? i * K_XSHIFT + j + 1 : op == OP_UP ? i * K_XSHIFT + j + 2 : (i + 1) * K_XSHIFT + j;
             Sum nt = pick(op == OP_DIAG, sum(c), op == OP_UP, ups, lefts);
             if (ends) nt = {bcode, 0, 0, 0, 0};
-            set_sum(c, step_on(nt, op == OP_DIAG && sc != S_MIN_SCORE, i * K_XSHIFT + j));
+            set_sum(c, step_on(nt, op == OP_DIAG && sc != S_MIN_SCORE, i * K_XSHIFT + j, op));
             h[c] = v;
             if (c == 0) { U = from_lane_above(h[0]); Us = sum_from_lane_above(sum(0)); }
         }
@@ -138,11 +178,14 @@ struct CWave : WaveBase<C, K_DEAD> {
 
 // One task.  Inlined into its kernel: a call would cost the callee-saved registers' stack slots, and the kernels are to use no private
 // memory.  The result comes back wave-uniform (every field is made of scalars and of values read from one lane); the caller stores it.
-template <int C>
-__device__ __forceinline__ DevResult carry_task(const DevTask& dt, const int lane)
+// FP: *fp takes the fingerprint of the edit string, 0 unless the status is OK (also wave-uniform).
+template <int C, bool FP = false>
+__device__ __forceinline__ DevResult carry_task(const DevTask& dt, const int lane, u32* const fp = nullptr)
 {
+    typedef SumT<FP> Sum;
     const STask t = stask_of(dt);
-    CWave<C> w;
+    CWave<C, FP> w;
+    if constexpr (FP) *fp = 0;
     w.seed(t, dt, lane);
 #pragma unroll
     for (int c = 0; c < C; ++c) w.set_sum(c, {0, 0, 0, 0, 0});
@@ -203,6 +246,7 @@ __device__ __forceinline__ DevResult carry_task(const DevTask& dt, const int lan
             Sum e;
             e.B = __builtin_amdgcn_readlane(w.bs.B, src); e.ln = __builtin_amdgcn_readlane(w.bs.ln, src); e.nm = __builtin_amdgcn_readlane(w.bs.nm, src);
             e.F = __builtin_amdgcn_readlane(w.bs.F, src); e.Lc = __builtin_amdgcn_readlane(w.bs.Lc, src);
+            if constexpr (FP) *fp = (u32)__builtin_amdgcn_readlane((int)w.bs.fp, src);
             const int xb = e.B / K_XSHIFT, yb = e.B % K_XSHIFT - 1;
             res.begin_a = t.A0 + xb + yb; res.begin_b = dt.begin_b + xb;   // :321
             res.score = bv;

@@ -132,7 +132,7 @@ enum KernelId : int {
     K_COUNT
 };
 
-// The band columns per lane of the kernels that take any band up to 543 (k_align<C,-1,true>, k_score, k_carry, k_chain_c, k_chain2g):
+// The band columns per lane of the kernels that take any band up to 543 (k_align<C,-1,true>, k_score, k_carry, k_carry_f, k_chain_c, k_chain2g):
 // the smallest C of 2, 3, 5, 9, 17 with 2*band+1 <= 64*C.  A wider band still says 17: every caller has its own guard against one.
 constexpr int FAMILY_COLS[5] = {2, 3, 5, 9, 17};
 constexpr int band_cols(const u32 band)
@@ -372,6 +372,7 @@ struct KernelFamily {
 };
 const KernelFamily& score_family();         // k_score<C>    (gamdp_score.hip)
 const KernelFamily& carry_family();         // k_carry<C>    (gamdp_carry.hip)
+const KernelFamily& carry_ops_family();     // k_carry_f<C>  (gamdp_carry_ops.hip)
 const KernelFamily& chain_carry_family();   // k_chain_c<C>  (gamdp_chain_carry.hip)
 const KernelFamily& chain_gen_family();     // k_chain2g<C>  (gamdp_kernel.hip)
 
@@ -425,6 +426,17 @@ struct CarryParams {
 };
 constexpr u32 CARRY_COLS_SHIFT = 16;
 // (carry_family(): the instantiation a band takes is band_cols(band); a grid of wavefronts)
+
+// ---- ... and the fingerprint of its edit string (k_carry_f, gamdp_carry_ops.hip; gamdp_carry_ops_batch) -------------------------
+// The record is k_carry's; the fingerprint (gamdp_ops_fingerprint, 0 unless the status is OK) goes to an array of its own.
+struct CarryOpsParams {
+    const DevTask* tasks;   // as CarryParams
+    u32 n_tasks;
+    u32* cursor;
+    DevResult* results;     // indexed by DevTask::res_idx
+    u32* ops_fp;            // indexed by DevTask::res_idx
+};
+// (carry_ops_family(): as carry_family())
 
 // ---- the main chain of a merge block on carry_task (k_chain_c, gamdp_chain_carry.hip; GAMDP_L1_CHAIN_CARRY) ---------------------
 // One wavefront (a workgroup of 64) per merge block, both orientation attempts one after the other; any band up to 543, the

@@ -336,6 +336,7 @@ Ctx::~Ctx()
     if (d_tasks) (void)hipFree(d_tasks);
     if (d_results) (void)hipFree(d_results);
     if (d_ops) (void)hipFree(d_ops);
+    if (d_ops_fp) (void)hipFree(d_ops_fp);
     if (d_cursor) (void)hipFree(d_cursor);
     if (d_chain) (void)hipFree(d_chain);
     if (h_chain) (void)hipHostFree(h_chain);
@@ -1072,16 +1073,20 @@ int Ctx::align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_op
     return 0;
 }
 
-// ---- the fill-only calls: gamdp_score_batch (k_score, gamdp_score.hip) and gamdp_carry_batch (k_carry, gamdp_carry.hip) ----
+// ---- the fill-only calls: gamdp_score_batch (k_score, gamdp_score.hip), gamdp_carry_batch (k_carry, gamdp_carry.hip) and
+// gamdp_carry_ops_batch (k_carry_f, gamdp_carry_ops.hip) ----
 // The same checks, pre-checks and descriptors as align(); then one launch of the call's kernel per column count C the batch's bands
 // take, each over its tasks by decreasing rows.  No scratch arena, no planner: a wavefront needs nothing but its registers.
 
-// What the two calls differ in: the record a wavefront leaves, the kernel that writes it, and the caller's result made from it.
+// What the calls differ in: the record a wavefront leaves, the kernel that writes it, the caller's result made from it, and whether
+// a fingerprint per task comes back beside the records (set_ops_fp: where the kernel's parameters take that array).
 struct ScoreCall {
     typedef ScoreRec Rec;
     typedef gamdp_score_result Out;
     typedef ScoreParams Params;
     static constexpr const char* api = "gamdp_score_batch";
+    static constexpr bool has_ops_fp = false;
+    static void set_ops_fp(Params&, u32*) {}
     static const KernelFamily& family() { return score_family(); }
     static u32 cols_of(const Rec& r) { return r.info >> 8; }
     static void collect(const Rec& r, u64 cells, Out& o)
@@ -1098,13 +1103,22 @@ struct CarryCall {
     typedef gamdp_result Out;
     typedef CarryParams Params;
     static constexpr const char* api = "gamdp_carry_batch";
+    static constexpr bool has_ops_fp = false;
+    static void set_ops_fp(Params&, u32*) {}
     static const KernelFamily& family() { return carry_family(); }
     static u32 cols_of(const Rec& r) { return r.flags >> CARRY_COLS_SHIFT; }
     static void collect(const Rec& r, u64 cells, Out& o) { fill_result(r, cells, o); }   // as align() makes a gamdp_result of a record
 };
+struct CarryOpsCall : CarryCall {   // the record and the result of CarryCall; the fingerprints are an array beside the records
+    typedef CarryOpsParams Params;
+    static constexpr const char* api = "gamdp_carry_ops_batch";
+    static constexpr bool has_ops_fp = true;
+    static void set_ops_fp(Params& p, u32* d) { p.ops_fp = d; }
+    static const KernelFamily& family() { return carry_ops_family(); }
+};
 
 template <class K>
-int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log)
+int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log, u32* const ops_fp)
 {
     typedef typename K::Rec Rec;
     if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_EHIP; }
@@ -1128,6 +1142,7 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
             std::memset(&out[i], 0, sizeof(out[i]));
             out[i].status = (uint8_t)st;
             out[i].cells = w_prep[i].cells;
+            if (K::has_ops_fp) ops_fp[i] = 0;   // (what a task the pre-checks settle keeps)
             w_prep[i].dt.res_idx = (u32)i;
             colsv[i] = st != GAMDP_ST_OK ? (int8_t)-1 : (int8_t)band_cols((u32)w_prep[i].dt.band);
             w_rows[i] = st != GAMDP_ST_OK ? 0u : (u32)w_prep[i].dt.X;
@@ -1152,6 +1167,11 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
     if ((rc_ = grow(this, d_tasks, cap_tasks, order.size() + 1))) return rc_;
     if ((rc_ = grow(this, d_results, cap_results, n + 1))) return rc_;
     if ((rc_ = grow_staging(n))) return rc_;
+    // (the fingerprints do not fit the record: an array of their own, zeroed for the tasks no wavefront takes, straight to the caller's)
+    if (K::has_ops_fp) {
+        if ((rc_ = grow(this, d_ops_fp, cap_ops_fp, n))) return rc_;
+        HIPCHK(this, hipMemsetAsync(d_ops_fp, 0, n * sizeof(u32), stream));
+    }
     Rec* const d_rec = reinterpret_cast<Rec*>(d_results);
     Rec* const h_rec = reinterpret_cast<Rec*>(h_results);
     parallel_for(order.size(), [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) h_tasks[k] = w_prep[order[k]].dt; });
@@ -1170,12 +1190,14 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
         HIPCHK(this, hipEventRecord(events[li].first, stream));
         typename K::Params p;
         p.tasks = d_tasks + L.first; p.n_tasks = L.count; p.cursor = d_cursor + li; p.results = d_rec;
+        K::set_ops_fp(p, d_ops_fp);
         const int e = launch_kernel(K::family().kernel[cols_index(L.cols)], K::family().threads, p, slots[li], stream);
         if (e != 0) { set_error(std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)e)); return GAMDP_EHIP; }
         HIPCHK(this, hipEventRecord(events[li].second, stream));
     }
     HIPCHK(this, hipMemcpyAsync(h_rec, d_rec, n * sizeof(Rec), hipMemcpyDeviceToHost, stream));
     HIPCHK(this, hipStreamSynchronize(stream));
+    if (K::has_ops_fp) HIPCHK(this, hipMemcpy(ops_fp, d_ops_fp, n * sizeof(u32), hipMemcpyDeviceToHost));
     parallel_for(n, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; i++) {
             if (colsv[i] < 0) continue;   // settled by the pre-checks
@@ -1201,6 +1223,7 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
 
 int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out) { return fill_only<ScoreCall>(tasks, n, out, score_log); }
 int Ctx::carry(const TaskSrc& tasks, size_t n, gamdp_result* out) { return fill_only<CarryCall>(tasks, n, out, carry_log); }
+int Ctx::carry_ops(const TaskSrc& tasks, size_t n, gamdp_result* out, u32* ops_fp) { return fill_only<CarryOpsCall>(tasks, n, out, carry_ops_log, ops_fp); }
 
 // ---- batch pieces -------------------------------------------------------------------------------------
 
@@ -1508,6 +1531,35 @@ int gamdp_task_preflight(uint64_t alen, uint64_t blen, uint32_t band, uint64_t b
     const int st = preflight(alen, blen, band, begin_a, end_a, begin_b, end_b, force_start != 0, force_end != 0, &X, &c);
     if (cells) *cells = c;
     return st;
+}
+
+int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
+                          gamdp_result* out, uint32_t* ops_fp)
+{
+    if (!ctx || !set_a || !set_b || !out || !ops_fp || (n && !tasks)) return GAMDP_EINVAL;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return guarded(c, [&]() -> int {
+        TaskSrc src;   // the caller's array, read in place
+        src.gt = tasks; src.sa = reinterpret_cast<const SeqSet*>(set_a); src.sb = reinterpret_cast<const SeqSet*>(set_b);
+        return c->carry_ops(src, n, out, ops_fp);
+    });
+}
+
+int gamdp_ctx_carry_ops_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n)
+{
+    if (!ctx || (cap && !out)) return GAMDP_EINVAL;
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    if (n) *n = c->carry_ops_log.size();
+    for (size_t i = 0; i < c->carry_ops_log.size() && i < cap; i++) out[i] = c->carry_ops_log[i];
+    return 0;
+}
+
+uint32_t gamdp_ops_fingerprint(const uint8_t* ops, uint64_t n)
+{
+    uint32_t f = 0;
+    if (!ops) return 0;
+    for (uint64_t i = 0; i < n; i++) f = f * GAMDP_OPS_FP_MULT + ((uint32_t)ops[i] + 1u);
+    return f;
 }
 
 unsigned gamdp_build_info(void) { return diag().build ? 1u : 0u; }

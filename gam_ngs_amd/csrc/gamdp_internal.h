@@ -274,7 +274,12 @@ struct Ctx {
     // gamdp_carry_batch (the kernel: gamdp_carry.hip), and what its last call launched (gamdp_ctx_carry_info)
     int carry(const TaskSrc& tasks, size_t n, gamdp_result* out);
     std::vector<gamdp_score_launch_info> carry_log;
-    template <class K> int fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log);   // what the two share (gamdp_host.cpp)
+    // gamdp_carry_ops_batch (the kernel: gamdp_carry_ops.hip), and what its last call launched (gamdp_ctx_carry_ops_info)
+    int carry_ops(const TaskSrc& tasks, size_t n, gamdp_result* out, u32* ops_fp);
+    std::vector<gamdp_score_launch_info> carry_ops_log;
+    u32* d_ops_fp = nullptr; u64 cap_ops_fp = 0;   // its fingerprints, one per task of the batch
+    // what the three share (gamdp_host.cpp); ops_fp: the caller's fingerprint array of a call that has one
+    template <class K> int fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log, u32* ops_fp = nullptr);
     int align(const ITask* tasks, size_t n, gamdp_result* out, const gamdp_ops* ops) { TaskSrc s; s.it = tasks; return align(s, n, out, ops); }
     int align(const std::vector<ITask>& tasks, gamdp_result* out, const gamdp_ops* ops) { return align(tasks.data(), tasks.size(), out, ops); }
     ~Ctx();

@@ -26,6 +26,7 @@ SYMBOLS = [
     "gamdp_ctx_l1_tail_calls", "gamdp_score_batch", "gamdp_ctx_score_info", "gamdp_carry_batch", "gamdp_ctx_carry_info",
     "gamdp_ctx_set_l1_chain", "gamdp_ctx_l1_chain_stats", "gamdp_ctx_set_l1_walk_bands",
     "gamdp_ctx_set_walk_skip", "gamdp_ctx_walk_skip_stats",
+    "gamdp_ops_fingerprint", "gamdp_carry_ops_batch", "gamdp_ctx_carry_ops_info",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
@@ -245,6 +246,12 @@ def load_library():
     lib.gamdp_carry_batch.restype = C.c_int
     lib.gamdp_ctx_carry_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
     lib.gamdp_ctx_carry_info.restype = C.c_int
+    lib.gamdp_ops_fingerprint.argtypes = [C.c_char_p, u64]
+    lib.gamdp_ops_fingerprint.restype = u32
+    lib.gamdp_carry_ops_batch.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(Result), C.POINTER(u32)]
+    lib.gamdp_carry_ops_batch.restype = C.c_int
+    lib.gamdp_ctx_carry_ops_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gamdp_ctx_carry_ops_info.restype = C.c_int
     lib.gamdp_task_preflight.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int, C.POINTER(u64)]
     lib.gamdp_ctx_l1_stats.argtypes = [vp, C.POINTER(L1Stats)]
     lib.gamdp_ctx_set_l1_hits.argtypes = [vp, C.c_int]

@@ -312,6 +312,37 @@ int gamdp_carry_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
  * bands take; the fields as for gamdp_ctx_score_info. */
 int gamdp_ctx_carry_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n);
 
+/* A fingerprint of an edit string over the public alphabet (GAMDP_OP_*), in forward order as gamdp_ops delivers it:
+ *     F(empty) = 0,    F(s . e) = F(s) * GAMDP_OPS_FP_MULT + (e + 1)   (mod 2^32).
+ * A total function of the bytes, on the host, without a context: any byte value e contributes e + 1, and n == 0 or ops == NULL
+ * gives 0.
+ * What it guarantees (the multiplier M is odd, and two ops differ by 0 < |d| <= 3):
+ *   - two strings of equal length that differ in exactly one op differ in F: the difference is d * M^k, which has at most one
+ *     factor of 2 (M^k is odd) and so is not 0 mod 2^32;
+ *   - two strings that differ by swapping two adjacent unequal ops differ in F: the difference is d * (M - 1) * M^k, and
+ *     M - 1 = 2^4 * 0x9E3779B with 0x9E3779B odd, so it has at most five factors of 2 and is not 0 mod 2^32.
+ * Any other pair of different strings collides with probability about 2^-32 per comparison. */
+#define GAMDP_OPS_FP_MULT 0x9E3779B1u
+uint32_t gamdp_ops_fingerprint(const uint8_t* ops, uint64_t n);
+
+/* gamdp_carry_batch with the fingerprint of the edit string: out[i] is exactly what gamdp_carry_batch writes, and ops_fp[i] is
+ * gamdp_ops_fingerprint of the edit string the reference would return for task i -- the bytes gamdp_align_batch delivers through
+ * gamdp_ops -- and 0 for every status other than GAMDP_ST_OK, the cases gamdp_task_preflight settles included.  There is still no
+ * edit string: the forward edit string of a cell is that of the cell the traceback's step leads to plus one op, so the fingerprint
+ * is a sixth field of the summary a cell carries (k_carry_f<C>: no directions, no walk, no scratch arena).
+ * What it is for: two edit strings can agree in begin, length, n_match, first and last match and still differ (a GAP_A / GAP_B
+ * pair taken in the other order); comparing ops_fp[i] with the fingerprint of the bytes gamdp_align_batch returned checks every
+ * op of every string on the device the batch ran on, call by call (tools/score_crosscheck.py --ops).
+ * Refusals as gamdp_carry_batch, with NULL ops_fp among the NULL arguments (GAMDP_EINVAL); n == 0 succeeds; a batch that holds a band
+ * above GAMDP_MAX_TUNED_BAND returns GAMDP_ENOTSUP as a whole (gamdp_last_error names the task; the context stays usable).  The
+ * launches count toward gamdp_ctx_kernel_time; gamdp_ctx_launch_info, gamdp_ctx_score_info and gamdp_ctx_carry_info keep describing
+ * their own calls.  It makes no promise of speed. */
+int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b,
+                          const gamdp_task* tasks, size_t n, gamdp_result* out, uint32_t* ops_fp);
+/* What the last gamdp_carry_ops_batch call on this context launched, in launch order: one launch ("k_carry_f<5>") per instantiation
+ * its bands take; the fields as for gamdp_ctx_score_info. */
+int gamdp_ctx_carry_ops_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n);
+
 /* bit 0: this library is the diagnostics build (-DGAMDP_DIAG; honours the GAMDP_DIAG_* switches that change kernel
  * paths or invalidate results).  The product build returns 0 and ignores those switches. */
 unsigned gamdp_build_info(void);

@@ -17,3 +17,17 @@ int gamdp_multi_align_merge_blocks(gamdp_multi* m, const gamdp_multi_seqset* mas
 /* (a bridge that opts in to GAMDP_WALK_SKIP_DIAG on the contexts of its handle links against these two; there is no context here) */
 int gamdp_ctx_set_walk_skip(gamdp_ctx* ctx, int mode) { (void)ctx; (void)mode; return GAMDP_ENODEV; }
 int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out) { (void)ctx; (void)out; return GAMDP_ENODEV; }
+/* (a bridge that checks the edit strings of its batches links against these three; the fingerprint needs no device and is the real one) */
+int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
+                          gamdp_result* out, uint32_t* ops_fp)
+{ (void)ctx; (void)set_a; (void)set_b; (void)tasks; (void)n; (void)out; (void)ops_fp; return GAMDP_ENODEV; }
+int gamdp_ctx_carry_ops_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n)
+{ (void)ctx; (void)out; (void)cap; if (n) *n = 0; return GAMDP_ENODEV; }
+uint32_t gamdp_ops_fingerprint(const uint8_t* ops, uint64_t n)
+{
+    uint32_t f = 0;
+    uint64_t i;
+    if (!ops) return 0;
+    for (i = 0; i < n; i++) f = f * GAMDP_OPS_FP_MULT + ((uint32_t)ops[i] + 1u);
+    return f;
+}

@@ -12,15 +12,24 @@ carries the summary of the traceback that would start in it), checks the other h
 score, n_match, length, first and last match, homology, status -- and cells must equal gamdp_align_batch's; the line then also holds
 carry_mismatches, carry_kernels, carry_kernel_ms and carry_gcups.  Without the flag the output is what it was.
 
+With --ops the edit strings are checked too.  gamdp_align_batch runs once more with edit strings (one buffer of |a| + |b| + 2 band +
+64 bytes per call, on the device and on the host: what limits the batch), the host fingerprints the bytes it returned
+(gamdp_ops_fingerprint), and gamdp_carry_ops_batch (gam_ngs_amd/csrc/gamdp_carry_ops.hip: the carry kernel with the fingerprint of
+the edit string as a sixth field of a cell's summary) gives the fingerprint of the string the reference would return: both must
+agree call by call, as must every field of the two results.  The line then also holds ops_mismatches, ops_first_mismatch (the call
+and both values), ops_kernels, ops_kernel_ms (k_carry_f), align_ops_kernel_ms (gamdp_align_batch with edit strings; align_kernel_ms
+is the same call without), ops_bytes and ops_gcups.
+
 Workloads:  --pairs N --len L --band B   N synthetic pairs of L bases (SequenceSet.synthetic), whole-sequence windows
             --mixed N                    N calls shaped like the merge-block driver's (tests/_mixed.py), band --band (default 150)
 
 The planner switches of DESIGN.md section 6 apply to gamdp_align_batch as always (read once per process): with
 GAMDP_NO_PAIR=1 GAMDP_QUAD_MIN=1000000000 in the environment it stays on the one-task int32 kernels.
 
-Usage: python tools/score_crosscheck.py --pairs 4096 --len 50000 --band 150 [--carry] [--reps 5] [--first-pair K]
+Usage: python tools/score_crosscheck.py --pairs 4096 --len 50000 --band 150 [--carry] [--ops] [--reps 5] [--first-pair K]
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -43,6 +52,7 @@ def main():
     ap.add_argument("--first-pair", type=int, default=0)
     ap.add_argument("--seed", type=int, default=20261019)
     ap.add_argument("--carry", action="store_true", help="also run gamdp_carry_batch and compare whole results")
+    ap.add_argument("--ops", action="store_true", help="also run gamdp_carry_ops_batch and compare the fingerprints of gamdp_align_batch's edit strings")
     args = ap.parse_args()
     if bool(args.pairs) == bool(args.mixed):
         ap.error("one of --pairs N or --mixed N")
@@ -67,6 +77,18 @@ def main():
     res, sc = (L.Result * n)(), (L.ScoreResult * n)()
     ca = (L.Result * n)() if args.carry else None
     align_ms, score_ms, carry_ms = [], [], []
+    if args.ops:
+        res_o, res_f, fp = (L.Result * n)(), (L.Result * n)(), (C.c_uint32 * n)()
+        caps = [sset.lengths[t.a_id] + sset.lengths[t.b_id] + 2 * t.band + 64 for t in tasks]
+        offs, ops_bytes = [], 0
+        for cap in caps:
+            offs.append(ops_bytes)
+            ops_bytes += cap
+        buf = C.create_string_buffer(max(1, ops_bytes))
+        buf_addr = C.addressof(buf)
+        ops_struct = L.Ops(C.cast(buf, C.c_void_p), (C.c_uint64 * n)(*offs), (C.c_uint64 * n)(*caps))
+    align_ops_ms, ops_ms = [], []
+    ops_mismatches, ops_first_bad = 0, None
     mismatches, first_bad = 0, None
     carry_mismatches, carry_first_bad = 0, None
     whole = lambda r: r.key() + (r.cells,)  # noqa: E731
@@ -82,6 +104,22 @@ def main():
             rc = ctx.lib.gamdp_carry_batch(ctx.handle, sset.handle, sset.handle, tasks, n, ca)
             assert rc == 0, ("gamdp_carry_batch", rc, ctx.last_error())
             c_ms = ctx.kernel_time(reset=True)[0]
+        if args.ops:
+            rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res_o, C.byref(ops_struct))
+            assert rc == 0, ("gamdp_align_batch with edit strings", rc, ctx.last_error())
+            ao_ms = ctx.kernel_time(reset=True)[0]
+            rc = ctx.lib.gamdp_carry_ops_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res_f, fp)
+            assert rc == 0, ("gamdp_carry_ops_batch", rc, ctx.last_error())
+            f_ms = ctx.kernel_time(reset=True)[0]
+            if rep:
+                align_ops_ms.append(ao_ms)
+                ops_ms.append(f_ms)
+            for i in range(n):   # (a status other than OK has no edit string: fingerprint 0 on both sides)
+                host_fp = ctx.lib.gamdp_ops_fingerprint(C.c_char_p(buf_addr + offs[i]), res_o[i].length) if res_o[i].status == 0 else 0
+                if host_fp != fp[i] or whole(res_o[i]) != whole(res_f[i]):
+                    ops_mismatches += 1
+                    if ops_first_bad is None:
+                        ops_first_bad = dict(task=i, align_fp=host_fp, carry_fp=fp[i], align=whole(res_o[i]), carry=whole(res_f[i]))
         if rep:
             align_ms.append(a_ms)
             score_ms.append(s_ms)
@@ -105,9 +143,13 @@ def main():
     if args.carry:
         rec.update(carry_mismatches=carry_mismatches, carry_first_mismatch=carry_first_bad, carry_kernels=[r["kernel"] for r in ctx.carry_info()],
                    carry_kernel_ms=[round(v, 3) for v in carry_ms], carry_gcups=round(cells / med(carry_ms) / 1e6, 1))
+    if args.ops:
+        rec.update(ops_mismatches=ops_mismatches, ops_first_mismatch=ops_first_bad, ops_kernels=[r["kernel"] for r in ctx.carry_ops_info()],
+                   ops_kernel_ms=[round(v, 3) for v in ops_ms], align_ops_kernel_ms=[round(v, 3) for v in align_ops_ms],
+                   ops_bytes=ops_bytes, ops_gcups=round(cells / med(ops_ms) / 1e6, 1))
     print(json.dumps(rec), flush=True)
     sset.close()
-    sys.exit(0 if mismatches == 0 and carry_mismatches == 0 else 1)
+    sys.exit(0 if mismatches == 0 and carry_mismatches == 0 and ops_mismatches == 0 else 1)
 
 
 if __name__ == "__main__":
