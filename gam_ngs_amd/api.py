@@ -134,6 +134,18 @@ class Context:
         self.lib.gamdp_ctx_carry_ops_info(self.handle, arr, n.value, C.byref(n))
         return [arr[i].as_dict() for i in range(n.value)]
 
+    def set_ops_chunk_bytes(self, nbytes: int):
+        """The bytes of edit strings one chunk of find_alignments_with_ops_fingerprints / ops_fingerprint_many may hold on the device
+        (gamdp_ctx_set_ops_chunk_bytes); 0 = the default, 1 GiB.  The results do not depend on it."""
+        _check(self, self.lib.gamdp_ctx_set_ops_chunk_bytes(self.handle, nbytes), "gamdp_ctx_set_ops_chunk_bytes")
+
+    def ops_fp_info(self):
+        """What the last find_alignments_with_ops_fingerprints / ops_fingerprint_many on this context did with k_ops_fp, as a dict
+        (gamdp_ctx_ops_fp_info)."""
+        st = L.OpsFpInfo()
+        _check(self, self.lib.gamdp_ctx_ops_fp_info(self.handle, C.byref(st)), "gamdp_ctx_ops_fp_info")
+        return st.as_dict()
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.gamdp_ctx_destroy(self.handle)
@@ -338,6 +350,14 @@ def task_preflight(alen, blen, band, begin_a, end_a, begin_b, end_b, fs=False, f
     return st, cells.value
 
 
+def task_ops_cap(alen, blen, band, begin_a, end_a, begin_b, end_b, fs=False, fe=False):
+    """An upper bound on the length of the call's edit string, a multiple of 16, or 0 where task_preflight settles the call
+    (gamdp_task_ops_cap)."""
+    m64 = (1 << 64) - 1
+    return int(L.load_library().gamdp_task_ops_cap(alen, blen, band, begin_a & m64, end_a & m64, begin_b & m64, end_b & m64,
+                                                    int(fs), int(fe)))
+
+
 @dataclass(frozen=True)
 class Contig:
     """A view of one sequence of a SequenceSet: optionally reverse-complemented (the reference's
@@ -470,6 +490,22 @@ class BandedSmithWaterman:
         out = (L.Result * n)()
         fp = (C.c_uint32 * n)()
         _check(self.ctx, self.ctx.lib.gamdp_carry_ops_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out, fp), "gamdp_carry_ops_batch")
+        return [MyAlignment.from_result(r, None) for r in out], list(fp)
+
+    def find_alignments_with_ops_fingerprints(self, calls, bands=None):
+        """find_alignments(calls, want_ops=True) with the fingerprint of every edit string in place of the strings
+        (gamdp_align_batch_fp: the strings stay on the device, k_ops_fp folds them there): (results, fingerprints), the results
+        without edit strings (ops None).  fingerprints[i] equals ops_fingerprint(find_alignments(calls, want_ops=True)[i].ops) for a
+        call whose status is OK and is 0 otherwise.  Any band find_alignments takes."""
+        n = len(calls)
+        if n == 0:
+            return [], []
+        if isinstance(self.ctx, MultiContext):
+            raise L.GamdpError("find_alignments_with_ops_fingerprints is a single-context call")
+        tasks, sa, sb = self._tasks(calls, bands)
+        out = (L.Result * n)()
+        fp = (C.c_uint32 * n)()
+        _check(self.ctx, self.ctx.lib.gamdp_align_batch_fp(self.ctx.handle, sa.handle, sb.handle, tasks, n, out, fp), "gamdp_align_batch_fp")
         return [MyAlignment.from_result(r, None) for r in out], list(fp)
 
     def find_alignments(self, calls, want_ops=False, bands=None) -> List[MyAlignment]:
@@ -617,6 +653,24 @@ def ops_fingerprint(ops) -> int:
     else:
         ops = bytes(ops)
     return int(L.load_library().gamdp_ops_fingerprint(ops, len(ops)))
+
+
+def ops_fingerprint_many(ctx: Context, strings) -> List[int]:
+    """gamdp_ops_fingerprint of every string (str over OPS_CHARS, bytes, or sequences of byte values, as ops_fingerprint takes them),
+    computed on the GPU by k_ops_fp's forward instantiation (gamdp_ops_fingerprint_batch): the strings go up back to back."""
+    raw = [bytes(OPS_CHARS.index(ch) for ch in s) if isinstance(s, str) else bytes(s) for s in strings]
+    n = len(raw)
+    if n == 0:
+        return []
+    offs, tot = [], 0
+    for s in raw:
+        offs.append(tot)
+        tot += len(s)
+    buf = b"".join(raw)
+    fp = (C.c_uint32 * n)()
+    _check(ctx, ctx.lib.gamdp_ops_fingerprint_batch(ctx.handle, buf, (C.c_uint64 * n)(*offs), (C.c_uint64 * n)(*[len(s) for s in raw]), n, fp),
+           "gamdp_ops_fingerprint_batch")
+    return list(fp)
 
 
 def encode(s) -> bytes:

@@ -438,6 +438,34 @@ struct CarryOpsParams {
 };
 // (carry_ops_family(): as carry_family())
 
+// ---- fingerprints of edit strings that lie in device memory (k_ops_fp, gamdp_ops_fp.hip; gamdp_align_batch_fp and
+// gamdp_ops_fingerprint_batch) ---------------------------------------------------------------------------------------------------
+// A string is cut into segments of OPS_FP_SEG_BYTES, one wavefront per segment, OPS_FP_LANE_BYTES contiguous bytes per lane; the
+// fingerprint is a polynomial in M = GAMDP_OPS_FP_MULT whose terms commute, so every segment adds its share into fp[idx].
+//   k_ops_fp<false>: the string as the alignment kernels leave it, r[0 .. length) in traceback order at ops + off; length and status
+//     come from results[idx] on the device (length clipped to len, the room the task was given); F = sum (r[k] + 1) M^k.
+//   k_ops_fp<true>:  a string in forward order in bytes [lead, len) of the room at ops + off (len a multiple of OPS_FP_LANE_BYTES:
+//     the string ends where a lane ends, and the `lead` bytes in front of it count nothing); F = sum (s[t] + 1) M^(len - 1 - t).
+// off is a multiple of 16 and the room ends on a multiple of 16: a lane loads 16 bytes at a time, and only where the string still is.
+constexpr u32 OPS_FP_SEG_BYTES = 4096, OPS_FP_LANE_BYTES = 64;
+struct OpsFpTask {
+    u64 off;
+    u32 len, lead;
+    u32 idx;                  // its place in results (k_ops_fp<false>) and in fp
+    u32 pad_;
+};
+struct OpsFpParams {
+    const uint8_t* ops;
+    const OpsFpTask* tasks;
+    const u32* seg_first;     // [n_tasks + 1]: the first segment of every task (ascending; the last entry = n_segs)
+    u32 n_tasks, n_segs;
+    const DevResult* results; // k_ops_fp<false> only
+    u32* fp;                  // zeroed before the launch
+};
+const void* ops_fp_kernel(bool forward);   // k_ops_fp<forward>, workgroups of OPS_FP_THREADS
+const char* ops_fp_kernel_name(bool forward);
+constexpr unsigned OPS_FP_THREADS = 256;
+
 // ---- the main chain of a merge block on carry_task (k_chain_c, gamdp_chain_carry.hip; GAMDP_L1_CHAIN_CARRY) ---------------------
 // One wavefront (a workgroup of 64) per merge block, both orientation attempts one after the other; any band up to 543, the
 // instantiation a band takes is band_cols(band) of chain_carry_family.  The grid is one workgroup per merge block of the launch, in the list's order:

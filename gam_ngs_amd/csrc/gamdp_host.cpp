@@ -337,6 +337,8 @@ Ctx::~Ctx()
     if (d_results) (void)hipFree(d_results);
     if (d_ops) (void)hipFree(d_ops);
     if (d_ops_fp) (void)hipFree(d_ops_fp);
+    if (d_fp_tasks) (void)hipFree(d_fp_tasks);
+    if (d_fp_segs) (void)hipFree(d_fp_segs);
     if (d_cursor) (void)hipFree(d_cursor);
     if (d_chain) (void)hipFree(d_chain);
     if (h_chain) (void)hipHostFree(h_chain);
@@ -464,6 +466,7 @@ struct AlignCall {
     size_t n;
     gamdp_result* out;
     const gamdp_ops* ops;
+    const u64* resident_caps;     // gamdp_align_batch_fp: room per task for edit strings that stay in d_ops (no download, no reversal); else nullptr
     u64 ops_total = 0;            // bytes of edit strings of the batch ...
     std::vector<uint8_t> hops;    // ... as the kernels wrote them
     std::vector<u32> hstats;      // the launches' device statistics (gamdp_ctx_launch_info)
@@ -555,6 +558,14 @@ void Ctx::align_prepare(AlignCall& a)
             prep[i].dt.ops_off = a.ops_total;
             prep[i].dt.ops_cap = a.ops->ops_cap[i];
             a.ops_total += a.ops->ops_cap[i];
+        }
+    } else if (a.resident_caps) {   // ... of every task, in a layout of the library's own: offsets and rooms are multiples of 16
+        for (size_t i = 0; i < n; i++) {
+            if (kidv[i] < 0) continue;
+            prep[i].dt.flags |= TF_WANT_OPS;
+            prep[i].dt.ops_off = a.ops_total;
+            prep[i].dt.ops_cap = a.resident_caps[i];
+            a.ops_total += a.resident_caps[i];
         }
     }
 }
@@ -930,8 +941,8 @@ int Ctx::align_run(AlignCall& a)
         HIPCHK(this, hipStreamWaitEvent(stream, aux_done, 0));
     }
     HIPCHK(this, hipMemcpyAsync(h_results, d_results, a.n * sizeof(DevResult), hipMemcpyDeviceToHost, stream));
-    a.hops.resize(a.ops_total);
-    if (a.ops_total) HIPCHK(this, hipMemcpyAsync(a.hops.data(), d_ops, a.ops_total, hipMemcpyDeviceToHost, stream));
+    a.hops.resize(a.resident_caps ? 0 : a.ops_total);
+    if (a.ops_total && !a.resident_caps) HIPCHK(this, hipMemcpyAsync(a.hops.data(), d_ops, a.ops_total, hipMemcpyDeviceToHost, stream));
     a.hstats.resize(log_launches ? launches.size() * LS_COUNT : 0);
     if (!a.hstats.empty()) HIPCHK(this, hipMemcpyAsync(a.hstats.data(), d_stats, a.hstats.size() * sizeof(u32), hipMemcpyDeviceToHost, stream));
     a.mark("enqueued");
@@ -1006,7 +1017,7 @@ void Ctx::align_collect(AlignCall& a)
             fill_result(hres[i], w_key[i], out[i]);   // (w_key[i] = prep[i].cells, 8 bytes apart instead of 120)
         }
     });
-    if (a.ops_total) {
+    if (a.ops_total && !a.resident_caps) {
         parallel_for(w_plan.n_host_tasks, [&](size_t lo, size_t hi) {
             for (size_t q = lo; q < hi; q++) {
                 const DevTask& d = h_tasks[q];
@@ -1039,13 +1050,13 @@ void Ctx::align_collect(AlignCall& a)
     }
 }
 
-int Ctx::align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_ops* ops)
+int Ctx::align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_ops* ops, const u64* resident_caps)
 {
     if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_EHIP; }
     if (n == 0) return 0;
     int rc_ = align_check(tasks, n);
     if (rc_) return rc_;
-    AlignCall a{tasks, n, out, ops};
+    AlignCall a{tasks, n, out, ops, resident_caps};
     align_prepare(a);
     align_group(a);
     route_merge_n(w_groups, a.rows_of, w_prep, w_kid, n_cu);
@@ -1224,6 +1235,173 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
 int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out) { return fill_only<ScoreCall>(tasks, n, out, score_log); }
 int Ctx::carry(const TaskSrc& tasks, size_t n, gamdp_result* out) { return fill_only<CarryCall>(tasks, n, out, carry_log); }
 int Ctx::carry_ops(const TaskSrc& tasks, size_t n, gamdp_result* out, u32* ops_fp) { return fill_only<CarryOpsCall>(tasks, n, out, carry_ops_log, ops_fp); }
+
+// ---- fingerprints of edit strings on the device: gamdp_align_batch_fp, gamdp_ops_fingerprint_batch (k_ops_fp, gamdp_ops_fp.hip) ----
+
+// An upper bound on gamdp_result.length of one call (0: the pre-checks settle it), rounded up to a multiple of 16; the argument is
+// in include/gamdp.h (gamdp_task_ops_cap)
+static u64 task_ops_cap(u64 alen, u64 blen, u64 band, u64 begin_a, u64 end_a, u64 begin_b, u64 end_b, bool fs, bool fe)
+{
+    u64 X = 0, cells = 0;
+    if (preflight(alen, blen, band, begin_a, end_a, begin_b, end_b, fs, fe, &X, &cells) != GAMDP_ST_OK) return 0;
+    const u64 by_band = X + 2 * band;                              // GAP_B <= 2 band + GAP_A <= 2 band + X
+    const u64 by_view = std::min<u64>(alen, begin_a + X + band);   // diag + GAP_B <= pos of the end cell + 1
+    const u64 bound = X + std::min(by_band, by_view);
+    return (std::max<u64>(bound, 1) + 15) / 16 * 16;
+}
+
+static u64 task_ops_cap(const ITask& t)   // (ids checked by align_check)
+{
+    const u64 alen_full = t.sa->lens[t.a_id], blen_full = t.sb->lens[t.b_id];
+    if (t.a_off > alen_full || t.b_off > blen_full) return 0;   // GAMDP_ST_INVALID (prepare_task)
+    return task_ops_cap(alen_full - t.a_off, blen_full - t.b_off, t.band, t.begin_a, t.end_a, t.begin_b, t.end_b, t.force_start, t.force_end);
+}
+
+int Ctx::ops_fp_launch(const bool forward, const std::vector<OpsFpTask>& tasks, const std::vector<u32>& seg_first, const size_t n_fp, u32* const fp)
+{
+    int rc_ = grow(this, d_ops_fp, cap_ops_fp, n_fp);
+    if (rc_) return rc_;
+    HIPCHK(this, hipMemsetAsync(d_ops_fp, 0, n_fp * sizeof(u32), stream));
+    const u32 n_segs = seg_first.back();
+    if (!tasks.empty() && n_segs) {
+        if ((rc_ = grow(this, d_fp_tasks, cap_fp_tasks, tasks.size()))) return rc_;
+        if ((rc_ = grow(this, d_fp_segs, cap_fp_segs, seg_first.size()))) return rc_;
+        HIPCHK(this, hipMemcpyAsync(d_fp_tasks, tasks.data(), tasks.size() * sizeof(OpsFpTask), hipMemcpyHostToDevice, stream));
+        HIPCHK(this, hipMemcpyAsync(d_fp_segs, seg_first.data(), seg_first.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
+        if (events.empty()) {
+            hipEvent_t e0, e1;
+            HIPCHK(this, hipEventCreate(&e0));
+            HIPCHK(this, hipEventCreate(&e1));
+            events.push_back({e0, e1});
+        }
+        OpsFpParams p;
+        p.ops = d_ops; p.tasks = d_fp_tasks; p.seg_first = d_fp_segs; p.n_tasks = (u32)tasks.size(); p.n_segs = n_segs;
+        p.results = d_results; p.fp = d_ops_fp;
+        // a wavefront per segment, grid-strided: at most eight workgroups per CU
+        const u32 waves_per_group = OPS_FP_THREADS / 64;
+        const u32 grid = (u32)std::min<u64>(((u64)n_segs + waves_per_group - 1) / waves_per_group, (u64)n_cu * 8);
+        HIPCHK(this, hipEventRecord(events[0].first, stream));
+        const int e = launch_kernel(ops_fp_kernel(forward), OPS_FP_THREADS, p, grid, stream);
+        if (e != 0) { set_error(std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)e)); return GAMDP_EHIP; }
+        HIPCHK(this, hipEventRecord(events[0].second, stream));
+    }
+    HIPCHK(this, hipMemcpyAsync(fp, d_ops_fp, n_fp * sizeof(u32), hipMemcpyDeviceToHost, stream));
+    HIPCHK(this, hipStreamSynchronize(stream));
+    if (!tasks.empty() && n_segs) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, events[0].first, events[0].second) == hipSuccess) { kernel_launches++; kernel_ms += ms; last_ops_fp.kernel_ms += ms; }
+        last_ops_fp.tasks += tasks.size(); last_ops_fp.segments += n_segs;
+    }
+    last_ops_fp.chunks++;
+    return 0;
+}
+
+static void ops_fp_info_begin(gamdp_ops_fp_info& r, const bool forward)
+{
+    std::memset(&r, 0, sizeof(r));
+    std::snprintf(r.kernel, sizeof(r.kernel), "%s", ops_fp_kernel_name(forward));
+    r.segment_bytes = OPS_FP_SEG_BYTES; r.lane_bytes = OPS_FP_LANE_BYTES;
+}
+
+// gamdp_align_batch_fp: the batch in chunks of consecutive tasks whose rooms fit the ops budget, every chunk through align() with
+// its edit strings resident, then k_ops_fp<false> over them
+int Ctx::align_fp(const gamdp_task* tasks, const SeqSet* sa, const SeqSet* sb, const size_t n, gamdp_result* out, u32* ops_fp)
+{
+    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_EHIP; }
+    ops_fp_info_begin(last_ops_fp, false);
+    if (n == 0) return 0;
+    TaskSrc all;
+    all.gt = tasks; all.sa = sa; all.sb = sb;
+    int rc_ = align_check(all, n);   // (ids and bands of the whole batch before the first chunk runs)
+    if (rc_) return rc_;
+    std::vector<u64> caps(n);
+    parallel_for(n, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) caps[i] = task_ops_cap(all[i]); });
+    const u64 budget = ops_chunk();
+    std::vector<OpsFpTask> fpt;
+    std::vector<u32> seg_first;
+    for (size_t first = 0; first < n;) {
+        size_t cnt = 0;
+        u64 sum = 0;
+        // (a task whose own room exceeds the budget goes alone; a chunk's results are indexed by 32 bits)
+        while (first + cnt < n && cnt < (1u << 30) && (cnt == 0 || sum + caps[first + cnt] <= budget)) sum += caps[first + cnt++];
+        TaskSrc src;
+        src.gt = tasks + first; src.sa = sa; src.sb = sb;
+        launch_log.clear();
+        last_walk_skip = gamdp_walk_skip_stats{};
+        last_walk_skip.mode = (uint32_t)walk_skip;
+        if ((rc_ = align(src, cnt, out + first, nullptr, caps.data() + first))) return rc_;
+        // the strings of the chunk: where align() put them (w_prep), how long the walks made them (out)
+        fpt.clear(); seg_first.clear();
+        u32 segs = 0;
+        for (size_t i = 0; i < cnt; i++) {
+            if (w_kid[i] < 0) continue;   // settled by the pre-checks: no string, no record on the device
+            const DevTask& d = w_prep[i].dt;
+            const gamdp_result& r = out[first + i];
+            if (r.status == GAMDP_ST_OK && r.length > d.ops_cap) {
+                set_error("gamdp_align_batch_fp: task " + std::to_string(first + i) + " returned an edit string of " + std::to_string(r.length) +
+                          " ops, the bound of gamdp_task_ops_cap (" + std::to_string(d.ops_cap) + ") was violated");
+                return GAMDP_EHIP;
+            }
+            OpsFpTask t;
+            t.off = d.ops_off; t.len = (u32)d.ops_cap; t.lead = 0; t.idx = (u32)i; t.pad_ = 0;
+            fpt.push_back(t);
+            seg_first.push_back(segs);
+            // (a task whose status is not OK keeps one segment: the kernel reads its status and skips it)
+            segs += r.status == GAMDP_ST_OK ? (u32)std::max<u64>(1, (r.length + OPS_FP_SEG_BYTES - 1) / OPS_FP_SEG_BYTES) : 1u;
+            if (r.status == GAMDP_ST_OK) last_ops_fp.bytes += r.length;
+        }
+        seg_first.push_back(segs);
+        if ((rc_ = ops_fp_launch(false, fpt, seg_first, cnt, ops_fp + first))) return rc_;
+        first += cnt;
+    }
+    return 0;
+}
+
+// gamdp_ops_fingerprint_batch: forward-order strings of the caller's, staged so that string i ends where a lane ends
+int Ctx::strings_fp(const uint8_t* ops, const u64* off, const u64* len, const size_t n, u32* fp)
+{
+    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_EHIP; }
+    ops_fp_info_begin(last_ops_fp, true);
+    for (size_t i = 0; i < n; i++) {
+        if (len[i] >= (1ull << 32) - OPS_FP_SEG_BYTES) { set_error("gamdp_ops_fingerprint_batch: string " + std::to_string(i) + " is longer than 2^32 - 4096 bytes"); return GAMDP_EINVAL; }
+        if (len[i] && !ops) { set_error("gamdp_ops_fingerprint_batch: NULL ops"); return GAMDP_EINVAL; }
+    }
+    const u64 budget = ops_chunk();
+    auto room = [&](size_t i) { return (len[i] + OPS_FP_LANE_BYTES - 1) / OPS_FP_LANE_BYTES * OPS_FP_LANE_BYTES; };
+    std::vector<OpsFpTask> fpt;
+    std::vector<u32> seg_first;
+    std::vector<uint8_t> stage;
+    for (size_t first = 0; first < n;) {
+        size_t cnt = 0;
+        u64 sum = 0;
+        while (first + cnt < n && cnt < (1u << 30) && (cnt == 0 || sum + room(first + cnt) <= budget)) sum += room(first + cnt++);
+        fpt.clear(); seg_first.clear();
+        stage.assign(sum, 0);
+        u64 at = 0;
+        u64 segs = 0;
+        for (size_t i = 0; i < cnt; i++) {
+            const u64 l = len[first + i], r = room(first + i);
+            if (l == 0) continue;   // (its fingerprint is the 0 the array is set to)
+            OpsFpTask t;
+            t.off = at; t.len = (u32)r; t.lead = (u32)(r - l); t.idx = (u32)i; t.pad_ = 0;
+            std::memcpy(stage.data() + at + t.lead, ops + off[first + i], l);
+            fpt.push_back(t);
+            seg_first.push_back((u32)segs);
+            segs += (r + OPS_FP_SEG_BYTES - 1) / OPS_FP_SEG_BYTES;
+            at += r;
+            last_ops_fp.bytes += l;
+        }
+        seg_first.push_back((u32)segs);
+        int rc_ = 0;
+        if (sum) {
+            if ((rc_ = grow(this, d_ops, cap_ops, sum))) return rc_;
+            HIPCHK(this, hipMemcpyAsync(d_ops, stage.data(), sum, hipMemcpyHostToDevice, stream));
+        }
+        if ((rc_ = ops_fp_launch(true, fpt, seg_first, cnt, fp + first))) return rc_;
+        first += cnt;
+    }
+    return 0;
+}
 
 // ---- batch pieces -------------------------------------------------------------------------------------
 
@@ -1551,6 +1729,53 @@ int gamdp_ctx_carry_ops_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out,
     const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
     if (n) *n = c->carry_ops_log.size();
     for (size_t i = 0; i < c->carry_ops_log.size() && i < cap; i++) out[i] = c->carry_ops_log[i];
+    return 0;
+}
+
+uint64_t gamdp_task_ops_cap(uint64_t alen, uint64_t blen, uint32_t band, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,
+                            uint64_t end_b, int force_start, int force_end)
+{
+    return task_ops_cap(alen, blen, band, begin_a, end_a, begin_b, end_b, force_start != 0, force_end != 0);
+}
+
+int gamdp_ctx_set_ops_chunk_bytes(gamdp_ctx* ctx, uint64_t bytes)
+{
+    if (!ctx) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->ops_chunk_bytes = bytes;   // 0 = back to the default
+    return 0;
+}
+
+int gamdp_align_batch_fp(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
+                         gamdp_result* out, uint32_t* ops_fp)
+{
+    if (!ctx || !set_a || !set_b || !out || !ops_fp || (n && !tasks)) return GAMDP_EINVAL;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    c->launch_log.clear();
+    c->last_walk_skip = gamdp_walk_skip_stats{};
+    c->last_walk_skip.mode = (uint32_t)c->walk_skip;
+    struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; } } log_guard{c};
+    c->log_launches = true; c->log_piece = 0;
+    return guarded(c, [&]() -> int {
+        if (c->arena_budget(true) == 0) { c->set_error("hipMemGetInfo failed"); return GAMDP_EHIP; }
+        return c->align_fp(tasks, reinterpret_cast<const SeqSet*>(set_a), reinterpret_cast<const SeqSet*>(set_b), n, out, ops_fp);
+    });
+}
+
+int gamdp_ops_fingerprint_batch(gamdp_ctx* ctx, const uint8_t* ops, const uint64_t* off, const uint64_t* len, size_t n, uint32_t* fp)
+{
+    if (!ctx || !fp || (n && (!off || !len))) return GAMDP_EINVAL;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return guarded(c, [&]() -> int { return c->strings_fp(ops, off, len, n, fp); });
+}
+
+static_assert(sizeof(gamdp_ops_fp_info) == 72 && offsetof(gamdp_ops_fp_info, tasks) == 32 && offsetof(gamdp_ops_fp_info, kernel_ms) == 64,
+              "gamdp_ops_fp_info: the layout include/gamdp.h documents (gam_ngs_amd/lib.py OpsFpInfo mirrors it)");
+
+int gamdp_ctx_ops_fp_info(const gamdp_ctx* ctx, gamdp_ops_fp_info* out)
+{
+    if (!ctx || !out) return GAMDP_EINVAL;
+    *out = reinterpret_cast<const Ctx*>(ctx)->last_ops_fp;
+    out->segment_bytes = OPS_FP_SEG_BYTES; out->lane_bytes = OPS_FP_LANE_BYTES;   // (before the first call too: the rest is 0 then)
     return 0;
 }
 

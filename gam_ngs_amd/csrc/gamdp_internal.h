@@ -257,7 +257,9 @@ struct Ctx {
     uint8_t* h_mirror = nullptr; u64 cap_mirror = 0;
     u32 chain_epoch = 0;
 
-    int align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_ops* ops);
+    // resident_caps (gamdp_align_batch_fp): an edit string for every task, left in d_ops in traceback order, task i in a room of
+    // resident_caps[i] bytes (a multiple of 16) behind the rooms of the tasks before it; nothing of them is downloaded
+    int align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_ops* ops, const u64* resident_caps = nullptr);
     // the steps of align(), in the order they run (gamdp_host.cpp)
     int align_check(const TaskSrc& tasks, size_t n);
     void align_prepare(AlignCall& a);
@@ -278,6 +280,17 @@ struct Ctx {
     int carry_ops(const TaskSrc& tasks, size_t n, gamdp_result* out, u32* ops_fp);
     std::vector<gamdp_score_launch_info> carry_ops_log;
     u32* d_ops_fp = nullptr; u64 cap_ops_fp = 0;   // its fingerprints, one per task of the batch
+    // gamdp_align_batch_fp / gamdp_ops_fingerprint_batch (the kernel: gamdp_ops_fp.hip): fingerprints of strings that lie in d_ops, a
+    // batch in chunks of at most ops_chunk() bytes of d_ops (gamdp_ctx_set_ops_chunk_bytes), and what the last call of either did
+    u64 ops_chunk_bytes = 0;   // 0: the default
+    u64 ops_chunk() const { return ops_chunk_bytes ? std::min<u64>(ops_chunk_bytes, 1ull << 40) : (1ull << 30); }
+    OpsFpTask* d_fp_tasks = nullptr; u64 cap_fp_tasks = 0;
+    u32* d_fp_segs = nullptr; u64 cap_fp_segs = 0;
+    gamdp_ops_fp_info last_ops_fp{};
+    int align_fp(const gamdp_task* tasks, const SeqSet* sa, const SeqSet* sb, size_t n, gamdp_result* out, u32* ops_fp);
+    int strings_fp(const uint8_t* ops, const u64* off, const u64* len, size_t n, u32* fp);
+    // one launch of k_ops_fp<forward> over `tasks` (strings in d_ops; seg_first as OpsFpParams) and the download of fp[0 .. n_fp)
+    int ops_fp_launch(bool forward, const std::vector<OpsFpTask>& tasks, const std::vector<u32>& seg_first, size_t n_fp, u32* fp);
     // what the three share (gamdp_host.cpp); ops_fp: the caller's fingerprint array of a call that has one
     template <class K> int fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log, u32* ops_fp = nullptr);
     int align(const ITask* tasks, size_t n, gamdp_result* out, const gamdp_ops* ops) { TaskSrc s; s.it = tasks; return align(s, n, out, ops); }

@@ -27,6 +27,8 @@ SYMBOLS = [
     "gamdp_ctx_set_l1_chain", "gamdp_ctx_l1_chain_stats", "gamdp_ctx_set_l1_walk_bands",
     "gamdp_ctx_set_walk_skip", "gamdp_ctx_walk_skip_stats",
     "gamdp_ops_fingerprint", "gamdp_carry_ops_batch", "gamdp_ctx_carry_ops_info",
+    "gamdp_task_ops_cap", "gamdp_align_batch_fp", "gamdp_ctx_set_ops_chunk_bytes", "gamdp_ops_fingerprint_batch",
+    "gamdp_ctx_ops_fp_info",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
@@ -74,6 +76,19 @@ class ScoreLaunchInfo(C.Structure):
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = d["kernel"].decode()
+        return d
+
+
+class OpsFpInfo(C.Structure):
+    """gamdp_ops_fp_info: what the last gamdp_align_batch_fp / gamdp_ops_fingerprint_batch did with k_ops_fp (static_assert in
+    gamdp_host.cpp)."""
+    _fields_ = [("kernel", C.c_char * 24), ("segment_bytes", C.c_uint32), ("lane_bytes", C.c_uint32), ("tasks", C.c_uint64),
+                ("segments", C.c_uint64), ("bytes", C.c_uint64), ("chunks", C.c_uint32), ("pad_", C.c_uint32),
+                ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
         d["kernel"] = d["kernel"].decode()
         return d
 
@@ -252,6 +267,17 @@ def load_library():
     lib.gamdp_carry_ops_batch.restype = C.c_int
     lib.gamdp_ctx_carry_ops_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
     lib.gamdp_ctx_carry_ops_info.restype = C.c_int
+    if hasattr(lib, "gamdp_align_batch_fp"):   # (as gamdp_ctx_set_walk_skip below: older builds through GAMDP_LIB)
+        lib.gamdp_task_ops_cap.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int]
+        lib.gamdp_task_ops_cap.restype = u64
+        lib.gamdp_align_batch_fp.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(Result), C.POINTER(u32)]
+        lib.gamdp_align_batch_fp.restype = C.c_int
+        lib.gamdp_ctx_set_ops_chunk_bytes.argtypes = [vp, u64]
+        lib.gamdp_ctx_set_ops_chunk_bytes.restype = C.c_int
+        lib.gamdp_ops_fingerprint_batch.argtypes = [vp, C.c_char_p, C.POINTER(u64), C.POINTER(u64), C.c_size_t, C.POINTER(u32)]
+        lib.gamdp_ops_fingerprint_batch.restype = C.c_int
+        lib.gamdp_ctx_ops_fp_info.argtypes = [vp, C.POINTER(OpsFpInfo)]
+        lib.gamdp_ctx_ops_fp_info.restype = C.c_int
     lib.gamdp_task_preflight.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int, C.POINTER(u64)]
     lib.gamdp_ctx_l1_stats.argtypes = [vp, C.POINTER(L1Stats)]
     lib.gamdp_ctx_set_l1_hits.argtypes = [vp, C.c_int]

@@ -343,6 +343,70 @@ int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp
  * its bands take; the fields as for gamdp_ctx_score_info. */
 int gamdp_ctx_carry_ops_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n);
 
+/* An upper bound on gamdp_result.length of one find_alignment call, on plain numbers (the arguments of gamdp_task_preflight; host
+ * only, no context): 0 for a call the pre-checks settle, otherwise a multiple of 16 (the bound rounded up; at least 16).
+ * The argument, against the traceback loop of banded_smith_waterman.cc:227-311.  Let X = x_size (:93-95, what the pre-checks size)
+ * and y_size = 2 band + 1.  The loop starts at x = max_i <= X - 1, y = max_j <= 2 band, pos = begin_a + x + y - band, runs while
+ * x >= 0, y >= 0 and pos >= 0, and every pass emits one op and takes one of three steps, in the pos == 0 branch (:229-262) as in
+ * the general one (:263-308):
+ *   diag   (MATCH / MISMATCH, :237-250, :272-285)   x--          : x and pos fall by one;
+ *   GAP_A  (:256-261, :286-291, :297-302)           x--, y++     : x falls by one, pos stays;
+ *   GAP_B  (:251-255, :292-296, :303-307)           y--          : pos falls by one, x stays.
+ * GAP_A is taken only where y < y_size - 1 (:251 tests y == y_size - 1 first; :286 and :297 require it), so y never exceeds 2 band.
+ * Row 0 is no exception: a diag or GAP_A step from x == 0 leaves x == -1 and ends the loop, a GAP_B step there lowers y and pos as
+ * anywhere; nor is pos == 0, where a diag or GAP_B step leaves pos == -1 and ends the loop and GAP_A lowers x.  Hence
+ *   #diag + #GAP_A <= max_i + 1 <= X                 (x falls from max_i to -1 at most),
+ *   #GAP_B         <= max_j + #GAP_A <= 2 band + X   (y rises only by GAP_A and ends the loop below 0),
+ *   #diag + #GAP_B <= pos(end cell) + 1 <= min(|a|, begin_a + X + band)   (a result with status OK read a.at(pos) at its end cell),
+ * and length = #diag + #GAP_A + #GAP_B <= X + min(X + 2 band, |a|, begin_a + X + band) <= 2 X + 2 band.  X <= 500 000 and
+ * band <= GAMDP_MAX_BAND keep the bound below 2^22 + 2^21. */
+uint64_t gamdp_task_ops_cap(uint64_t alen, uint64_t blen, uint32_t band, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,
+                            uint64_t end_b, int force_start, int force_end);
+
+/* gamdp_align_batch with an edit string requested for every task, and the fingerprint of each in place of the strings: out[i] is
+ * exactly what gamdp_align_batch writes for such a call, ops_fp[i] is gamdp_ops_fingerprint of the bytes it would deliver through
+ * gamdp_ops, and 0 for every status other than GAMDP_ST_OK, the cases gamdp_task_preflight settles included.  The strings never
+ * leave the device: the library lays them out itself (task i in a room of gamdp_task_ops_cap bytes at a 16-byte aligned offset),
+ * runs the ordinary alignment launches, leaves the strings where the walks wrote them -- in traceback order, which is the order the
+ * fingerprint's polynomial wants -- and folds them with k_ops_fp (segments of 4 096 bytes, one wavefront each) on the context's
+ * stream; n x 4 bytes come back.  A batch goes in chunks of consecutive tasks whose rooms sum to at most the context's ops budget
+ * (gamdp_ctx_set_ops_chunk_bytes: 1 GiB by default; a task whose own room exceeds it goes alone).
+ * Which walk this checks: a task that wants an edit string takes the one-task walk of its kernel (every step one at a time, the
+ * multi-task kernels included), so the fingerprints check that walk and everything it reads -- strips, re-created directions, side
+ * captures -- against gamdp_carry_ops_batch, op by op, at any batch size (tools/score_crosscheck.py --ops --device-fp); the result
+ * fields of the multi-task walks are what gamdp_carry_batch checks.  It is also the fingerprint for bands above
+ * GAMDP_MAX_TUNED_BAND: there is no band refusal, anything gamdp_align_batch takes is taken.
+ * GAMDP_EINVAL for NULL ctx / sets / out / ops_fp and NULL tasks with n > 0, before anything is touched; n == 0 succeeds; ids out of
+ * range and reverse complements of a packed-only set are refused as gamdp_align_batch refuses them.  Should a task come back with
+ * length above its room (the bound of gamdp_task_ops_cap violated), the call fails with GAMDP_EHIP and gamdp_last_error names the
+ * task: never a fingerprint of a truncated string.  gamdp_ctx_launch_info describes the alignment launches of the last chunk;
+ * every launch counts toward gamdp_ctx_kernel_time. */
+int gamdp_align_batch_fp(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
+                         gamdp_result* out, uint32_t* ops_fp);
+/* The ops budget of gamdp_align_batch_fp and gamdp_ops_fingerprint_batch: the bytes of edit strings one chunk may hold on the device;
+ * 0 = the default (1 GiB).  A property of the context like gamdp_ctx_set_arena_bytes.  GAMDP_EINVAL for a NULL ctx. */
+int gamdp_ctx_set_ops_chunk_bytes(gamdp_ctx* ctx, uint64_t bytes);
+
+/* fp[i] = gamdp_ops_fingerprint(ops + off[i], len[i]) for n strings in forward order in a host buffer, at any offsets, of any
+ * bytes: staged into the aligned layout on upload, in chunks of the same budget, and folded by k_ops_fp's forward instantiation.
+ * The kernel on its own.  GAMDP_EINVAL for NULL ctx / fp, NULL off / len with n > 0, NULL ops with a string that is not empty, and a
+ * string of 2^32 - 4 096 bytes or more; n == 0 succeeds. */
+int gamdp_ops_fingerprint_batch(gamdp_ctx* ctx, const uint8_t* ops, const uint64_t* off, const uint64_t* len, size_t n, uint32_t* fp);
+
+/* What the last gamdp_align_batch_fp or gamdp_ops_fingerprint_batch call on this context did with k_ops_fp, summed over its chunks. */
+typedef struct gamdp_ops_fp_info {
+    char kernel[24];          /* "k_ops_fp<false>" (traceback order: gamdp_align_batch_fp) or "k_ops_fp<true>" (forward order) */
+    uint32_t segment_bytes;   /* bytes of a string one wavefront folds */
+    uint32_t lane_bytes;      /* ... and one lane of it */
+    uint64_t tasks;           /* strings handed to the kernel (empty strings and calls the pre-checks settle are not) */
+    uint64_t segments;        /* wavefront units */
+    uint64_t bytes;           /* bytes of strings folded */
+    uint32_t chunks;          /* chunks the batch went in */
+    uint32_t pad_;
+    double kernel_ms;         /* HIP events around the k_ops_fp launches */
+} gamdp_ops_fp_info;          /* 72 bytes */
+int gamdp_ctx_ops_fp_info(const gamdp_ctx* ctx, gamdp_ops_fp_info* out);   /* GAMDP_EINVAL for NULL ctx / out */
+
 /* bit 0: this library is the diagnostics build (-DGAMDP_DIAG; honours the GAMDP_DIAG_* switches that change kernel
  * paths or invalidate results).  The product build returns 0 and ignores those switches. */
 unsigned gamdp_build_info(void);

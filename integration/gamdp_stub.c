@@ -23,6 +23,46 @@ int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp
 { (void)ctx; (void)set_a; (void)set_b; (void)tasks; (void)n; (void)out; (void)ops_fp; return GAMDP_ENODEV; }
 int gamdp_ctx_carry_ops_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n)
 { (void)ctx; (void)out; (void)cap; if (n) *n = 0; return GAMDP_ENODEV; }
+/* (a bridge that takes the fingerprints of its batches' edit strings from the device links against these five; the bound on an edit
+ * string's length needs no device and is the real one: the pre-checks of banded_smith_waterman.cc:90-132 as gamdp_task_preflight
+ * makes them, then X + min(X + 2 band, |a|, begin_a + X + band) rounded up to 16 -- tests/test_ops_fp_cabi.py compares the two) */
+int gamdp_align_batch_fp(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
+                         gamdp_result* out, uint32_t* ops_fp)
+{ (void)n; if (!ctx || !set_a || !set_b || !out || !ops_fp || (n && !tasks)) return GAMDP_EINVAL; return GAMDP_ENODEV; }
+int gamdp_ctx_set_ops_chunk_bytes(gamdp_ctx* ctx, uint64_t bytes) { (void)bytes; return ctx ? GAMDP_ENODEV : GAMDP_EINVAL; }
+int gamdp_ops_fingerprint_batch(gamdp_ctx* ctx, const uint8_t* ops, const uint64_t* off, const uint64_t* len, size_t n, uint32_t* fp)
+{ (void)ops; if (!ctx || !fp || (n && (!off || !len))) return GAMDP_EINVAL; return GAMDP_ENODEV; }
+int gamdp_ctx_ops_fp_info(const gamdp_ctx* ctx, gamdp_ops_fp_info* out) { return (!ctx || !out) ? GAMDP_EINVAL : GAMDP_ENODEV; }
+uint64_t gamdp_task_ops_cap(uint64_t alen, uint64_t blen, uint32_t band32, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,
+                            uint64_t end_b, int force_start, int force_end)
+{
+    const uint64_t band = band32;
+    const int64_t maxgap = 10;   /* FORCE_MAXGAP_LEN */
+    int64_t lo, hi, up;
+    uint64_t X, lim, by_band, by_view, bound;
+    (void)force_end;             /* (it moves the end cell, not the bound) */
+    if (end_b < begin_b) return 0;                                   /* :90, EMPTY */
+    if (begin_a >= (1ull << 31) - 65536) return 0;                   /* INVALID */
+    if (begin_b >= blen) return 0;                                   /* OUT_OF_RANGE or INVALID */
+    if (end_b >= blen) end_b = blen - 1;                             /* :91 */
+    X = end_b - begin_b + 1;                                         /* :93-95 */
+    lim = alen + band - begin_a;
+    if (lim < X) X = lim;
+    if (X > 500000) X = 500000;
+    if (X == 0) return 0;                                            /* INVALID */
+    lo = (int64_t)begin_a - (int64_t)band > 0 ? (int64_t)begin_a - (int64_t)band : 0;
+    hi = (int64_t)begin_a + (int64_t)band;
+    if (force_start) {                                               /* row 0 reads a.at(pos) for 0 <= pos <= 10 in the band (:116) */
+        up = hi < maxgap ? hi : maxgap;
+        if (lo <= up && up >= (int64_t)alen) return 0;               /* OUT_OF_RANGE */
+    }
+    if (begin_a > alen + band) return 0;                             /* every cell beyond |a|: OUT_OF_RANGE or EMPTY */
+    by_band = X + 2 * band;
+    by_view = begin_a + X + band < alen ? begin_a + X + band : alen;
+    bound = X + (by_band < by_view ? by_band : by_view);
+    if (bound == 0) bound = 1;
+    return (bound + 15) / 16 * 16;
+}
 uint32_t gamdp_ops_fingerprint(const uint8_t* ops, uint64_t n)
 {
     uint32_t f = 0;

@@ -20,19 +20,29 @@ agree call by call, as must every field of the two results.  The line then also 
 and both values), ops_kernels, ops_kernel_ms (k_carry_f), align_ops_kernel_ms (gamdp_align_batch with edit strings; align_kernel_ms
 is the same call without), ops_bytes and ops_gcups.
 
+With --ops --device-fp the align side's fingerprints come from gamdp_align_batch_fp instead: the edit strings stay on the device, in
+rooms of gamdp_task_ops_cap bytes, k_ops_fp (gam_ngs_amd/csrc/gamdp_ops_fp.hip) folds them there and 4 bytes per call come back, the
+batch in chunks of the context's ops budget (--ops-chunk-bytes; 1 GiB by default) -- so no buffer of the batch's edit strings exists
+anywhere and the batch may be of any size.  The line then also holds device_fp_mismatches (against gamdp_carry_ops_batch, as
+ops_mismatches), align_fp_kernel_ms (all launches of the call), ops_fp_kernel_ms (k_ops_fp alone), ops_fp_info (gamdp_ctx_ops_fp_info
+of the last repetition), align_fp_wall_ms (the whole call) and align_fp_bytes_to_host.  --host-fp-too runs the download path of plain
+--ops beside it in every repetition, the two alternating (align_ops_wall_ms: the call, the reversal inside it and the host's
+fingerprints; align_ops_bytes_to_host), for measurements of one against the other in one process.
+
 Workloads:  --pairs N --len L --band B   N synthetic pairs of L bases (SequenceSet.synthetic), whole-sequence windows
             --mixed N                    N calls shaped like the merge-block driver's (tests/_mixed.py), band --band (default 150)
 
 The planner switches of DESIGN.md section 6 apply to gamdp_align_batch as always (read once per process): with
 GAMDP_NO_PAIR=1 GAMDP_QUAD_MIN=1000000000 in the environment it stays on the one-task int32 kernels.
 
-Usage: python tools/score_crosscheck.py --pairs 4096 --len 50000 --band 150 [--carry] [--ops] [--reps 5] [--first-pair K]
+Usage: python tools/score_crosscheck.py --pairs 4096 --len 50000 --band 150 [--carry] [--ops [--device-fp [--host-fp-too]]] [--reps 5] [--first-pair K]
 """
 import argparse
 import ctypes as C
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -53,7 +63,12 @@ def main():
     ap.add_argument("--seed", type=int, default=20261019)
     ap.add_argument("--carry", action="store_true", help="also run gamdp_carry_batch and compare whole results")
     ap.add_argument("--ops", action="store_true", help="also run gamdp_carry_ops_batch and compare the fingerprints of gamdp_align_batch's edit strings")
+    ap.add_argument("--device-fp", action="store_true", help="with --ops: the align side's fingerprints from gamdp_align_batch_fp (the strings stay on the device)")
+    ap.add_argument("--host-fp-too", action="store_true", help="with --ops --device-fp: also the download path of plain --ops, alternating with it")
+    ap.add_argument("--ops-chunk-bytes", type=int, default=0, help="gamdp_ctx_set_ops_chunk_bytes (0: the default, 1 GiB)")
     args = ap.parse_args()
+    if (args.device_fp and not args.ops) or (args.host_fp_too and not args.device_fp):
+        ap.error("--device-fp goes with --ops, --host-fp-too with --device-fp")
     if bool(args.pairs) == bool(args.mixed):
         ap.error("one of --pairs N or --mixed N")
     ctx = gam.Context(0)
@@ -77,8 +92,16 @@ def main():
     res, sc = (L.Result * n)(), (L.ScoreResult * n)()
     ca = (L.Result * n)() if args.carry else None
     align_ms, score_ms, carry_ms = [], [], []
+    host_fp_path = args.ops and (not args.device_fp or args.host_fp_too)
     if args.ops:
         res_o, res_f, fp = (L.Result * n)(), (L.Result * n)(), (C.c_uint32 * n)()
+        ops_bytes = 0
+    if args.device_fp:
+        res_d, fp_d = (L.Result * n)(), (C.c_uint32 * n)()
+        ctx.set_ops_chunk_bytes(args.ops_chunk_bytes)
+    dev_ms, dev_fp_ms, dev_wall_ms, host_wall_ms = [], [], [], []
+    dev_mismatches, dev_first_bad, fp_info = 0, None, None
+    if host_fp_path:
         caps = [sset.lengths[t.a_id] + sset.lengths[t.b_id] + 2 * t.band + 64 for t in tasks]
         offs, ops_bytes = [], 0
         for cap in caps:
@@ -105,21 +128,42 @@ def main():
             assert rc == 0, ("gamdp_carry_batch", rc, ctx.last_error())
             c_ms = ctx.kernel_time(reset=True)[0]
         if args.ops:
-            rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res_o, C.byref(ops_struct))
-            assert rc == 0, ("gamdp_align_batch with edit strings", rc, ctx.last_error())
-            ao_ms = ctx.kernel_time(reset=True)[0]
             rc = ctx.lib.gamdp_carry_ops_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res_f, fp)
             assert rc == 0, ("gamdp_carry_ops_batch", rc, ctx.last_error())
             f_ms = ctx.kernel_time(reset=True)[0]
             if rep:
-                align_ops_ms.append(ao_ms)
                 ops_ms.append(f_ms)
+        if host_fp_path:
+            t0 = time.perf_counter()
+            rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res_o, C.byref(ops_struct))
+            assert rc == 0, ("gamdp_align_batch with edit strings", rc, ctx.last_error())
+            host_fps = [ctx.lib.gamdp_ops_fingerprint(C.c_char_p(buf_addr + offs[i]), res_o[i].length) if res_o[i].status == 0 else 0 for i in range(n)]
+            wall = (time.perf_counter() - t0) * 1e3
+            ao_ms = ctx.kernel_time(reset=True)[0]
+            if rep:
+                align_ops_ms.append(ao_ms)
+                host_wall_ms.append(wall)
             for i in range(n):   # (a status other than OK has no edit string: fingerprint 0 on both sides)
-                host_fp = ctx.lib.gamdp_ops_fingerprint(C.c_char_p(buf_addr + offs[i]), res_o[i].length) if res_o[i].status == 0 else 0
-                if host_fp != fp[i] or whole(res_o[i]) != whole(res_f[i]):
+                if host_fps[i] != fp[i] or whole(res_o[i]) != whole(res_f[i]):
                     ops_mismatches += 1
                     if ops_first_bad is None:
-                        ops_first_bad = dict(task=i, align_fp=host_fp, carry_fp=fp[i], align=whole(res_o[i]), carry=whole(res_f[i]))
+                        ops_first_bad = dict(task=i, align_fp=host_fps[i], carry_fp=fp[i], align=whole(res_o[i]), carry=whole(res_f[i]))
+        if args.device_fp:
+            t0 = time.perf_counter()
+            rc = ctx.lib.gamdp_align_batch_fp(ctx.handle, sset.handle, sset.handle, tasks, n, res_d, fp_d)
+            wall = (time.perf_counter() - t0) * 1e3
+            assert rc == 0, ("gamdp_align_batch_fp", rc, ctx.last_error())
+            d_ms = ctx.kernel_time(reset=True)[0]
+            fp_info = ctx.ops_fp_info()
+            if rep:
+                dev_ms.append(d_ms)
+                dev_fp_ms.append(fp_info["kernel_ms"])
+                dev_wall_ms.append(wall)
+            for i in range(n):
+                if fp_d[i] != fp[i] or whole(res_d[i]) != whole(res_f[i]):
+                    dev_mismatches += 1
+                    if dev_first_bad is None:
+                        dev_first_bad = dict(task=i, align_fp=fp_d[i], carry_fp=fp[i], align=whole(res_d[i]), carry=whole(res_f[i]))
         if rep:
             align_ms.append(a_ms)
             score_ms.append(s_ms)
@@ -147,9 +191,16 @@ def main():
         rec.update(ops_mismatches=ops_mismatches, ops_first_mismatch=ops_first_bad, ops_kernels=[r["kernel"] for r in ctx.carry_ops_info()],
                    ops_kernel_ms=[round(v, 3) for v in ops_ms], align_ops_kernel_ms=[round(v, 3) for v in align_ops_ms],
                    ops_bytes=ops_bytes, ops_gcups=round(cells / med(ops_ms) / 1e6, 1))
+    if host_fp_path and args.device_fp:
+        rec.update(align_ops_wall_ms=[round(v, 2) for v in host_wall_ms], align_ops_bytes_to_host=ops_bytes + 40 * n)
+    if args.device_fp:
+        gbs = fp_info["bytes"] / (med(dev_fp_ms) * 1e6) if med(dev_fp_ms) > 0 else None
+        rec.update(device_fp_mismatches=dev_mismatches, device_fp_first_mismatch=dev_first_bad, align_fp_kernel_ms=[round(v, 3) for v in dev_ms],
+                   ops_fp_kernel_ms=[round(v, 4) for v in dev_fp_ms], ops_fp_info=fp_info, ops_fp_gb_per_s=round(gbs, 1) if gbs else None,
+                   align_fp_wall_ms=[round(v, 2) for v in dev_wall_ms], align_fp_bytes_to_host=44 * n)
     print(json.dumps(rec), flush=True)
     sset.close()
-    sys.exit(0 if mismatches == 0 and carry_mismatches == 0 and ops_mismatches == 0 else 1)
+    sys.exit(0 if mismatches == 0 and carry_mismatches == 0 and ops_mismatches == 0 and dev_mismatches == 0 else 1)
 
 
 if __name__ == "__main__":
