@@ -358,6 +358,14 @@ def task_ops_cap(alen, blen, band, begin_a, end_a, begin_b, end_b, fs=False, fe=
                                                     int(fs), int(fe)))
 
 
+def task_live_columns(alen, blen, band, begin_a, end_a, begin_b, end_b, fs=False, fe=False):
+    """The largest number of cells inside a (0 <= begin_a - band + i + j < alen) in one row of the call's band matrix, or 0 where
+    task_preflight settles the call (gamdp_task_live_columns): the entries per step a fill over the live cells alone needs."""
+    m64 = (1 << 64) - 1
+    return int(L.load_library().gamdp_task_live_columns(alen, blen, band, begin_a & m64, end_a & m64, begin_b & m64, end_b & m64,
+                                                         int(fs), int(fe)))
+
+
 @dataclass(frozen=True)
 class Contig:
     """A view of one sequence of a SequenceSet: optionally reverse-complemented (the reference's

@@ -438,6 +438,24 @@ struct CarryOpsParams {
 };
 // (carry_ops_family(): as carry_family())
 
+// ---- the live width of a call (gamdp_task_live_columns, include/gamdp.h) -------------------------------------------------------
+// The largest number of live cells (0 <= pos = begin_a - band + i + j < alen) in one row i < X, 0 <= j <= 2 band, of a call the
+// pre-checks let through (X = its rows).  Row i holds min(2 band, alen - 1 - A0 - i) + min(0, A0 + i) + 1 of them, A0 = begin_a -
+// band: concave in i, rising while i < min(-A0, alen - 1 - A0 - 2 band), level up to the larger of the two, falling behind it.  So
+// the maximum over [0, X) is at that point, clamped into the range.
+GAMDP_HD inline u64 live_columns_hd(u64 alen, u64 band, u64 begin_a, u64 X)
+{
+    if (X == 0 || alen == 0) return 0;
+    if (alen > (1ull << 62)) alen = 1ull << 62;   // (keeps the signed arithmetic below in range; the result is at most 2 band + 1)
+    const int64_t A0 = (int64_t)begin_a - (int64_t)band, last = (int64_t)alen - 1 - A0;
+    int64_t i = -A0 < last - 2 * (int64_t)band ? -A0 : last - 2 * (int64_t)band;
+    if (i < 0) i = 0;
+    if (i > (int64_t)X - 1) i = (int64_t)X - 1;
+    const int64_t right = 2 * (int64_t)band < last - i ? 2 * (int64_t)band : last - i, left = A0 + i < 0 ? A0 + i : 0;
+    const int64_t w = right + left + 1;
+    return w > 0 ? (u64)w : 0;
+}
+
 // ---- fingerprints of edit strings that lie in device memory (k_ops_fp, gamdp_ops_fp.hip; gamdp_align_batch_fp and
 // gamdp_ops_fingerprint_batch) ---------------------------------------------------------------------------------------------------
 // A string is cut into segments of OPS_FP_SEG_BYTES, one wavefront per segment, OPS_FP_LANE_BYTES contiguous bytes per lane; the

@@ -1738,6 +1738,14 @@ uint64_t gamdp_task_ops_cap(uint64_t alen, uint64_t blen, uint32_t band, uint64_
     return task_ops_cap(alen, blen, band, begin_a, end_a, begin_b, end_b, force_start != 0, force_end != 0);
 }
 
+uint64_t gamdp_task_live_columns(uint64_t alen, uint64_t blen, uint32_t band, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,
+                                 uint64_t end_b, int force_start, int force_end)
+{
+    u64 X = 0, cells = 0;
+    if (preflight(alen, blen, band, begin_a, end_a, begin_b, end_b, force_start != 0, force_end != 0, &X, &cells) != GAMDP_ST_OK) return 0;
+    return live_columns_hd(alen, band, begin_a, X);
+}
+
 int gamdp_ctx_set_ops_chunk_bytes(gamdp_ctx* ctx, uint64_t bytes)
 {
     if (!ctx) return GAMDP_EINVAL;

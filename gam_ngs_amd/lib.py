@@ -29,6 +29,7 @@ SYMBOLS = [
     "gamdp_ops_fingerprint", "gamdp_carry_ops_batch", "gamdp_ctx_carry_ops_info",
     "gamdp_task_ops_cap", "gamdp_align_batch_fp", "gamdp_ctx_set_ops_chunk_bytes", "gamdp_ops_fingerprint_batch",
     "gamdp_ctx_ops_fp_info",
+    "gamdp_task_live_columns",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
@@ -278,6 +279,9 @@ def load_library():
         lib.gamdp_ops_fingerprint_batch.restype = C.c_int
         lib.gamdp_ctx_ops_fp_info.argtypes = [vp, C.POINTER(OpsFpInfo)]
         lib.gamdp_ctx_ops_fp_info.restype = C.c_int
+    if hasattr(lib, "gamdp_task_live_columns"):   # (as above: older builds through GAMDP_LIB)
+        lib.gamdp_task_live_columns.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int]
+        lib.gamdp_task_live_columns.restype = u64
     lib.gamdp_task_preflight.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int, C.POINTER(u64)]
     lib.gamdp_ctx_l1_stats.argtypes = [vp, C.POINTER(L1Stats)]
     lib.gamdp_ctx_set_l1_hits.argtypes = [vp, C.c_int]

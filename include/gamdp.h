@@ -343,6 +343,21 @@ int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp
  * its bands take; the fields as for gamdp_ctx_score_info. */
 int gamdp_ctx_carry_ops_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n);
 
+/* The live width of one find_alignment call, on plain numbers (the arguments of gamdp_task_preflight; host only, no context): 0
+ * for a call the pre-checks settle, otherwise the largest number of cells with 0 <= begin_a + i + j - band < alen in any one row
+ * i < x_size, 0 <= j <= 2 band.  In closed form, with A0 = begin_a - band and last = alen - 1 - A0: row i holds
+ *     n(i) = min(2 band, last - i) + min(0, A0 + i) + 1
+ * such cells (none when that is negative), which rises while i < min(-A0, last - 2 band), is level up to the larger of the two and
+ * falls behind it; so the result is max(0, n(i*)) with i* = min(-A0, last - 2 band) clamped to [0, x_size - 1].  It never exceeds
+ * min(2 band + 1, alen).
+ * What it is for: a cell outside a holds 0 and no traceback enters it, so a fill needs the live cells only, and a sweep by
+ * anti-diagonals (cell (i, j) at step 2 i + j, sources one and two steps back) holds at most one cell per row and at most this many
+ * rows in a step: three steps of this many entries are the whole state of a carry fill (gamdp_carry_batch) at any band, whatever
+ * the rows and however far the band reaches beyond a -- against x_size * (2 band + 1) * 4 bytes of band matrix in gamdp_align_batch.
+ * tests/_carrywmodel.py is that schedule in Python, its ring sized by this function and every read checked. */
+uint64_t gamdp_task_live_columns(uint64_t alen, uint64_t blen, uint32_t band, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,
+                                 uint64_t end_b, int force_start, int force_end);
+
 /* An upper bound on gamdp_result.length of one find_alignment call, on plain numbers (the arguments of gamdp_task_preflight; host
  * only, no context): 0 for a call the pre-checks settle, otherwise a multiple of 16 (the bound rounded up; at least 16).
  * The argument, against the traceback loop of banded_smith_waterman.cc:227-311.  Let X = x_size (:93-95, what the pre-checks size)

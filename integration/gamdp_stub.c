@@ -71,3 +71,29 @@ uint32_t gamdp_ops_fingerprint(const uint8_t* ops, uint64_t n)
     for (i = 0; i < n; i++) f = f * GAMDP_OPS_FP_MULT + ((uint32_t)ops[i] + 1u);
     return f;
 }
+/* (the live width of a call needs no device and is the real one: the pre-checks of gamdp_task_preflight, then the closed form
+ * include/gamdp.h states -- tests/test_carry_wide_cabi.py compares the two) */
+uint64_t gamdp_task_live_columns(uint64_t alen, uint64_t blen, uint32_t band32, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,
+                                 uint64_t end_b, int force_start, int force_end)
+{
+    /* a call the pre-checks let through has an edit-string bound (gamdp_task_ops_cap above makes the same pre-checks) */
+    const int64_t band = band32;
+    int64_t A0, last, i, right, left, w;
+    uint64_t X, lim;
+    if (gamdp_task_ops_cap(alen, blen, band32, begin_a, end_a, begin_b, end_b, force_start, force_end) == 0 || alen == 0) return 0;
+    if (end_b >= blen) end_b = blen - 1;
+    X = end_b - begin_b + 1;
+    lim = alen + (uint64_t)band - begin_a;
+    if (lim < X) X = lim;
+    if (X > 500000) X = 500000;
+    if (alen > (1ull << 62)) alen = 1ull << 62;
+    A0 = (int64_t)begin_a - band;
+    last = (int64_t)alen - 1 - A0;
+    i = -A0 < last - 2 * band ? -A0 : last - 2 * band;
+    if (i < 0) i = 0;
+    if (i > (int64_t)X - 1) i = (int64_t)X - 1;
+    right = 2 * band < last - i ? 2 * band : last - i;
+    left = A0 + i < 0 ? A0 + i : 0;
+    w = right + left + 1;
+    return w > 0 ? (uint64_t)w : 0;
+}
