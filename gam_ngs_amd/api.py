@@ -88,6 +88,17 @@ class Context:
         _check(self, self.lib.gamdp_ctx_walk_skip_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_stats")
         return st.as_dict()
 
+    def set_walk_skip_pair(self, mode: int):
+        """The same choice for the walks of the two-task band-512 kernel, a property of its own: L.WALK_STRIPS (the default) or
+        L.WALK_SKIP_DIAG (gamdp_ctx_set_walk_skip_pair).  The results do not depend on it."""
+        _check(self, self.lib.gamdp_ctx_set_walk_skip_pair(self.handle, mode), "gamdp_ctx_set_walk_skip_pair")
+
+    def walk_skip_pair_stats(self):
+        """What the two-task launches of the last gamdp_align_batch on this context counted, as a dict (gamdp_ctx_walk_skip_pair_stats)."""
+        st = L.WalkSkipPairStats()
+        _check(self, self.lib.gamdp_ctx_walk_skip_pair_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_pair_stats")
+        return st.as_dict()
+
     def l1_tail_calls(self):
         """The tail alignments of the last alignMergeBlocks on this context and the seed each was given, as
         (merge_block, right, begin_a, source) tuples ordered by merge block, left before right (gamdp_ctx_l1_tail_calls)."""
@@ -261,6 +272,22 @@ class MultiContext:
             st = L.WalkSkipStats()
             if self.lib.gamdp_ctx_walk_skip_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
                 raise L.GamdpError("gamdp_ctx_walk_skip_stats failed on context %d" % i)
+            out.append(st.as_dict())
+        return out
+
+    def set_walk_skip_pair(self, mode: int, which=None):
+        """Context.set_walk_skip_pair on every context of the handle, or on context `which` alone."""
+        for i in (range(len(self.devices)) if which is None else (which,)):
+            if self.lib.gamdp_ctx_set_walk_skip_pair(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
+                raise L.GamdpError("gamdp_ctx_set_walk_skip_pair(%r) failed on context %d" % (mode, i))
+
+    def walk_skip_pair_stats(self):
+        """Context.walk_skip_pair_stats of every context of the handle (a list of dicts)."""
+        out = []
+        for i in range(len(self.devices)):
+            st = L.WalkSkipPairStats()
+            if self.lib.gamdp_ctx_walk_skip_pair_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
+                raise L.GamdpError("gamdp_ctx_walk_skip_pair_stats failed on context %d" % i)
             out.append(st.as_dict())
         return out
 

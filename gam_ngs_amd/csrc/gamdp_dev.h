@@ -96,6 +96,10 @@ enum : int { LS_UNITS = 0, LS_DIRFREE, LS_PACKED_TOP, LS_PACKED_TOP_MIXED, LS_ST
 // the eight-task kernel's walks test for indel-free groups before they ask for a strip (kernel_walk.inc, walk_many<..., SKIP>):
 // set by the host for contexts in GAMDP_WALK_SKIP_DIAG mode; every other kernel ignores it
 constexpr u32 LP_WALK_SKIP_DIAG = 32;
+// the same test in the two-task kernel's walks, side by side (walk_many<17, 4, ..., 2, 64, SKIP>) and one task after the other
+// (kernel_finish.inc, finish_walk<..., SKIP>): set by the host for K_P17_CE4 launches of contexts in GAMDP_WALK_SKIP_DIAG mode of
+// gamdp_ctx_set_walk_skip_pair; every other kernel ignores it.  Counted in the same LS_SKIP_* words (a launch runs one kernel).
+constexpr u32 LP_WALK_SKIP_PAIR = 64;
 // the two-task kernel walks its two tasks side by side (kernel_walk.inc) instead of one after the other: set by the host for
 // launches of at most two rounds, where the wavefronts of a SIMD walk at the same time and the scalar unit is the bottleneck
 constexpr u32 LP_WALK_SIDE_BY_SIDE = 1;

@@ -88,6 +88,7 @@ const Tuning& tuning()
         if ((e = std::getenv("GAMDP_L1_CHAIN_CARRY"))) x.l1_chain_carry = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_L1_WALK_ANY_BAND"))) x.l1_walk_any_band = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_WALK_SKIP"))) x.walk_skip = std::atoi(e) == 1;
+        if ((e = std::getenv("GAMDP_WALK_SKIP_PAIR"))) x.walk_skip_pair = std::atoi(e) == 1;
         return x;
     }();
     return t;
@@ -309,6 +310,7 @@ int Ctx::init(int dev)
     l1_chain = tuning().l1_chain_carry ? GAMDP_L1_CHAIN_CARRY : GAMDP_L1_CHAIN_WALK;
     walk_bands = tuning().l1_walk_any_band ? GAMDP_L1_WALK_ANY_BAND : GAMDP_L1_WALK_BAND_150;
     walk_skip = tuning().walk_skip ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
+    walk_skip_pair = tuning().walk_skip_pair ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
     if (hipSetDevice(dev) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("hipGetDeviceProperties failed"); return GAMDP_ENODEV; }
@@ -862,15 +864,19 @@ int Ctx::align_scratch(u64 arena_call)
     return 0;
 }
 
+// whether a launch of the two-task kernel walks its two tasks side by side (LP_WALK_SIDE_BY_SIDE)
+static bool walks_side_by_side(const Launch& L) { return L.kid == K_P17_CE4 && (u64)L.count / 2 <= tuning().side_walk_rounds * L.n_slots; }
+
 // LaunchParams::flags / prio_* of a launch
-static void launch_policy(const Launch& L, LaunchParams& p, const int walk_skip)
+static void launch_policy(const Launch& L, LaunchParams& p, const int walk_skip, const int walk_skip_pair)
 {
     const Tuning& tu = tuning();
     const u64 tpw = (u64)kernel_info[L.kid].tasks_per_wave, units = L.count / tpw;
-    p.flags = (L.kid == K_P17_CE4 && (u64)L.count / 2 <= tu.side_walk_rounds * L.n_slots) ? LP_WALK_SIDE_BY_SIDE : 0u;
+    p.flags = walks_side_by_side(L) ? LP_WALK_SIDE_BY_SIDE : 0u;
     if (tu.no_packed_top) p.flags |= LP_NO_PACKED_TOP;
     if (tu.no_packed_top_mixed) p.flags |= LP_NO_PACKED_TOP_MIXED;
     if (L.kid == K_O19_CE15 && walk_skip == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_DIAG;   // (gamdp_ctx_set_walk_skip; the eight-task kernel alone has the test)
+    if (L.kid == K_P17_CE4 && walk_skip_pair == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_PAIR;   // (gamdp_ctx_set_walk_skip_pair; the two-task kernel, both of its walk paths)
     // the end-cell / strip / walk phase of the two- and eight-task kernels issues one level above a steady-state fill in
     // launches of more than two rounds (gamdp_dev.h; GAMDP_WALK_PRIO=0..3 overrides, A/B)
     p.flags |= (tu.walk_prio >= 0 ? (u32)tu.walk_prio : (units > 2ull * L.n_slots ? 1u : 0u)) << LP_WALK_PRIO_SHIFT;
@@ -928,7 +934,7 @@ int Ctx::align_run(AlignCall& a)
         p.scratch = d_scratch + L.scratch_off; p.slot_words = L.slot_words; p.dir_words = L.dir_words; p.ypad = L.ypad;
         p.ckpt_off = L.ckpt_off; p.bnd_off = L.bnd_off;
         p.stats = d_stats + li * LS_COUNT;
-        launch_policy(L, p, walk_skip);
+        launch_policy(L, p, walk_skip, walk_skip_pair);
         hipStream_t const on = L.aux ? aux_stream : stream;
         HIPCHK(this, hipEventRecord(events[li].first, on));
         const int e = launch_align(L.kid, p, L.n_slots, L.dyn_lds, on);
@@ -995,6 +1001,14 @@ void Ctx::align_collect(AlignCall& a)
                 W.tests += st[LS_SKIP_TESTS]; W.groups_tested += st[LS_SKIP_TESTED]; W.groups_skipped += st[LS_SKIP_GROUPS];
                 W.rows_skipped += 64ull * st[LS_SKIP_GROUPS] - st[LS_SKIP_SHORT];
                 W.strips += st[LS_STRIPS];
+            }
+            if (L.kid == K_P17_CE4) {   // gamdp_ctx_walk_skip_pair_stats: the two-task launches of the call
+                gamdp_walk_skip_pair_stats& W = last_walk_skip_pair;
+                W.tests += st[LS_SKIP_TESTS]; W.groups_tested += st[LS_SKIP_TESTED]; W.groups_skipped += st[LS_SKIP_GROUPS];
+                W.rows_skipped += 64ull * st[LS_SKIP_GROUPS] - st[LS_SKIP_SHORT];
+                W.strips += st[LS_STRIPS];
+                if (walks_side_by_side(L)) W.launches_side_by_side++; else W.launches_one_by_one++;
+                W.mode = (uint32_t)walk_skip_pair;   // (everything stays 0 when the call makes no two-task launch)
             }
             r.piece = log_piece;
             r.rounds = L.n_slots ? (double)r.units / (double)L.n_slots : 0.0;
@@ -1329,6 +1343,7 @@ int Ctx::align_fp(const gamdp_task* tasks, const SeqSet* sa, const SeqSet* sb, c
         launch_log.clear();
         last_walk_skip = gamdp_walk_skip_stats{};
         last_walk_skip.mode = (uint32_t)walk_skip;
+        last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
         if ((rc_ = align(src, cnt, out + first, nullptr, caps.data() + first))) return rc_;
         // the strings of the chunk: where align() put them (w_prep), how long the walks made them (out)
         fpt.clear(); seg_first.clear();
@@ -1559,6 +1574,24 @@ int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out)
     return 0;
 }
 
+static_assert(sizeof(gamdp_walk_skip_pair_stats) == 56 && offsetof(gamdp_walk_skip_pair_stats, strips) == 32 && offsetof(gamdp_walk_skip_pair_stats, mode) == 40 &&
+              offsetof(gamdp_walk_skip_pair_stats, launches_side_by_side) == 44 && offsetof(gamdp_walk_skip_pair_stats, launches_one_by_one) == 48,
+              "gamdp_walk_skip_pair_stats: the layout include/gamdp.h documents (gam_ngs_amd/lib.py WalkSkipPairStats mirrors it)");
+
+int gamdp_ctx_set_walk_skip_pair(gamdp_ctx* ctx, int mode)
+{
+    if ((mode != GAMDP_WALK_STRIPS && mode != GAMDP_WALK_SKIP_DIAG) || !ctx) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->walk_skip_pair = mode;
+    return 0;
+}
+
+int gamdp_ctx_walk_skip_pair_stats(const gamdp_ctx* ctx, gamdp_walk_skip_pair_stats* out)
+{
+    if (!ctx || !out) return GAMDP_EINVAL;
+    *out = reinterpret_cast<const Ctx*>(ctx)->last_walk_skip_pair;
+    return 0;
+}
+
 int gamdp_seqset_create(gamdp_ctx* ctx, const uint8_t* const* seqs, const uint64_t* lens, uint32_t n, int is_ascii,
                         gamdp_seqset** out)
 {
@@ -1599,6 +1632,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     c->launch_log.clear();
     c->last_walk_skip = gamdp_walk_skip_stats{};
     c->last_walk_skip.mode = (uint32_t)c->walk_skip;
+    c->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; for (Ctx* h : c->helpers) h->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {
@@ -1634,6 +1668,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     cc[1]->kernel_ms = 0; cc[1]->kernel_launches = 0;
     cc[1]->launch_log.clear(); cc[1]->log_launches = true;
     cc[1]->walk_skip = c->walk_skip; cc[1]->last_walk_skip = gamdp_walk_skip_stats{};
+    cc[1]->walk_skip_pair = c->walk_skip_pair; cc[1]->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
     int rc[2] = {0, 0};
     auto worker = [&](int t) noexcept {
         for (size_t k = (size_t)t; k < 4 && rc[t] == 0; k += 2) {
@@ -1653,6 +1688,13 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
         gamdp_walk_skip_stats& W = c->last_walk_skip;
         const gamdp_walk_skip_stats& H = cc[1]->last_walk_skip;
         W.tests += H.tests; W.groups_tested += H.groups_tested; W.groups_skipped += H.groups_skipped; W.rows_skipped += H.rows_skipped; W.strips += H.strips;
+    }
+    {
+        gamdp_walk_skip_pair_stats& W = c->last_walk_skip_pair;
+        const gamdp_walk_skip_pair_stats& H = cc[1]->last_walk_skip_pair;
+        W.tests += H.tests; W.groups_tested += H.groups_tested; W.groups_skipped += H.groups_skipped; W.rows_skipped += H.rows_skipped; W.strips += H.strips;
+        W.launches_side_by_side += H.launches_side_by_side; W.launches_one_by_one += H.launches_one_by_one;
+        W.mode |= H.mode;   // (the helper runs in the owner's mode)
     }
     std::stable_sort(c->launch_log.begin(), c->launch_log.end(), [](const gamdp_launch_info& x, const gamdp_launch_info& y) { return x.piece < y.piece; });
     if (rc[1]) c->set_error(cc[1]->err);
@@ -1761,6 +1803,7 @@ int gamdp_align_batch_fp(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_
     c->launch_log.clear();
     c->last_walk_skip = gamdp_walk_skip_stats{};
     c->last_walk_skip.mode = (uint32_t)c->walk_skip;
+    c->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {

@@ -58,6 +58,7 @@ struct Tuning {
     bool l1_chain_carry = false;        // GAMDP_L1_CHAIN_CARRY=1: new contexts start in GAMDP_L1_CHAIN_CARRY mode (gamdp_ctx_set_l1_chain)
     bool l1_walk_any_band = false;      // GAMDP_L1_WALK_ANY_BAND=1: new contexts start with GAMDP_L1_WALK_ANY_BAND (gamdp_ctx_set_l1_walk_bands)
     bool walk_skip = false;             // GAMDP_WALK_SKIP=1: new contexts start in GAMDP_WALK_SKIP_DIAG mode (gamdp_ctx_set_walk_skip)
+    bool walk_skip_pair = false;        // GAMDP_WALK_SKIP_PAIR=1: ... and in GAMDP_WALK_SKIP_DIAG mode of gamdp_ctx_set_walk_skip_pair
 };
 const Tuning& tuning();
 
@@ -221,6 +222,9 @@ struct Ctx {
     // eight-task launches of the last gamdp_align_batch counted (align_collect adds while log_launches is set)
     int walk_skip = GAMDP_WALK_STRIPS;
     gamdp_walk_skip_stats last_walk_skip{};
+    // the same for the two-task band-512 kernel, a property of its own (gamdp_ctx_set_walk_skip_pair -> LP_WALK_SKIP_PAIR)
+    int walk_skip_pair = GAMDP_WALK_STRIPS;
+    gamdp_walk_skip_pair_stats last_walk_skip_pair{};
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }

@@ -365,11 +365,15 @@ __device__ __forceinline__ void finish_many(const LaunchParams& p, const u32 fir
     if constexpr (NT == 8 || LPT == 64) {
         if (side_by_side && skip != (1 << NT) - 1) {
             // (eight-task kernel, LP_WALK_SKIP_DIAG: the instance whose walks jump over indel-free groups -- wave-uniform, per launch)
+            // (two-task kernel, LP_WALK_SKIP_PAIR: the same, in that kernel's checkpoint format; walk_pair_skip makes the strips)
             bool skip_diag = false;
             if constexpr (PK && NT == 8 && LPT == QL) skip_diag = (p.flags & LP_WALK_SKIP_DIAG) != 0;
             for (;;) {
                 u32 need;
-                if constexpr (PK && NT == 8 && LPT == QL) {
+                if constexpr (PK && NT == 2 && LPT == 64) {
+                    if (p.flags & LP_WALK_SKIP_PAIR) { walk_pair_skip<C, CE>(&ta, &tb, wcs, skip, lane, &p); need = 0; }
+                    else need = (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
+                } else if constexpr (PK && NT == 8 && LPT == QL) {
                     need = skip_diag ? (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT, true>(&ta, &tb, wcs, skip, lane, lds_tk, p.stats))
                                      : (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
                 } else need = (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
@@ -402,6 +406,10 @@ __device__ __forceinline__ void finish_many(const LaunchParams& p, const u32 fir
     for (int s = 0; s < NT; ++s) {
         if ((padding >> s) & 1) continue;
         const int lb = (LPT == 64) ? 0 : QL * (s & 3), hs = (LPT == 64) ? s : s >> 2;
+        // (two-task kernel, LP_WALK_SKIP_PAIR: the instance whose walk makes the diagonal test -- wave-uniform, per launch)
+        if constexpr (PK && NT == 2 && LPT == 64) {
+            if (p.flags & LP_WALK_SKIP_PAIR) { finish_walk<C, CE, HASN, LPT, PK, false, true>(task_tkp(s), &p.tasks[first_task + (u32)s], &p, lane, lb, hs, &wcs[s]); continue; }
+        }
         finish_walk<C, CE, HASN, LPT, PK>(task_tkp(s), &p.tasks[first_task + (u32)s], &p, lane, lb, hs, &wcs[s]);
     }
 }

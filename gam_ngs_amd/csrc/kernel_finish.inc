@@ -127,12 +127,16 @@ __device__ __noinline__ void end_cell(const Tk* tp, const int lane, WalkCarry* w
 // that task's values in every lane; the whole wavefront works on one task at a time here, exactly as with one task per
 // wavefront -- only the lanes that own the direction words / strips are offset by lane_base.
 // Two tasks per wavefront in packed f16 (PK): the strips' inputs are the packed stores, pk_half_ = which task of the pair.
-template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool EARLY = false>
+// SKIP (two-task kernel only, LP_WALK_SKIP_PAIR; a second instance, the default one holds none of it): the diagonal test of
+// walk_many<..., SKIP> (kernel_walk.inc has the argument) for the walk that has the whole wavefront: before a block without
+// directions costs a strip, lane k tests the k-th span below the walk and the walk jumps over the passing prefix.
+template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool EARLY = false, bool SKIP = false>
 __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, const LaunchParams* pp, const int lane, const int lane_base_, const int pk_half_, WalkCarry* wcp)
 {
     const int lane_base = (LPT == 64) ? 0 : uni(lane_base_);
     const int pk_half = PK ? uni(pk_half_) : 0;
     typedef Strip<LPT, PK> ST;
+    static_assert(!SKIP || (PK && LPT == 64 && !HASN && !EARLY && DIRFREE_OK<CE, C, HASN>), "the diagonal test reads the two-task kernel's checkpoint rows (PairFmt<C, 64>); the chain walkers stay without it");
     const Tk t = load_uniform(tp);
     const DevTask* dtp = unip(dtp_);
     const u32 dt_flags = (u32)uni((int)dtp->flags) & TF_LIVE_MASK, dt_res_idx = (u32)uni((int)dtp->res_idx);
@@ -192,6 +196,11 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
             int dg_iters = 0, dg_refills = 0;
             const long long walk_t0 = (dt_flags & TF_DIAG_COUNT_MAT) ? wall_clock64() : 0;
             int cvalid_lo = 0;  // cached blocks below this one are not usable (direction-free, not materialised)
+            // SKIP: a test that found no passing span is not repeated before the walk has its strip (sk_fail_at = mat_calls then);
+            // what this walk counted (LS_SKIP_*).  Diagnostics that count strips keep their strips.
+            [[maybe_unused]] int sk_fail_at = -1;
+            [[maybe_unused]] const bool sk_on = !(dt_flags & TF_DIAG_COUNT_MAT);
+            [[maybe_unused]] u32 sk_tests = 0, sk_tested = 0, sk_groups = 0, sk_short = 0;
             auto get_word = [&](const int blk, const int l_, const int c_) -> u32 {
                 const int g = c_ >> 2;
                 int k = cblk0 - blk;
@@ -315,6 +324,88 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                     // about one instruction per 4 cycles, so the walk is bound by its instruction count, not by the
                     // vector ALU: one iteration per run instead of one per direction word.
                     const int tau = x + l, blk = tau >> 4, r = tau & 15;
+                    if constexpr (SKIP) {
+                        // ---- get_word() would ask for a strip here: are the groups below nothing but diagonal steps?  (kernel_walk.inc,
+                        // walk_many<..., SKIP>: the same test, the same validity rules, in the same units -- a diagonal step adds 12 or 21
+                        // to G = H + 16 x + 8 y, which is what materialise_impl's unpack() for PK, LPT == 64 yields before its factor 4.)
+                        // The walk state is wave-uniform here, so all 64 lanes take a span each: lane k the k-th one below the walk (the
+                        // first down to the next checkpoint row, 64 rows each after that), up to 4 096 rows per test.  A test costs one
+                        // memory round trip however many lanes take part -- every lane's loads are in flight together -- and the walk of a
+                        // lone wavefront is bound by its round trips and its instruction count: an indel-free 50 kb path takes 13 tests.
+                        const int strip = ST::strip_of(lane_base + l, t.sshift);
+                        if (sk_on && blk >= t.df_lo && blk < t.df_hi && sk_fail_at != mat_calls && !(blk >= mat_lo && blk <= mat_hi) &&
+                            !(strip == old_q && blk >= old_lo && blk <= old_hi)) {
+                            typedef PairFmt<C, LPT> FMT;
+                            const int gi = blk >> 2, d0 = (tau & 63) + 1;                    // checkpoint gi: d0 steps below the walk
+                            const int g_lo = t.df_lo >> 2, g_top = (t.df_hi >> 2) - 1;       // the groups whose checkpoint rows the fill stored
+                            const int off = (lane == 0) ? 0 : d0 + 64 * (lane - 1), cnt = (lane == 0) ? d0 : 64;   // this lane's span: steps [off, off + cnt) from the top
+                            const int gb = gi - lane;                                        // the checkpoint at its lower end, gb + 1 at its upper end
+                            const int ll = min(max(l, 0), LPT - 1), cc = min(max(c, 0), C - 1);
+                            // every cell of the span is an else-branch cell of the fill (the cell it ends on keeps x >= 1, pos >= 1: row 0
+                            // and pos == 0 stay with the single steps above), its lower checkpoint row exists
+                            const bool at_start = len == 0u;
+                            const bool up_ok = (lane == 0) ? (at_start || (d0 == 64 && gi + 1 <= g_top)) : true;
+                            const bool span_ok = up_ok && gb >= g_lo && x - (off + cnt) >= 1 && pos - (off + cnt) >= 1;
+                            auto ck_val = [&](const int gidx) -> int {   // as materialise_impl's unpack(raw[c], ckbase) for PK, LPT == 64, in units of G
+                                gptr ck = t.ckpt + (u64)min(max(gidx, g_lo), g_top) * (u64)FMT::CK_WORDS;
+                                const u32 v = ck[(u32)ll * FMT::CK_LANE + cc];
+                                return pat_decode(pk_half ? v >> 16 : v & 0xFFFFu) + (int)ck[FMT::CK_ROWS + pk_half * 64 + ll];
+                            };
+                            const int g_bot = ck_val(gb), g_up = ck_val(gb + 1);
+                            // (a lane without a span reads lane 0's bases: nothing in front of the sequences' padding is touched)
+                            const int off_ld = span_ok ? off : 0;
+                            const int ia_lo = (int)t.a_base + pos - off_ld - 63, ib_lo = (int)t.b_base + t.begin_b + x - off_ld - 63;   // base p of the span's 64 (0 = lowest row)
+                            u32 aw[5], bw[5];
+#pragma unroll
+                            for (int k = 0; k < 5; ++k) { aw[k] = t.a2[(ia_lo >> 4) + k]; bw[k] = t.b2[(ib_lo >> 4) + k]; }
+                            // the upper value: the score at the end cell, else the checkpoint row the walk stands on (a full span of 64)
+                            const int g_top_val = (lane == 0 && at_start) ? best + 16 * x + 8 * y : g_up;
+                            const int p0 = 64 - cnt;                                         // lane 0: the top d0 bases only
+                            u32 eq[4];
+                            int m = 0;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                const u32 a16 = __builtin_amdgcn_alignbit(aw[k + 1], aw[k], (u32)(ia_lo & 15) * 2u), b16 = __builtin_amdgcn_alignbit(bw[k + 1], bw[k], (u32)(ib_lo & 15) * 2u);
+                                const u32 xr = a16 ^ b16, ne = (xr | (xr >> 1)) & 0x55555555u;
+                                const int q0 = p0 - 16 * k;
+                                const u32 msk = (q0 <= 0) ? 0x55555555u : ((q0 >= 16) ? 0u : (0x55555555u << (2 * q0)));
+                                eq[k] = ~ne & msk;
+                                m += __builtin_popcount(eq[k]);
+                            }
+                            const bool pass = span_ok && g_top_val - g_bot == 12 * cnt + 9 * m;
+                            const u64 m_pass = __ballot(pass);
+                            const int np = (~m_pass == 0ull) ? 64 : __builtin_ctzll(~m_pass);   // the passing prefix
+                            sk_tests++; sk_tested += (u32)__builtin_popcountll(__ballot(span_ok));
+                            if (np > 0) {
+                                const bool inc = lane < np;
+                                int cnt_m = inc ? m : 0;
+                                cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0xB1, 0xf, 0xf, true);   // quad_perm:[1,0,3,2]
+                                cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0x4E, 0xf, 0xf, true);   // quad_perm:[2,3,0,1]
+                                cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0x141, 0xf, 0xf, true);  // row_half_mirror
+                                cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0x140, 0xf, 0xf, true);  // row_mirror: every lane = its row's sum
+                                nm += (u32)(__builtin_amdgcn_readlane(cnt_m, 0) + __builtin_amdgcn_readlane(cnt_m, 16) +
+                                            __builtin_amdgcn_readlane(cnt_m, 32) + __builtin_amdgcn_readlane(cnt_m, 48));
+                                const u64 m_eq = __ballot(inc && m > 0);
+                                if (m_eq) {
+                                    int ptop = 0, pbot = 0;
+#pragma unroll
+                                    for (int kk = 0; kk < 4; ++kk) if (eq[kk]) ptop = 16 * kk + ((31 - __builtin_clz(eq[kk])) >> 1);
+#pragma unroll
+                                    for (int kk = 3; kk >= 0; --kk) if (eq[kk]) pbot = 16 * kk + (__builtin_ctz(eq[kk]) >> 1);
+                                    const int off_hi = __builtin_amdgcn_readlane(off + 63 - ptop, __builtin_ctzll(m_eq));        // steps below the walk
+                                    const int off_lo = __builtin_amdgcn_readlane(off + 63 - pbot, 63 - __builtin_clzll(m_eq));
+                                    if (!have_last) { have_last = true; la = pos - off_hi; lb = t.begin_b + x - off_hi; }
+                                    have_first = true; fa = pos - off_lo; fb = t.begin_b + x - off_lo;
+                                }
+                                const int n = d0 + 64 * (np - 1);
+                                x -= n; pos -= n; len += (u32)n;
+                                sk_groups += (u32)np; sk_short += (u32)(64 - d0);
+                                cblk0 = -1; cl = -1; cg = -1;   // the cached direction words are those of the blocks the walk has left
+                                continue;                       // round again: the next test, directions, or row 0 / pos == 0
+                            }
+                            sk_fail_at = mat_calls;
+                        }
+                    }
                     const u32 w_here = get_word(blk, l, c);  // (re)fills the cache / materialises the strip if needed
                     const int k0 = cblk0 - blk, e = c & 3;
                     const int myk = lane >> 2;
@@ -429,6 +520,14 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
             res.last_b = have_last ? lb : res.begin_b;
             res.flags = (have_first ? 1u : 0u) | (have_last ? 2u : 0u) | (ST_OK << 8);
             if (pp->stats != nullptr && lane == 0 && mat_calls > 0) atomicAdd(unip(pp->stats) + LS_STRIPS, (u32)mat_calls);   // (gamdp_ctx_launch_info)
+            if constexpr (SKIP) {
+                if (pp->stats != nullptr && lane == 0 && sk_tests != 0) {   // (gamdp_ctx_walk_skip_pair_stats)
+                    atomicAdd(unip(pp->stats) + LS_SKIP_TESTS, sk_tests);
+                    atomicAdd(unip(pp->stats) + LS_SKIP_TESTED, sk_tested);
+                    atomicAdd(unip(pp->stats) + LS_SKIP_GROUPS, sk_groups);
+                    if (sk_short != 0) atomicAdd(unip(pp->stats) + LS_SKIP_SHORT, sk_short);
+                }
+            }
             if (dt_flags & TF_DIAG_COUNT_MAT) {  // diagnostics only: result unusable
                 res.n_match = (u32)mat_calls;
                 res.first_a = (int)mat_ticks + uni(wcp->mat_ticks);

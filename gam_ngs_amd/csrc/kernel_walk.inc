@@ -26,14 +26,14 @@
 // inlined and calls again.  Nothing of the walks is in registers while a strip is made, so nobody saves registers around it
 // (as a call from in here: 28 callee-saved registers stored and re-loaded per strip call, 14 KB of scratch each time).  The
 // two-task kernel (LPT = 64: carries in the caller's frame, one copy per lane) keeps the call in here and always returns 0.
-// SKIP (eight-task kernel only, LP_WALK_SKIP_DIAG; a second instance, the default one holds none of it): a walk that stands on
-// a block without directions first asks whether the groups below it hold nothing but diagonal steps, and jumps over those that do
-// (the test sits where the inner loop finds `need`) before it is reported as waiting for a strip.  skip_stats: the launch's
-// statistics words (LS_SKIP_*), nullptr = not counted.
+// SKIP (the packed kernels: the eight-task one under LP_WALK_SKIP_DIAG, the two-task one under LP_WALK_SKIP_PAIR; a second instance,
+// the default one holds none of it): a walk that stands on a block without directions first asks whether the groups below it hold
+// nothing but diagonal steps, and jumps over those that do (the test sits where the inner loop finds `need`) before it is reported as
+// waiting for a strip.  skip_stats: the launch's statistics words (LS_SKIP_*), nullptr = not counted.
 template <int C, int CE, bool HASN, bool PK, int NT, int LPT = QL, bool SKIP = false>
 __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* wcs, const int skip_mask_, const int lane, const Tk* tks = nullptr, u32* skip_stats = nullptr)
 {
-    static_assert(!SKIP || (PK && LPT == QL && NT == 8), "the diagonal test reads the eight-task kernel's checkpoint rows (PairFmt::GRP)");
+    static_assert(!SKIP || (PK && ((LPT == QL && NT == 8) || (LPT == 64 && NT == 2))), "the diagonal test reads the packed kernels' checkpoint rows (PairFmt)");
     static_assert(DIRFREE_OK<CE, C, HASN>, "the multi-task kernels are direction-free kernels");
     static_assert((LPT == QL && (NT == 4 || NT == 8)) || (LPT == 64 && NT == 2 && PK), "one or two quads, or the pair of the two-task kernel");
     static_assert(!HASN, "only the N-free kernels use it (the N planes would be two more word pairs per lane and iteration)");
@@ -65,8 +65,6 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
     gptr const dir = (gptr)pick64((u64)tap->dir, (u64)tbq->dir);
     const int df_lo = pick(tap->df_lo, tbq->df_lo), df_hi = pick(tap->df_hi, tbq->df_hi);
     const int sshift = uni(tap->sshift);   // the same for every task of the wavefront
-    gptr ckpt = nullptr;                   // SKIP: the slot's checkpoint rows
-    if constexpr (SKIP) ckpt = (gptr)pick64((u64)tap->ckpt, (u64)tbq->ckpt);
 
     const WalkCarry w0 = wcs[gt];
     int x = w0.x, y = w0.y, pos = w0.pos;
@@ -130,15 +128,25 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
             const bool cand = active && need && !stuck && !(blk0 >= mat_lo && blk0 <= mat_hi);
             if (__ballot(cand) != 0) {
                 typedef PairFmt<C, LPT> FMT;
+                gptr const ckpt = (gptr)pick64((u64)tap->ckpt, (u64)tbq->ckpt);   // the slot's checkpoint rows
                 const int gi = blk0 >> 2, d0 = (tau & 63) + 1;             // checkpoint gi: d0 steps below the walk
                 const int g_lo = df_lo >> 2, g_top = (df_hi >> 2) - 1;     // the groups whose checkpoint rows the fill stored
                 const int off = (j == 0) ? 0 : d0 + 64 * (j - 1), cnt = (j == 0) ? d0 : 64;   // this lane's span: steps [off, off + cnt) from the top
                 const int gb = gi - j;                                     // the checkpoint at its lower end, gb + 1 at its upper end
                 const int cc = min(max(c, 0), C - 1);
                 auto ck_val = [&](const int gidx) -> int {
-                    gptr rp = ckpt + (u64)min(max(gidx, g_lo), g_top) * (u64)FMT::CK_WORDS + (u32)(lane_base + ll) * FMT::CK_LANE;
-                    const u32 v = rp[cc];
-                    return (int)(float)(half ? hi_of(v) : lo_of(v)) + (int)rp[C + half];   // as materialise_impl's unpack(row[c], grp_base), in units of G
+                    gptr ck = ckpt + (u64)min(max(gidx, g_lo), g_top) * (u64)FMT::CK_WORDS;
+                    if constexpr (FMT::GRP) {
+                        gptr rp = ck + (u32)(lane_base + ll) * FMT::CK_LANE;
+                        const u32 v = rp[cc];
+                        return (int)(float)(half ? hi_of(v) : lo_of(v)) + (int)rp[C + half];   // as materialise_impl's unpack(row[c], grp_base), in units of G
+                    } else {
+                        // the two-task format: lane-major rows of PATTERNS, the bases behind them as [task][lane] -- as materialise_impl's
+                        // unpack(raw[c], ckbase) for PK, LPT == 64 (img_load<C, true> + pat_decode), in units of G; the top blocks store
+                        // through h2_to_pat, so every row reads the same way
+                        const u32 v = ck[(u32)ll * FMT::CK_LANE + cc];
+                        return pat_decode(half ? v >> 16 : v & 0xFFFFu) + (int)ck[FMT::CK_ROWS + half * 64 + ll];
+                    }
                 };
                 const int g_bot = ck_val(gb), g_up = ck_val(gb + 1);
                 const int ia_lo = a_base + pos - off - 63, ib_lo = bb_base + x - off - 63;   // base p of the span's 64 (0 = lowest row)
@@ -271,6 +279,28 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
         }
     }
     if (m_need == 0) break;
+    if constexpr (LPT == 64 && SKIP) {
+        // back to the caller (walk_pair_skip below) for the strips, as with a task per DPP row: this instance makes no call, so it
+        // saves no registers around one and has no frame of its own.  The carries are one copy per lane: every lane stores the same.
+#pragma unroll
+        for (int s = 0; s < NT; ++s) {
+            WalkCarry& w = wcs[s];
+            const int L0 = 8 * s;
+            w.x = __builtin_amdgcn_readlane(x, L0); w.y = __builtin_amdgcn_readlane(y, L0); w.pos = __builtin_amdgcn_readlane(pos, L0);
+            w.len = (u32)__builtin_amdgcn_readlane((int)len, L0); w.nm = (u32)__builtin_amdgcn_readlane((int)nm, L0);
+            w.la = __builtin_amdgcn_readlane(la, L0); w.lb = __builtin_amdgcn_readlane(lb, L0);
+            w.fa = __builtin_amdgcn_readlane(fa, L0); w.fb = __builtin_amdgcn_readlane(fb, L0); w.have = __builtin_amdgcn_readlane(have, L0);
+            w.mat_q = __builtin_amdgcn_readlane(mat_q, L0); w.mat_lo = __builtin_amdgcn_readlane(mat_lo, L0); w.mat_hi = __builtin_amdgcn_readlane(mat_hi, L0);
+            w.old_q = __builtin_amdgcn_readlane(old_q, L0); w.old_lo = __builtin_amdgcn_readlane(old_lo, L0); w.old_hi = __builtin_amdgcn_readlane(old_hi, L0);
+            w.mat_calls = __builtin_amdgcn_readlane(mat_calls, L0);
+            w.need_q = __builtin_amdgcn_readlane(strip, L0); w.need_ghi = __builtin_amdgcn_readlane(blk0 >> 2, L0);
+        }
+        count_skips();
+        u32 need = 0;
+#pragma unroll
+        for (int s = 0; s < NT; ++s) need |= ((m_need >> (8 * s)) & 0xFFull) ? (1u << s) : 0u;
+        return need;
+    } else
     if constexpr (LPT != 64) {
         // back to the caller for the strips: the first lane of every group stores its task's state (uniform within the group)
         if (j == 0 && g < NT) {
@@ -288,6 +318,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
         return need;
     }
     // ---- the strips that are asked for, one task at a time with the whole wavefront on it
+    if constexpr (!SKIP)
     while (m_need != 0) {
         const int first = __builtin_ctzll(m_need), sel = first >> 3;
         const int q_s = __builtin_amdgcn_readlane(strip, first), ghi_s = __builtin_amdgcn_readlane(blk0 >> 2, first);
@@ -319,6 +350,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
         count_skips();
         return 0u;
     }
+    count_skips();
 #pragma unroll
     for (int s = 0; s < NT; ++s) {
         WalkCarry& w = wcs[s];
@@ -332,4 +364,34 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
         w.mat_calls = __builtin_amdgcn_readlane(mat_calls, L0);
     }
     return 0u;
+}
+
+// The side-by-side walks of the two-task kernel with the diagonal test (LP_WALK_SKIP_PAIR): walk_many<..., 2, 64, SKIP> returns for its
+// strips and they are made here, one task at a time with the whole wavefront on it -- what finish_many does in the kernel itself for the
+// eight-task kernel.  Out of line: the kernel's own code and frame are what they were without the test, and nothing of the walks is in
+// registers while a strip is made.  (pp, not its stats pointer: a value of *pp that the kernel hands over is one more register it
+// keeps across its calls.)
+template <int C, int CE>
+__device__ __noinline__ void walk_pair_skip(const Tk* tap, const Tk* tbp, WalkCarry* wcs, const int skip_mask, const int lane, const LaunchParams* pp)
+{
+    typedef Strip<64, true> ST;
+    u32* const skip_stats = unip(unip(pp)->stats);
+    for (;;) {
+        const u32 need = (u32)uni((int)walk_many<C, CE, false, true, 2, 64, true>(tap, tbp, wcs, skip_mask, lane, nullptr, skip_stats));
+        if (need == 0) break;
+#pragma unroll 1
+        for (u32 rest = need; rest != 0; rest &= rest - 1) {
+            const int s = __builtin_ctz(rest);
+            const Tk* const tsp = s ? tbp : tap;
+            const int q_s = uni(wcs[s].need_q), ghi_s = uni(wcs[s].need_ghi);
+            materialise_auto<C, CE, false, 64, true>(tsp, q_s, ghi_s, lane, s, 0);
+            // the loads of the walk must see those stores: wait until L2 has them, then drop this CU's L1 lines
+            __builtin_amdgcn_s_waitcnt(0);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            WalkCarry& w = wcs[s];   // (one copy per lane, wave-uniform values)
+            w.old_q = w.mat_q; w.old_lo = w.mat_lo; w.old_hi = w.mat_hi;
+            w.mat_q = q_s; w.mat_hi = 4 * ghi_s + 3; w.mat_lo = max(4 * (ghi_s - (ST::groups_of(q_s) - 1)), uni(tsp->df_lo));
+            w.mat_calls++;
+        }
+    }
 }

@@ -25,7 +25,7 @@ SYMBOLS = [
     "gamdp_find_hits_batch", "gamdp_ctx_set_l1_hits", "gamdp_ctx_l1_hits_stats",
     "gamdp_ctx_l1_tail_calls", "gamdp_score_batch", "gamdp_ctx_score_info", "gamdp_carry_batch", "gamdp_ctx_carry_info",
     "gamdp_ctx_set_l1_chain", "gamdp_ctx_l1_chain_stats", "gamdp_ctx_set_l1_walk_bands",
-    "gamdp_ctx_set_walk_skip", "gamdp_ctx_walk_skip_stats",
+    "gamdp_ctx_set_walk_skip", "gamdp_ctx_walk_skip_stats", "gamdp_ctx_set_walk_skip_pair", "gamdp_ctx_walk_skip_pair_stats",
     "gamdp_ops_fingerprint", "gamdp_carry_ops_batch", "gamdp_ctx_carry_ops_info",
     "gamdp_task_ops_cap", "gamdp_align_batch_fp", "gamdp_ctx_set_ops_chunk_bytes", "gamdp_ops_fingerprint_batch",
     "gamdp_ctx_ops_fp_info",
@@ -37,7 +37,7 @@ ST_OK, ST_EMPTY, ST_OUT_OF_RANGE, ST_INVALID = 0, 1, 2, 3
 L1_HITS_HOST, L1_HITS_DEVICE = 0, 1   # gamdp_ctx_set_l1_hits
 L1_CHAIN_WALK, L1_CHAIN_CARRY = 0, 1   # gamdp_ctx_set_l1_chain
 L1_WALK_BAND_150, L1_WALK_ANY_BAND = 0, 1   # gamdp_ctx_set_l1_walk_bands
-WALK_STRIPS, WALK_SKIP_DIAG = 0, 1   # gamdp_ctx_set_walk_skip
+WALK_STRIPS, WALK_SKIP_DIAG = 0, 1   # gamdp_ctx_set_walk_skip, gamdp_ctx_set_walk_skip_pair
 ST_DIAG_RANGE = 9   # diagnostics build only: a packed-f16 block left the exact range (never expected)
 
 
@@ -160,6 +160,16 @@ class WalkSkipStats(C.Structure):
     """gamdp_walk_skip_stats: what the eight-task launches of the last gamdp_align_batch counted (static_assert in gamdp_host.cpp)."""
     _fields_ = [("tests", C.c_uint64), ("groups_tested", C.c_uint64), ("groups_skipped", C.c_uint64), ("rows_skipped", C.c_uint64),
                 ("strips", C.c_uint64), ("mode", C.c_uint32), ("pad_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
+class WalkSkipPairStats(C.Structure):
+    """gamdp_walk_skip_pair_stats: what the two-task launches of the last gamdp_align_batch counted (static_assert in gamdp_host.cpp)."""
+    _fields_ = [("tests", C.c_uint64), ("groups_tested", C.c_uint64), ("groups_skipped", C.c_uint64), ("rows_skipped", C.c_uint64),
+                ("strips", C.c_uint64), ("mode", C.c_uint32), ("launches_side_by_side", C.c_uint32), ("launches_one_by_one", C.c_uint32),
+                ("pad_", C.c_uint32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
@@ -297,6 +307,11 @@ def load_library():
         lib.gamdp_ctx_set_walk_skip.restype = C.c_int
         lib.gamdp_ctx_walk_skip_stats.argtypes = [vp, C.POINTER(WalkSkipStats)]
         lib.gamdp_ctx_walk_skip_stats.restype = C.c_int
+    if hasattr(lib, "gamdp_ctx_set_walk_skip_pair"):   # (the same)
+        lib.gamdp_ctx_set_walk_skip_pair.argtypes = [vp, C.c_int]
+        lib.gamdp_ctx_set_walk_skip_pair.restype = C.c_int
+        lib.gamdp_ctx_walk_skip_pair_stats.argtypes = [vp, C.POINTER(WalkSkipPairStats)]
+        lib.gamdp_ctx_walk_skip_pair_stats.restype = C.c_int
     lib.gamdp_ctx_l1_hits_stats.argtypes = [vp, C.POINTER(L1HitsStats)]
     lib.gamdp_ctx_l1_hits_stats.restype = C.c_int
     lib.gamdp_ctx_l1_tail_calls.argtypes = [vp, C.POINTER(L1TailCall), C.c_size_t, C.POINTER(C.c_size_t)]

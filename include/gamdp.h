@@ -197,6 +197,29 @@ typedef struct gamdp_walk_skip_stats {
 } gamdp_walk_skip_stats;       /* 48 bytes */
 int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
 
+/* The same choice for the walks of the two-task band-512 kernel ("k_align_p<17,4>"), a property of its own: the modes are
+ * GAMDP_WALK_STRIPS (the default) and GAMDP_WALK_SKIP_DIAG as above, and the test is the same one, read off that kernel's checkpoint
+ * rows.  It covers both ways the kernel walks: its two tasks side by side (launches of few rounds) and one task after the other with
+ * the whole wavefront (long launches), where up to 64 groups are tested at a time.  A task whose edit string is wanted keeps its
+ * strips.  Results do not depend on the mode.  The two properties are independent: gamdp_ctx_set_walk_skip leaves the two-task
+ * kernel alone, this one leaves the eight-task kernel (and every other kernel) alone.  gamdp_multi_* honours each context's own
+ * setting; GAMDP_WALK_SKIP_PAIR=1 in the environment (read once per process) makes SKIP_DIAG the mode of new contexts. */
+int gamdp_ctx_set_walk_skip_pair(gamdp_ctx* ctx, int mode);   /* GAMDP_EINVAL for NULL / unknown mode (mode checked first) */
+/* What the two-task launches of the last gamdp_align_batch on this context counted on the device, summed over the call's launches
+ * and pieces; everything 0 (`mode` too) when the call made no two-task launch, and before the first call. */
+typedef struct gamdp_walk_skip_pair_stats {
+    uint64_t tests;            /* as in gamdp_walk_skip_stats (one test looks at up to 8 groups side by side, up to 64 one by one) */
+    uint64_t groups_tested;
+    uint64_t groups_skipped;
+    uint64_t rows_skipped;
+    uint64_t strips;           /* strip re-creations of those launches (the sum of their gamdp_launch_info.strips) */
+    uint32_t mode;             /* GAMDP_WALK_* the call ran in */
+    uint32_t launches_side_by_side;   /* two-task launches that walked their two tasks side by side ... */
+    uint32_t launches_one_by_one;     /* ... and one task after the other */
+    uint32_t pad_;
+} gamdp_walk_skip_pair_stats;  /* 56 bytes */
+int gamdp_ctx_walk_skip_pair_stats(const gamdp_ctx* ctx, gamdp_walk_skip_pair_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
+
 /* ---- sequences ---------------------------------------------------------------------------- */
 /* seqs[i] points to lens[i] bytes: ASCII bases when is_ascii!=0 (normalised like Nucleotide(char)),
  * else base codes A=0 T=1 C=2 G=3 N=4.  Packs to 2 bit + N mask and uploads to the ctx's GPU. */

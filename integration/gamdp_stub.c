@@ -17,6 +17,9 @@ int gamdp_multi_align_merge_blocks(gamdp_multi* m, const gamdp_multi_seqset* mas
 /* (a bridge that opts in to GAMDP_WALK_SKIP_DIAG on the contexts of its handle links against these two; there is no context here) */
 int gamdp_ctx_set_walk_skip(gamdp_ctx* ctx, int mode) { (void)ctx; (void)mode; return GAMDP_ENODEV; }
 int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out) { (void)ctx; (void)out; return GAMDP_ENODEV; }
+/* (... and to the same test in the two-task band-512 kernel) */
+int gamdp_ctx_set_walk_skip_pair(gamdp_ctx* ctx, int mode) { (void)ctx; (void)mode; return GAMDP_ENODEV; }
+int gamdp_ctx_walk_skip_pair_stats(const gamdp_ctx* ctx, gamdp_walk_skip_pair_stats* out) { (void)ctx; (void)out; return GAMDP_ENODEV; }
 /* (a bridge that checks the edit strings of its batches links against these three; the fingerprint needs no device and is the real one) */
 int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
                           gamdp_result* out, uint32_t* ops_fp)

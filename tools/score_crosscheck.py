@@ -62,6 +62,7 @@ def main():
     ap.add_argument("--first-pair", type=int, default=0)
     ap.add_argument("--seed", type=int, default=20261019)
     ap.add_argument("--carry", action="store_true", help="also run gamdp_carry_batch and compare whole results")
+    ap.add_argument("--walk-skip-pair", action="store_true", help="with --carry: gamdp_align_batch runs with gamdp_ctx_set_walk_skip_pair(GAMDP_WALK_SKIP_DIAG)")
     ap.add_argument("--ops", action="store_true", help="also run gamdp_carry_ops_batch and compare the fingerprints of gamdp_align_batch's edit strings")
     ap.add_argument("--device-fp", action="store_true", help="with --ops: the align side's fingerprints from gamdp_align_batch_fp (the strings stay on the device)")
     ap.add_argument("--host-fp-too", action="store_true", help="with --ops --device-fp: also the download path of plain --ops, alternating with it")
@@ -71,7 +72,12 @@ def main():
         ap.error("--device-fp goes with --ops, --host-fp-too with --device-fp")
     if bool(args.pairs) == bool(args.mixed):
         ap.error("one of --pairs N or --mixed N")
+    if args.walk_skip_pair and not args.carry:
+        ap.error("--walk-skip-pair goes with --carry")
     ctx = gam.Context(0)
+    skip_pair = None
+    if args.walk_skip_pair:   # the two-task kernel's walks jump over indel-free groups: checked call by call against gamdp_carry_batch
+        ctx.set_walk_skip_pair(L.WALK_SKIP_DIAG)
     if args.mixed:
         import _mixed
         seqs, calls = _mixed.mixed_batch(args.seed, max(1, args.mixed // 8), 8, band=args.band)
@@ -120,6 +126,8 @@ def main():
         rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res, None)
         assert rc == 0, ("gamdp_align_batch", rc, ctx.last_error())
         a_ms = ctx.kernel_time(reset=True)[0]
+        if args.walk_skip_pair:
+            skip_pair = ctx.walk_skip_pair_stats()
         rc = ctx.lib.gamdp_score_batch(ctx.handle, sset.handle, sset.handle, tasks, n, sc)
         assert rc == 0, ("gamdp_score_batch", rc, ctx.last_error())
         s_ms = ctx.kernel_time(reset=True)[0]
@@ -187,6 +195,8 @@ def main():
     if args.carry:
         rec.update(carry_mismatches=carry_mismatches, carry_first_mismatch=carry_first_bad, carry_kernels=[r["kernel"] for r in ctx.carry_info()],
                    carry_kernel_ms=[round(v, 3) for v in carry_ms], carry_gcups=round(cells / med(carry_ms) / 1e6, 1))
+    if args.walk_skip_pair:
+        rec.update(walk_skip_pair=skip_pair)
     if args.ops:
         rec.update(ops_mismatches=ops_mismatches, ops_first_mismatch=ops_first_bad, ops_kernels=[r["kernel"] for r in ctx.carry_ops_info()],
                    ops_kernel_ms=[round(v, 3) for v in ops_ms], align_ops_kernel_ms=[round(v, 3) for v in align_ops_ms],
