@@ -99,6 +99,18 @@ class Context:
         _check(self, self.lib.gamdp_ctx_walk_skip_pair_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_pair_stats")
         return st.as_dict()
 
+    def set_walk_skip_i32(self, mode: int):
+        """The same choice for the walks of the int32 direction-free kernels (k_align<17,4>, k_align_q<19,15>, k_align<9,-1,true>,
+        k_align<17,-1,true>), a third property: L.WALK_STRIPS (the default) or L.WALK_SKIP_DIAG (gamdp_ctx_set_walk_skip_i32).
+        The results do not depend on it."""
+        _check(self, self.lib.gamdp_ctx_set_walk_skip_i32(self.handle, mode), "gamdp_ctx_set_walk_skip_i32")
+
+    def walk_skip_i32_stats(self):
+        """What the launches of those kernels in the last gamdp_align_batch on this context counted, as a dict (gamdp_ctx_walk_skip_i32_stats)."""
+        st = L.WalkSkipI32Stats()
+        _check(self, self.lib.gamdp_ctx_walk_skip_i32_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_i32_stats")
+        return st.as_dict()
+
     def l1_tail_calls(self):
         """The tail alignments of the last alignMergeBlocks on this context and the seed each was given, as
         (merge_block, right, begin_a, source) tuples ordered by merge block, left before right (gamdp_ctx_l1_tail_calls)."""
@@ -288,6 +300,22 @@ class MultiContext:
             st = L.WalkSkipPairStats()
             if self.lib.gamdp_ctx_walk_skip_pair_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
                 raise L.GamdpError("gamdp_ctx_walk_skip_pair_stats failed on context %d" % i)
+            out.append(st.as_dict())
+        return out
+
+    def set_walk_skip_i32(self, mode: int, which=None):
+        """Context.set_walk_skip_i32 on every context of the handle, or on context `which` alone."""
+        for i in (range(len(self.devices)) if which is None else (which,)):
+            if self.lib.gamdp_ctx_set_walk_skip_i32(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
+                raise L.GamdpError("gamdp_ctx_set_walk_skip_i32(%r) failed on context %d" % (mode, i))
+
+    def walk_skip_i32_stats(self):
+        """Context.walk_skip_i32_stats of every context of the handle (a list of dicts)."""
+        out = []
+        for i in range(len(self.devices)):
+            st = L.WalkSkipI32Stats()
+            if self.lib.gamdp_ctx_walk_skip_i32_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
+                raise L.GamdpError("gamdp_ctx_walk_skip_i32_stats failed on context %d" % i)
             out.append(st.as_dict())
         return out
 

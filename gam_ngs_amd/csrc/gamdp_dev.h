@@ -100,6 +100,10 @@ constexpr u32 LP_WALK_SKIP_DIAG = 32;
 // (kernel_finish.inc, finish_walk<..., SKIP>): set by the host for K_P17_CE4 launches of contexts in GAMDP_WALK_SKIP_DIAG mode of
 // gamdp_ctx_set_walk_skip_pair; every other kernel ignores it.  Counted in the same LS_SKIP_* words (a launch runs one kernel).
 constexpr u32 LP_WALK_SKIP_PAIR = 64;
+// the same test in the walks of the int32 direction-free kernels, read off their int32 checkpoint images (finish_walk<..., SKIP> with
+// PK == false): set by the host for launches of k_align<17,4>, k_align_q<19,15> (N-aware or not), k_align<9,-1,true> and
+// k_align<17,-1,true> of contexts in GAMDP_WALK_SKIP_DIAG mode of gamdp_ctx_set_walk_skip_i32; every other kernel ignores it.
+constexpr u32 LP_WALK_SKIP_I32 = 128;
 // the two-task kernel walks its two tasks side by side (kernel_walk.inc) instead of one after the other: set by the host for
 // launches of at most two rounds, where the wavefronts of a SIMD walk at the same time and the scalar unit is the bottleneck
 constexpr u32 LP_WALK_SIDE_BY_SIDE = 1;

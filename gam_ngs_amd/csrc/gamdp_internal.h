@@ -59,6 +59,7 @@ struct Tuning {
     bool l1_walk_any_band = false;      // GAMDP_L1_WALK_ANY_BAND=1: new contexts start with GAMDP_L1_WALK_ANY_BAND (gamdp_ctx_set_l1_walk_bands)
     bool walk_skip = false;             // GAMDP_WALK_SKIP=1: new contexts start in GAMDP_WALK_SKIP_DIAG mode (gamdp_ctx_set_walk_skip)
     bool walk_skip_pair = false;        // GAMDP_WALK_SKIP_PAIR=1: ... and in GAMDP_WALK_SKIP_DIAG mode of gamdp_ctx_set_walk_skip_pair
+    bool walk_skip_i32 = false;         // GAMDP_WALK_SKIP_I32=1: ... and of gamdp_ctx_set_walk_skip_i32
 };
 const Tuning& tuning();
 
@@ -225,6 +226,9 @@ struct Ctx {
     // the same for the two-task band-512 kernel, a property of its own (gamdp_ctx_set_walk_skip_pair -> LP_WALK_SKIP_PAIR)
     int walk_skip_pair = GAMDP_WALK_STRIPS;
     gamdp_walk_skip_pair_stats last_walk_skip_pair{};
+    // ... and for the int32 direction-free kernels, a third property (gamdp_ctx_set_walk_skip_i32 -> LP_WALK_SKIP_I32)
+    int walk_skip_i32 = GAMDP_WALK_STRIPS;
+    gamdp_walk_skip_i32_stats last_walk_skip_i32{};
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }

@@ -410,6 +410,10 @@ __device__ __forceinline__ void finish_many(const LaunchParams& p, const u32 fir
         if constexpr (PK && NT == 2 && LPT == 64) {
             if (p.flags & LP_WALK_SKIP_PAIR) { finish_walk<C, CE, HASN, LPT, PK, false, true>(task_tkp(s), &p.tasks[first_task + (u32)s], &p, lane, lb, hs, &wcs[s]); continue; }
         }
+        // (four-task kernel, LP_WALK_SKIP_I32: the same for its int32 checkpoint rows, the task's lanes from lane_base on)
+        if constexpr (!PK && NT == QT && LPT == QL) {
+            if (p.flags & LP_WALK_SKIP_I32) { finish_walk<C, CE, HASN, LPT, PK, false, true>(task_tkp(s), &p.tasks[first_task + (u32)s], &p, lane, lb, hs, &wcs[s]); continue; }
+        }
         finish_walk<C, CE, HASN, LPT, PK>(task_tkp(s), &p.tasks[first_task + (u32)s], &p, lane, lb, hs, &wcs[s]);
     }
 }

@@ -127,16 +127,21 @@ __device__ __noinline__ void end_cell(const Tk* tp, const int lane, WalkCarry* w
 // that task's values in every lane; the whole wavefront works on one task at a time here, exactly as with one task per
 // wavefront -- only the lanes that own the direction words / strips are offset by lane_base.
 // Two tasks per wavefront in packed f16 (PK): the strips' inputs are the packed stores, pk_half_ = which task of the pair.
-// SKIP (two-task kernel only, LP_WALK_SKIP_PAIR; a second instance, the default one holds none of it): the diagonal test of
-// walk_many<..., SKIP> (kernel_walk.inc has the argument) for the walk that has the whole wavefront: before a block without
-// directions costs a strip, lane k tests the k-th span below the walk and the walk jumps over the passing prefix.
+// SKIP (a second instance, the default one holds none of it): the diagonal test of walk_many<..., SKIP> (kernel_walk.inc has the
+// argument) for the walk that has the whole wavefront: before a block without directions costs a strip, lane k tests the k-th
+// span below the walk and the walk jumps over the passing prefix.  Two formats of checkpoint row: the two-task kernel's patterns
+// (PK, LP_WALK_SKIP_PAIR) and the int32 images of every other direction-free kernel (LP_WALK_SKIP_I32: k_align and k_align_q,
+// N-aware or not, LPT == 64 or one DPP row per task).
+template <bool PK> struct SkipIdx { typedef int64_t T; };   // a base index of the test's loads (the two-task instance keeps its 32-bit ones)
+template <> struct SkipIdx<true> { typedef int T; };
 template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool EARLY = false, bool SKIP = false>
 __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, const LaunchParams* pp, const int lane, const int lane_base_, const int pk_half_, WalkCarry* wcp)
 {
     const int lane_base = (LPT == 64) ? 0 : uni(lane_base_);
     const int pk_half = PK ? uni(pk_half_) : 0;
     typedef Strip<LPT, PK> ST;
-    static_assert(!SKIP || (PK && LPT == 64 && !HASN && !EARLY && DIRFREE_OK<CE, C, HASN>), "the diagonal test reads the two-task kernel's checkpoint rows (PairFmt<C, 64>); the chain walkers stay without it");
+    static_assert(!SKIP || (!EARLY && DIRFREE_OK<CE, C, HASN>), "the diagonal test reads checkpoint rows; the chain walkers stay without it");
+    static_assert(!SKIP || (PK ? (LPT == 64 && !HASN) : (LPT == 64 || LPT == QL)), "the diagonal test knows the two-task kernel's checkpoint rows (PairFmt<C, 64>) and the int32 images of the one- and four-task kernels");
     const Tk t = load_uniform(tp);
     const DevTask* dtp = unip(dtp_);
     const u32 dt_flags = (u32)uni((int)dtp->flags) & TF_LIVE_MASK, dt_res_idx = (u32)uni((int)dtp->res_idx);
@@ -332,10 +337,14 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                         // first down to the next checkpoint row, 64 rows each after that), up to 4 096 rows per test.  A test costs one
                         // memory round trip however many lanes take part -- every lane's loads are in flight together -- and the walk of a
                         // lone wavefront is bound by its round trips and its instruction count: an indel-free 50 kb path takes 13 tests.
+                        // Int32 images (!PK): the row holds G4 = 4 G itself, so the same equality in units of 4 -- a diagonal step adds
+                        // 4 (S + 16) = 84 for equal codes (N-N too), 64 when exactly one side is N, 48 for a mismatch: what enc_b() puts
+                        // into the untagged ring of do_block_df.  With four tasks per wavefront the lanes of the row are lane_base + l;
+                        // all 64 lanes of the wavefront still take a span each, the walk has the wavefront to itself.
                         const int strip = ST::strip_of(lane_base + l, t.sshift);
                         if (sk_on && blk >= t.df_lo && blk < t.df_hi && sk_fail_at != mat_calls && !(blk >= mat_lo && blk <= mat_hi) &&
                             !(strip == old_q && blk >= old_lo && blk <= old_hi)) {
-                            typedef PairFmt<C, LPT> FMT;
+                            constexpr int UNIT = PK ? 1 : 4;                                 // what the checkpoint rows count in: G or G4
                             const int gi = blk >> 2, d0 = (tau & 63) + 1;                    // checkpoint gi: d0 steps below the walk
                             const int g_lo = t.df_lo >> 2, g_top = (t.df_hi >> 2) - 1;       // the groups whose checkpoint rows the fill stored
                             const int off = (lane == 0) ? 0 : d0 + 64 * (lane - 1), cnt = (lane == 0) ? d0 : 64;   // this lane's span: steps [off, off + cnt) from the top
@@ -347,45 +356,82 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                             const bool up_ok = (lane == 0) ? (at_start || (d0 == 64 && gi + 1 <= g_top)) : true;
                             const bool span_ok = up_ok && gb >= g_lo && x - (off + cnt) >= 1 && pos - (off + cnt) >= 1;
                             auto ck_val = [&](const int gidx) -> int {   // as materialise_impl's unpack(raw[c], ckbase) for PK, LPT == 64, in units of G
-                                gptr ck = t.ckpt + (u64)min(max(gidx, g_lo), g_top) * (u64)FMT::CK_WORDS;
-                                const u32 v = ck[(u32)ll * FMT::CK_LANE + cc];
-                                return pat_decode(pk_half ? v >> 16 : v & 0xFFFFu) + (int)ck[FMT::CK_ROWS + pk_half * 64 + ll];
+                                if constexpr (PK) {
+                                    typedef PairFmt<C, LPT> FMT;
+                                    gptr ck = t.ckpt + (u64)min(max(gidx, g_lo), g_top) * (u64)FMT::CK_WORDS;
+                                    const u32 v = ck[(u32)ll * FMT::CK_LANE + cc];
+                                    return pat_decode(pk_half ? v >> 16 : v & 0xFFFFu) + (int)ck[FMT::CK_ROWS + pk_half * 64 + ll];
+                                } else {   // ... and its (int)raw[c] for the int32 images: word c of wavefront lane lane_base + l (img_store<C, true> in do_block_df), G4
+                                    gptr ck = t.ckpt + (u64)min(max(gidx, g_lo), g_top) * (u64)IMG_WORDS<C, true>;
+                                    return (int)ck[(u32)(lane_base + ll) * (u32)LANE_WORDS<C> + (u32)cc];
+                                }
                             };
                             const int g_bot = ck_val(gb), g_up = ck_val(gb + 1);
                             // (a lane without a span reads lane 0's bases: nothing in front of the sequences' padding is touched)
                             const int off_ld = span_ok ? off : 0;
-                            const int ia_lo = (int)t.a_base + pos - off_ld - 63, ib_lo = (int)t.b_base + t.begin_b + x - off_ld - 63;   // base p of the span's 64 (0 = lowest row)
+                            typedef typename SkipIdx<PK>::T SI;
+                            const SI ia_lo = (SI)t.a_base + pos - off_ld - 63, ib_lo = (SI)t.b_base + t.begin_b + x - off_ld - 63;   // base p of the span's 64 (0 = lowest row)
                             u32 aw[5], bw[5];
 #pragma unroll
                             for (int k = 0; k < 5; ++k) { aw[k] = t.a2[(ia_lo >> 4) + k]; bw[k] = t.b2[(ib_lo >> 4) + k]; }
+                            // N-aware: the N planes of the same 64 bases (32 per word), bit p = base p; a MATCH is equal codes or an N on either
+                            // side (the reference's op), the score tells N-N (5, an equal pair) from exactly one N (0)
+                            [[maybe_unused]] u32 na[2] = {0u, 0u}, nb[2] = {0u, 0u};
+                            if constexpr (HASN) {
+                                u32 anw[3], bnw[3];
+#pragma unroll
+                                for (int k = 0; k < 3; ++k) { anw[k] = t.an[(ia_lo >> 5) + k]; bnw[k] = t.bn[(ib_lo >> 5) + k]; }
+#pragma unroll
+                                for (int k = 0; k < 2; ++k) {
+                                    na[k] = __builtin_amdgcn_alignbit(anw[k + 1], anw[k], (u32)(ia_lo & 31));
+                                    nb[k] = __builtin_amdgcn_alignbit(bnw[k + 1], bnw[k], (u32)(ib_lo & 31));
+                                }
+                            }
                             // the upper value: the score at the end cell, else the checkpoint row the walk stands on (a full span of 64)
-                            const int g_top_val = (lane == 0 && at_start) ? best + 16 * x + 8 * y : g_up;
+                            const int g_top_val = (lane == 0 && at_start) ? UNIT * (best + 16 * x + 8 * y) : g_up;
                             const int p0 = 64 - cnt;                                         // lane 0: the top d0 bases only
                             u32 eq[4];
                             int m = 0;
+                            [[maybe_unused]] int n1 = 0;   // pairs with exactly one N
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
                                 const u32 a16 = __builtin_amdgcn_alignbit(aw[k + 1], aw[k], (u32)(ia_lo & 15) * 2u), b16 = __builtin_amdgcn_alignbit(bw[k + 1], bw[k], (u32)(ib_lo & 15) * 2u);
                                 const u32 xr = a16 ^ b16, ne = (xr | (xr >> 1)) & 0x55555555u;
                                 const int q0 = p0 - 16 * k;
                                 const u32 msk = (q0 <= 0) ? 0x55555555u : ((q0 >= 16) ? 0u : (0x55555555u << (2 * q0)));
-                                eq[k] = ~ne & msk;
-                                m += __builtin_popcount(eq[k]);
+                                if constexpr (HASN) {
+                                    auto spread = [](u32 v) -> u32 {   // 16 bits to the even positions
+                                        v = (v | (v << 8)) & 0x00FF00FFu;
+                                        v = (v | (v << 4)) & 0x0F0F0F0Fu;
+                                        v = (v | (v << 2)) & 0x33333333u;
+                                        return (v | (v << 1)) & 0x55555555u;
+                                    };
+                                    const u32 a16n = (na[k >> 1] >> (16 * (k & 1))) & 0xFFFFu, b16n = (nb[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+                                    const u32 any = spread(a16n | b16n), both = spread(a16n & b16n);
+                                    const u32 e_k = (both | (~any & ~ne)) & msk, n1_k = any & ~both & msk;
+                                    m += __builtin_popcount(e_k);
+                                    n1 += __builtin_popcount(n1_k);
+                                    eq[k] = e_k | n1_k;
+                                } else {
+                                    eq[k] = ~ne & msk;
+                                    m += __builtin_popcount(eq[k]);
+                                }
                             }
-                            const bool pass = span_ok && g_top_val - g_bot == 12 * cnt + 9 * m;
+                            const int mm = HASN ? m + n1 : m;   // MATCH ops of the span
+                            const bool pass = span_ok && g_top_val - g_bot == UNIT * (12 * cnt + 9 * m) + (HASN ? 16 * n1 : 0);
                             const u64 m_pass = __ballot(pass);
                             const int np = (~m_pass == 0ull) ? 64 : __builtin_ctzll(~m_pass);   // the passing prefix
                             sk_tests++; sk_tested += (u32)__builtin_popcountll(__ballot(span_ok));
                             if (np > 0) {
                                 const bool inc = lane < np;
-                                int cnt_m = inc ? m : 0;
+                                int cnt_m = inc ? mm : 0;
                                 cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0xB1, 0xf, 0xf, true);   // quad_perm:[1,0,3,2]
                                 cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0x4E, 0xf, 0xf, true);   // quad_perm:[2,3,0,1]
                                 cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0x141, 0xf, 0xf, true);  // row_half_mirror
                                 cnt_m += __builtin_amdgcn_update_dpp(0, cnt_m, 0x140, 0xf, 0xf, true);  // row_mirror: every lane = its row's sum
                                 nm += (u32)(__builtin_amdgcn_readlane(cnt_m, 0) + __builtin_amdgcn_readlane(cnt_m, 16) +
                                             __builtin_amdgcn_readlane(cnt_m, 32) + __builtin_amdgcn_readlane(cnt_m, 48));
-                                const u64 m_eq = __ballot(inc && m > 0);
+                                const u64 m_eq = __ballot(inc && mm > 0);
                                 if (m_eq) {
                                     int ptop = 0, pbot = 0;
 #pragma unroll
@@ -521,7 +567,7 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
             res.flags = (have_first ? 1u : 0u) | (have_last ? 2u : 0u) | (ST_OK << 8);
             if (pp->stats != nullptr && lane == 0 && mat_calls > 0) atomicAdd(unip(pp->stats) + LS_STRIPS, (u32)mat_calls);   // (gamdp_ctx_launch_info)
             if constexpr (SKIP) {
-                if (pp->stats != nullptr && lane == 0 && sk_tests != 0) {   // (gamdp_ctx_walk_skip_pair_stats)
+                if (pp->stats != nullptr && lane == 0 && sk_tests != 0) {   // (gamdp_ctx_walk_skip_pair_stats, gamdp_ctx_walk_skip_i32_stats)
                     atomicAdd(unip(pp->stats) + LS_SKIP_TESTS, sk_tests);
                     atomicAdd(unip(pp->stats) + LS_SKIP_TESTED, sk_tested);
                     atomicAdd(unip(pp->stats) + LS_SKIP_GROUPS, sk_groups);
@@ -561,5 +607,9 @@ __device__ __forceinline__ void finish_task(const Tk* tp, const DevTask* dtp, co
 {
     WalkCarry wc;
     end_cell<C>(tp, lane, &wc);
+    // (LP_WALK_SKIP_I32: the instance whose walk makes the diagonal test -- wave-uniform, per launch)
+    if constexpr (!PK && DIRFREE_OK<CE, C, HASN>) {
+        if (pp->flags & LP_WALK_SKIP_I32) { finish_walk<C, CE, HASN, LPT, PK, false, true>(tp, dtp, pp, lane, lane_base, pk_half, &wc); return; }
+    }
     finish_walk<C, CE, HASN, LPT, PK>(tp, dtp, pp, lane, lane_base, pk_half, &wc);
 }

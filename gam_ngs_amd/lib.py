@@ -26,6 +26,7 @@ SYMBOLS = [
     "gamdp_ctx_l1_tail_calls", "gamdp_score_batch", "gamdp_ctx_score_info", "gamdp_carry_batch", "gamdp_ctx_carry_info",
     "gamdp_ctx_set_l1_chain", "gamdp_ctx_l1_chain_stats", "gamdp_ctx_set_l1_walk_bands",
     "gamdp_ctx_set_walk_skip", "gamdp_ctx_walk_skip_stats", "gamdp_ctx_set_walk_skip_pair", "gamdp_ctx_walk_skip_pair_stats",
+    "gamdp_ctx_set_walk_skip_i32", "gamdp_ctx_walk_skip_i32_stats",
     "gamdp_ops_fingerprint", "gamdp_carry_ops_batch", "gamdp_ctx_carry_ops_info",
     "gamdp_task_ops_cap", "gamdp_align_batch_fp", "gamdp_ctx_set_ops_chunk_bytes", "gamdp_ops_fingerprint_batch",
     "gamdp_ctx_ops_fp_info",
@@ -37,7 +38,7 @@ ST_OK, ST_EMPTY, ST_OUT_OF_RANGE, ST_INVALID = 0, 1, 2, 3
 L1_HITS_HOST, L1_HITS_DEVICE = 0, 1   # gamdp_ctx_set_l1_hits
 L1_CHAIN_WALK, L1_CHAIN_CARRY = 0, 1   # gamdp_ctx_set_l1_chain
 L1_WALK_BAND_150, L1_WALK_ANY_BAND = 0, 1   # gamdp_ctx_set_l1_walk_bands
-WALK_STRIPS, WALK_SKIP_DIAG = 0, 1   # gamdp_ctx_set_walk_skip, gamdp_ctx_set_walk_skip_pair
+WALK_STRIPS, WALK_SKIP_DIAG = 0, 1   # gamdp_ctx_set_walk_skip, gamdp_ctx_set_walk_skip_pair, gamdp_ctx_set_walk_skip_i32
 ST_DIAG_RANGE = 9   # diagnostics build only: a packed-f16 block left the exact range (never expected)
 
 
@@ -173,6 +174,16 @@ class WalkSkipPairStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
+class WalkSkipI32Stats(C.Structure):
+    """gamdp_walk_skip_i32_stats: what the launches of the int32 direction-free kernels in the last gamdp_align_batch counted
+    (static_assert in gamdp_host.cpp)."""
+    _fields_ = [("tests", C.c_uint64), ("groups_tested", C.c_uint64), ("groups_skipped", C.c_uint64), ("rows_skipped", C.c_uint64),
+                ("strips", C.c_uint64), ("mode", C.c_uint32), ("launches", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class L1TailCall(C.Structure):
@@ -312,6 +323,11 @@ def load_library():
         lib.gamdp_ctx_set_walk_skip_pair.restype = C.c_int
         lib.gamdp_ctx_walk_skip_pair_stats.argtypes = [vp, C.POINTER(WalkSkipPairStats)]
         lib.gamdp_ctx_walk_skip_pair_stats.restype = C.c_int
+    if hasattr(lib, "gamdp_ctx_set_walk_skip_i32"):   # (the same)
+        lib.gamdp_ctx_set_walk_skip_i32.argtypes = [vp, C.c_int]
+        lib.gamdp_ctx_set_walk_skip_i32.restype = C.c_int
+        lib.gamdp_ctx_walk_skip_i32_stats.argtypes = [vp, C.POINTER(WalkSkipI32Stats)]
+        lib.gamdp_ctx_walk_skip_i32_stats.restype = C.c_int
     lib.gamdp_ctx_l1_hits_stats.argtypes = [vp, C.POINTER(L1HitsStats)]
     lib.gamdp_ctx_l1_hits_stats.restype = C.c_int
     lib.gamdp_ctx_l1_tail_calls.argtypes = [vp, C.POINTER(L1TailCall), C.c_size_t, C.POINTER(C.c_size_t)]

@@ -220,6 +220,30 @@ typedef struct gamdp_walk_skip_pair_stats {
 } gamdp_walk_skip_pair_stats;  /* 56 bytes */
 int gamdp_ctx_walk_skip_pair_stats(const gamdp_ctx* ctx, gamdp_walk_skip_pair_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
 
+/* The same choice for the walks of the int32 direction-free kernels, a third property: "k_align<17,4,false>" and
+ * "k_align<17,4,true>" (band 512, one task per wavefront), "k_align_q<19,15,false>" and "k_align_q<19,15,true>" (band 150, four
+ * tasks per wavefront), "k_align<9,-1,true>" and "k_align<17,-1,true>" (every band from 160 to 543 other than 512).  The modes are
+ * GAMDP_WALK_STRIPS (the default) and GAMDP_WALK_SKIP_DIAG as above; the test is the same one, read off those kernels' int32
+ * checkpoint rows, with the reference's three-valued score where a sequence may hold N (N against N scores as a match, N against
+ * a base 0; both are MATCH ops).  Up to 64 groups are tested at a time.  A task whose edit string is wanted keeps its strips (so
+ * gamdp_align_batch_fp does); the chain kernels of gamdp_align_merge_blocks and "k_align_w" do not have the test.  Results do not
+ * depend on the mode.  The three properties are independent: each leaves the kernels of the other two alone.  gamdp_multi_*
+ * honours each context's own setting; GAMDP_WALK_SKIP_I32=1 in the environment (read once per process) makes SKIP_DIAG the mode
+ * of new contexts. */
+int gamdp_ctx_set_walk_skip_i32(gamdp_ctx* ctx, int mode);   /* GAMDP_EINVAL for NULL / unknown mode (mode checked first) */
+/* What the launches of those six kernels in the last gamdp_align_batch on this context counted on the device, summed over the
+ * call's launches and pieces; everything 0 (`mode` too) when the call made no such launch, and before the first call. */
+typedef struct gamdp_walk_skip_i32_stats {
+    uint64_t tests;            /* as in gamdp_walk_skip_stats (one test looks at up to 64 groups) */
+    uint64_t groups_tested;
+    uint64_t groups_skipped;
+    uint64_t rows_skipped;
+    uint64_t strips;           /* strip re-creations of those launches (the sum of their gamdp_launch_info.strips) */
+    uint32_t mode;             /* GAMDP_WALK_* the call ran in */
+    uint32_t launches;         /* the call's launches of the six kernels */
+} gamdp_walk_skip_i32_stats;   /* 48 bytes */
+int gamdp_ctx_walk_skip_i32_stats(const gamdp_ctx* ctx, gamdp_walk_skip_i32_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
+
 /* ---- sequences ---------------------------------------------------------------------------- */
 /* seqs[i] points to lens[i] bytes: ASCII bases when is_ascii!=0 (normalised like Nucleotide(char)),
  * else base codes A=0 T=1 C=2 G=3 N=4.  Packs to 2 bit + N mask and uploads to the ctx's GPU. */

@@ -20,6 +20,9 @@ int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out) 
 /* (... and to the same test in the two-task band-512 kernel) */
 int gamdp_ctx_set_walk_skip_pair(gamdp_ctx* ctx, int mode) { (void)ctx; (void)mode; return GAMDP_ENODEV; }
 int gamdp_ctx_walk_skip_pair_stats(const gamdp_ctx* ctx, gamdp_walk_skip_pair_stats* out) { (void)ctx; (void)out; return GAMDP_ENODEV; }
+/* (... and in the int32 direction-free kernels) */
+int gamdp_ctx_set_walk_skip_i32(gamdp_ctx* ctx, int mode) { (void)ctx; (void)mode; return GAMDP_ENODEV; }
+int gamdp_ctx_walk_skip_i32_stats(const gamdp_ctx* ctx, gamdp_walk_skip_i32_stats* out) { (void)ctx; (void)out; return GAMDP_ENODEV; }
 /* (a bridge that checks the edit strings of its batches links against these three; the fingerprint needs no device and is the real one) */
 int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
                           gamdp_result* out, uint32_t* ops_fp)

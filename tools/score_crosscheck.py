@@ -11,6 +11,9 @@ With --carry a third call, gamdp_carry_batch (gam_ngs_amd/csrc/gamdp_carry.hip: 
 carries the summary of the traceback that would start in it), checks the other half: every field of every gamdp_result -- begin,
 score, n_match, length, first and last match, homology, status -- and cells must equal gamdp_align_batch's; the line then also holds
 carry_mismatches, carry_kernels, carry_kernel_ms and carry_gcups.  Without the flag the output is what it was.
+--carry --walk-skip-pair / --walk-skip-i32: gamdp_align_batch runs with that walk-skip property on (gamdp_ctx_set_walk_skip_pair,
+gamdp_ctx_set_walk_skip_i32), so every field of its results is checked against a kernel that has no walk at all; the line then
+also holds the property's statistics of the last call.
 
 With --ops the edit strings are checked too.  gamdp_align_batch runs once more with edit strings (one buffer of |a| + |b| + 2 band +
 64 bytes per call, on the device and on the host: what limits the batch), the host fingerprints the bytes it returned
@@ -63,6 +66,7 @@ def main():
     ap.add_argument("--seed", type=int, default=20261019)
     ap.add_argument("--carry", action="store_true", help="also run gamdp_carry_batch and compare whole results")
     ap.add_argument("--walk-skip-pair", action="store_true", help="with --carry: gamdp_align_batch runs with gamdp_ctx_set_walk_skip_pair(GAMDP_WALK_SKIP_DIAG)")
+    ap.add_argument("--walk-skip-i32", action="store_true", help="with --carry: gamdp_align_batch runs with gamdp_ctx_set_walk_skip_i32(GAMDP_WALK_SKIP_DIAG)")
     ap.add_argument("--ops", action="store_true", help="also run gamdp_carry_ops_batch and compare the fingerprints of gamdp_align_batch's edit strings")
     ap.add_argument("--device-fp", action="store_true", help="with --ops: the align side's fingerprints from gamdp_align_batch_fp (the strings stay on the device)")
     ap.add_argument("--host-fp-too", action="store_true", help="with --ops --device-fp: also the download path of plain --ops, alternating with it")
@@ -74,10 +78,15 @@ def main():
         ap.error("one of --pairs N or --mixed N")
     if args.walk_skip_pair and not args.carry:
         ap.error("--walk-skip-pair goes with --carry")
+    if args.walk_skip_i32 and not args.carry:
+        ap.error("--walk-skip-i32 goes with --carry")
     ctx = gam.Context(0)
     skip_pair = None
     if args.walk_skip_pair:   # the two-task kernel's walks jump over indel-free groups: checked call by call against gamdp_carry_batch
         ctx.set_walk_skip_pair(L.WALK_SKIP_DIAG)
+    skip_i32 = None
+    if args.walk_skip_i32:    # ... and those of the int32 direction-free kernels
+        ctx.set_walk_skip_i32(L.WALK_SKIP_DIAG)
     if args.mixed:
         import _mixed
         seqs, calls = _mixed.mixed_batch(args.seed, max(1, args.mixed // 8), 8, band=args.band)
@@ -128,6 +137,8 @@ def main():
         a_ms = ctx.kernel_time(reset=True)[0]
         if args.walk_skip_pair:
             skip_pair = ctx.walk_skip_pair_stats()
+        if args.walk_skip_i32:
+            skip_i32 = ctx.walk_skip_i32_stats()
         rc = ctx.lib.gamdp_score_batch(ctx.handle, sset.handle, sset.handle, tasks, n, sc)
         assert rc == 0, ("gamdp_score_batch", rc, ctx.last_error())
         s_ms = ctx.kernel_time(reset=True)[0]
@@ -197,6 +208,8 @@ def main():
                    carry_kernel_ms=[round(v, 3) for v in carry_ms], carry_gcups=round(cells / med(carry_ms) / 1e6, 1))
     if args.walk_skip_pair:
         rec.update(walk_skip_pair=skip_pair)
+    if args.walk_skip_i32:
+        rec.update(walk_skip_i32=skip_i32)
     if args.ops:
         rec.update(ops_mismatches=ops_mismatches, ops_first_mismatch=ops_first_bad, ops_kernels=[r["kernel"] for r in ctx.carry_ops_info()],
                    ops_kernel_ms=[round(v, 3) for v in ops_ms], align_ops_kernel_ms=[round(v, 3) for v in align_ops_ms],

@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""A/B of the int32 direction-free kernels' walk modes (gamdp_ctx_set_walk_skip_i32): GAMDP_WALK_STRIPS against GAMDP_WALK_SKIP_DIAG,
+alternating on ONE context, one batch per row, one kernel per process (the planner's switches are read once per process):
+
+    --cell c17     k_align<17,4,false>      band 512   GAMDP_NO_PAIR=1
+    --cell c17n    k_align<17,4,true>       band 512   (every pair holds an N)
+    --cell q19     k_align_q<19,15,false>   band 150   GAMDP_NO_PAIR=1 GAMDP_QUAD_MIN=1
+    --cell q19n    k_align_q<19,15,true>    band 150   GAMDP_QUAD_MIN=1 (every pair holds an N)
+    --cell gen9    k_align<9,-1,true>       band 200
+    --cell gen17   k_align<17,-1,true>      band 300
+
+The tool says which environment a cell needs and stops when the launches of a row are not that kernel's.
+
+Rows: 50 kb and 5 kb pairs, identical, at 0.04 % indels, at 0.2 % indels and at config 5's 3 % substitutions + 1 % + 1 % indels.
+Per row: kernel time of the call (gamdp_ctx_kernel_time) in either mode, median and range; whether the results of the two modes are
+the same bytes; the device's counts; with --carry the results of the `on` mode against gamdp_carry_batch.
+
+    python tools/walk_skip_i32_ab.py --cell gen9 [--reps 5] [--scale 1.0] [--lengths 50k,5k] [--carry] [--json]
+
+--scale shrinks the pair counts (a quick look)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import gam_ngs_amd as gam  # noqa: E402
+from gam_ngs_amd import lib as L  # noqa: E402
+from srchash import source_hash  # noqa: E402
+from walk_skip_ab import diverged  # noqa: E402
+
+DIVERGENCES = ((0.0, 0.0, 0.0), (0.0, 0.02, 0.02), (0.0, 0.1, 0.1), (3.0, 1.0, 1.0))
+# cell -> (kernel, band, every pair holds an N, environment)
+CELLS = {
+    "c17":   ("k_align<17,4,false>", 512, False, {"GAMDP_NO_PAIR": "1"}),
+    "c17n":  ("k_align<17,4,true>", 512, True, {}),
+    "q19":   ("k_align_q<19,15,false>", 150, False, {"GAMDP_NO_PAIR": "1", "GAMDP_QUAD_MIN": "1"}),
+    "q19n":  ("k_align_q<19,15,true>", 150, True, {"GAMDP_QUAD_MIN": "1"}),
+    "gen9":  ("k_align<9,-1,true>", 200, False, {}),
+    "gen17": ("k_align<17,-1,true>", 300, False, {}),
+}
+PAIRS = {"50k": (50000, 4096), "5k": (5000, 32768)}   # pairs per row
+
+
+def workload(ctx, rng, n_pairs, length, div, band, with_n):
+    sub, ins, dele = (v / 100.0 for v in div)
+    seqs, blens = [], []
+    step = max(1, (32 << 20) // length)    # ~32 M bases at a time
+    for first in range(0, n_pairs, step):
+        n = min(step, n_pairs - first)
+        A = rng.integers(0, 4, n * length, dtype=np.uint8)
+        Bs, lens = diverged(rng, A, n, length, sub, ins, dele)
+        if with_n:                         # one N in the middle of every a: the call goes to the N-aware kernel, the path crosses an N-base pair
+            A[length // 2::length] = 4
+        at = 0
+        for k in range(n):
+            seqs.append(A[k * length:(k + 1) * length].tobytes())
+            seqs.append(Bs[at:at + lens[k]].tobytes())
+            at += int(lens[k])
+            blens.append(int(lens[k]))
+    sset = gam.SequenceSet(ctx, seqs, ascii=False)
+    tasks = (L.Task * n_pairs)()
+    for k in range(n_pairs):
+        t = tasks[k]
+        t.a_id, t.b_id, t.band = 2 * k, 2 * k + 1, band
+        t.begin_a, t.end_a, t.begin_b, t.end_b = 0, length - 1, 0, max(blens[k], 1) - 1
+    return sset, tasks
+
+
+def one_row(ctx, kernel, name, sset, tasks, n, div, reps, carry):
+    modes = (L.WALK_STRIPS, L.WALK_SKIP_DIAG)
+    outs = {m: (L.Result * n)() for m in modes}
+    first = None
+    ms = {m: [] for m in modes}
+    stats, different = {}, 0
+    for rep in range(reps + 1):            # (rep 0 warms up)
+        for mode in modes:
+            ctx.set_walk_skip_i32(mode)
+            ctx.kernel_time(reset=True)
+            rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, outs[mode], None)
+            assert rc == 0, (rc, ctx.last_error())
+            if rep:
+                ms[mode].append(ctx.kernel_time()[0])
+            raw = C.string_at(outs[mode], C.sizeof(outs[mode]))
+            if first is None:
+                first = raw
+            different += raw != first
+            if rep == reps:
+                stats[mode] = ctx.walk_skip_i32_stats()
+                kernels = sorted({r["kernel"] for r in ctx.launch_info()})
+    ctx.set_walk_skip_i32(L.WALK_STRIPS)
+    if kernels != [kernel]:
+        sys.exit("the row ran %s, not %s alone: set the cell's environment (see --help)" % (kernels, kernel))
+    on = stats[L.WALK_SKIP_DIAG]
+    rec = dict(workload=name, kernel=kernel, calls=n, sub=div[0], ins=div[1], dele=div[2], results_differ=different,
+               strips_off=stats[L.WALK_STRIPS]["strips"], strips_on=on["strips"], stats_on=on)
+    for mode, key in ((L.WALK_STRIPS, "off"), (L.WALK_SKIP_DIAG, "on")):
+        v = sorted(ms[mode])
+        rec["ms_" + key] = dict(median=round(v[len(v) // 2], 2), min=round(v[0], 2), max=round(v[-1], 2))
+    if carry:
+        ca = (L.Result * n)()
+        rc = ctx.lib.gamdp_carry_batch(ctx.handle, sset.handle, sset.handle, tasks, n, ca)
+        assert rc == 0, (rc, ctx.last_error())
+        whole = lambda r: r.key() + (r.cells,)  # noqa: E731
+        res = outs[L.WALK_SKIP_DIAG]
+        rec["carry_mismatches"] = sum(1 for i in range(n) if whole(res[i]) != whole(ca[i]))
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cell", required=True, choices=sorted(CELLS))
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--lengths", default="50k,5k")
+    ap.add_argument("--carry", action="store_true")
+    ap.add_argument("--json", action="store_true")
+    args = ap.parse_args()
+    assert args.reps >= 1
+    kernel, band, with_n, env = CELLS[args.cell]
+    missing = {k: v for k, v in env.items() if os.environ.get(k) != v}
+    if missing:
+        sys.exit("--cell %s needs %s in the environment" % (args.cell, " ".join("%s=%s" % kv for kv in sorted(missing.items()))))
+    ctx = gam.Context(0)
+    rows = []
+    print("source %s, %s band %d, %d calls per mode after a warm-up, kernel ms: median (min - max)" % (source_hash(), kernel, band, args.reps), flush=True)
+    print("%-16s %-13s %8s %9s %11s %11s  %-24s %-24s %s" % ("workload", "sub/ins/del %", "strips", "strips on", "grp tested", "grp skipped",
+                                                          "ms off", "ms on", "on/off"), flush=True)
+    for w in args.lengths.split(","):
+        length, n_full = PAIRS[w]
+        n = max(8, int(n_full * args.scale)) & ~3
+        for di, div in enumerate(DIVERGENCES):
+            rng = np.random.default_rng(20261020 + di)
+            sset, tasks = workload(ctx, rng, n, length, div, band, with_n)
+            name = "%d x %s" % (n, w.replace("k", " kb"))
+            rec = one_row(ctx, kernel, name, sset, tasks, n, div, args.reps, args.carry)
+            sset.close()
+            rows.append(rec)
+            f = lambda d: "%.2f (%.2f - %.2f)" % (d["median"], d["min"], d["max"])  # noqa: E731
+            print("%-16s %-13s %8d %9d %11d %11d  %-24s %-24s %.3f%s%s" % (
+                name, "%g/%g/%g" % div, rec["strips_off"], rec["strips_on"], rec["stats_on"]["groups_tested"],
+                rec["stats_on"]["groups_skipped"], f(rec["ms_off"]), f(rec["ms_on"]), rec["ms_on"]["median"] / rec["ms_off"]["median"],
+                "  RESULTS DIFFER in %d calls" % rec["results_differ"] if rec["results_differ"] else "",
+                ("  carry mismatches %d" % rec["carry_mismatches"]) if args.carry else ""), flush=True)
+    if args.json:
+        print(json.dumps(dict(source=source_hash(), cell=args.cell, kernel=kernel, band=band, reps=args.reps, rows=rows)))
+    bad = sum(r["results_differ"] for r in rows) + sum(r.get("carry_mismatches", 0) for r in rows)
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
