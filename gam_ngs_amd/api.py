@@ -111,6 +111,20 @@ class Context:
         _check(self, self.lib.gamdp_ctx_walk_skip_i32_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_i32_stats")
         return st.as_dict()
 
+    def set_walk_skip_backoff(self, mode: int):
+        """Whether walks in L.WALK_SKIP_DIAG mode of any of the three properties above back off from the test after failures, a
+        fourth property: L.WALK_BACKOFF_OFF (the default: every candidate point is tested) or L.WALK_BACKOFF_ON (after `fails` tests
+        in a row that skipped nothing, the next gamdp_walk_skip_backoff_hold(fails) points pass without a test;
+        gamdp_ctx_set_walk_skip_backoff).  The results do not depend on it."""
+        _check(self, self.lib.gamdp_ctx_set_walk_skip_backoff(self.handle, mode), "gamdp_ctx_set_walk_skip_backoff")
+
+    def walk_skip_backoff_stats(self):
+        """The candidate points the walks of the last gamdp_align_batch on this context passed without a test, per kernel family, as a
+        dict (gamdp_ctx_walk_skip_backoff_stats)."""
+        st = L.WalkSkipBackoffStats()
+        _check(self, self.lib.gamdp_ctx_walk_skip_backoff_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_backoff_stats")
+        return st.as_dict()
+
     def l1_tail_calls(self):
         """The tail alignments of the last alignMergeBlocks on this context and the seed each was given, as
         (merge_block, right, begin_a, source) tuples ordered by merge block, left before right (gamdp_ctx_l1_tail_calls)."""
@@ -316,6 +330,22 @@ class MultiContext:
             st = L.WalkSkipI32Stats()
             if self.lib.gamdp_ctx_walk_skip_i32_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
                 raise L.GamdpError("gamdp_ctx_walk_skip_i32_stats failed on context %d" % i)
+            out.append(st.as_dict())
+        return out
+
+    def set_walk_skip_backoff(self, mode: int, which=None):
+        """Context.set_walk_skip_backoff on every context of the handle, or on context `which` alone."""
+        for i in (range(len(self.devices)) if which is None else (which,)):
+            if self.lib.gamdp_ctx_set_walk_skip_backoff(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
+                raise L.GamdpError("gamdp_ctx_set_walk_skip_backoff(%r) failed on context %d" % (mode, i))
+
+    def walk_skip_backoff_stats(self):
+        """Context.walk_skip_backoff_stats of every context of the handle (a list of dicts)."""
+        out = []
+        for i in range(len(self.devices)):
+            st = L.WalkSkipBackoffStats()
+            if self.lib.gamdp_ctx_walk_skip_backoff_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
+                raise L.GamdpError("gamdp_ctx_walk_skip_backoff_stats failed on context %d" % i)
             out.append(st.as_dict())
         return out
 

@@ -92,7 +92,8 @@ struct LaunchParams {
 // (LS_SKIP_*: the eight-task kernel's walks in LP_WALK_SKIP_DIAG launches -- tests made, groups whose equality was evaluated, groups
 // jumped over, and the rows by which the jumped-over spans fall short of 64 each (the span below a walk's end cell ends on the next
 // checkpoint row: 1 .. 64 rows) -- rows = 64 groups - short, which keeps the words 32 bits wide; gamdp_ctx_walk_skip_stats)
-enum : int { LS_UNITS = 0, LS_DIRFREE, LS_PACKED_TOP, LS_PACKED_TOP_MIXED, LS_STRIPS, LS_TOP_WANTED, LS_SKIP_TESTS, LS_SKIP_TESTED, LS_SKIP_GROUPS, LS_SKIP_SHORT, LS_COUNT = 12 };
+enum : int { LS_UNITS = 0, LS_DIRFREE, LS_PACKED_TOP, LS_PACKED_TOP_MIXED, LS_STRIPS, LS_TOP_WANTED, LS_SKIP_TESTS, LS_SKIP_TESTED, LS_SKIP_GROUPS, LS_SKIP_SHORT, LS_SKIP_HELD, LS_COUNT = 12 };
+// (LS_SKIP_HELD: candidate points a walk passed without a test, LP_WALK_SKIP_BACKOFF below; gamdp_ctx_walk_skip_backoff_stats)
 // the eight-task kernel's walks test for indel-free groups before they ask for a strip (kernel_walk.inc, walk_many<..., SKIP>):
 // set by the host for contexts in GAMDP_WALK_SKIP_DIAG mode; every other kernel ignores it
 constexpr u32 LP_WALK_SKIP_DIAG = 32;
@@ -104,6 +105,32 @@ constexpr u32 LP_WALK_SKIP_PAIR = 64;
 // PK == false): set by the host for launches of k_align<17,4>, k_align_q<19,15> (N-aware or not), k_align<9,-1,true> and
 // k_align<17,-1,true> of contexts in GAMDP_WALK_SKIP_DIAG mode of gamdp_ctx_set_walk_skip_i32; every other kernel ignores it.
 constexpr u32 LP_WALK_SKIP_I32 = 128;
+// The walks that make the diagonal test back off from it after failures (gamdp_ctx_set_walk_skip_backoff): set by the host beside one of
+// the three flags above, read by the SKIP instances alone.  A walk counts the tests in a row that skipped nothing (`fails`) and passes
+// its next walk_backoff_hold(fails) candidate points without a test and without a load, as after a failed test; a test that skips a
+// group puts the count back to 0.  The indel rate of a pair is about the same all along it, and a failed test is a serial memory round
+// trip in front of the strip call it did not save.
+constexpr u32 LP_WALK_SKIP_BACKOFF = 4;
+// ... the schedule: 2^fails - 1 candidate points, WALK_BACKOFF_HOLD_MAX at the most (DESIGN.md section 6 has the sweep behind the value).
+// The device code and gamdp_walk_skip_backoff_hold (gamdp_host.cpp) both read it.
+#ifndef GAMDP_WALK_BACKOFF_HOLD_MAX   // (the sweep builds one library per value)
+#define GAMDP_WALK_BACKOFF_HOLD_MAX 15
+#endif
+constexpr u32 WALK_BACKOFF_HOLD_MAX = GAMDP_WALK_BACKOFF_HOLD_MAX;
+constexpr u32 walk_backoff_hold(const u32 fails)
+{
+    const u32 full = fails >= 32u ? 0xFFFFFFFFu : (1u << fails) - 1u;
+    return full < WALK_BACKOFF_HOLD_MAX ? full : WALK_BACKOFF_HOLD_MAX;
+}
+// A walk's two values in one word (walk_many keeps them in its task's WalkCarry between calls): fails in bits 0-5, never counted past
+// WALK_BACKOFF_FAILS_CAP (the schedule is constant from there on), hold in the bits above.
+constexpr u32 WALK_BACKOFF_FAILS_CAP = 32, WALK_BACKOFF_HOLD_SHIFT = 6;
+static_assert(WALK_BACKOFF_HOLD_MAX < (1u << (31 - WALK_BACKOFF_HOLD_SHIFT)), "hold fits the word beside fails, sign bit clear");
+constexpr u32 walk_backoff_after_fail(const u32 state)   // the word after a test that skipped nothing
+{
+    const u32 f = (state & 63u) < WALK_BACKOFF_FAILS_CAP ? (state & 63u) + 1u : WALK_BACKOFF_FAILS_CAP;
+    return f | (walk_backoff_hold(f) << WALK_BACKOFF_HOLD_SHIFT);
+}
 // the two-task kernel walks its two tasks side by side (kernel_walk.inc) instead of one after the other: set by the host for
 // launches of at most two rounds, where the wavefronts of a SIMD walk at the same time and the scalar unit is the bottleneck
 constexpr u32 LP_WALK_SIDE_BY_SIDE = 1;

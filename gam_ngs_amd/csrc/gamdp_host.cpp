@@ -90,6 +90,7 @@ const Tuning& tuning()
         if ((e = std::getenv("GAMDP_WALK_SKIP"))) x.walk_skip = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_WALK_SKIP_PAIR"))) x.walk_skip_pair = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_WALK_SKIP_I32"))) x.walk_skip_i32 = std::atoi(e) == 1;
+        if ((e = std::getenv("GAMDP_WALK_SKIP_BACKOFF"))) x.walk_skip_backoff = std::atoi(e) == 1;
         return x;
     }();
     return t;
@@ -313,6 +314,7 @@ int Ctx::init(int dev)
     walk_skip = tuning().walk_skip ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
     walk_skip_pair = tuning().walk_skip_pair ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
     walk_skip_i32 = tuning().walk_skip_i32 ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
+    walk_skip_backoff = tuning().walk_skip_backoff ? GAMDP_WALK_BACKOFF_ON : GAMDP_WALK_BACKOFF_OFF;
     if (hipSetDevice(dev) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("hipGetDeviceProperties failed"); return GAMDP_ENODEV; }
@@ -876,7 +878,7 @@ static bool walks_on_i32_images(const int kid)
 }
 
 // LaunchParams::flags / prio_* of a launch
-static void launch_policy(const Launch& L, LaunchParams& p, const int walk_skip, const int walk_skip_pair, const int walk_skip_i32)
+static void launch_policy(const Launch& L, LaunchParams& p, const int walk_skip, const int walk_skip_pair, const int walk_skip_i32, const int walk_skip_backoff)
 {
     const Tuning& tu = tuning();
     const u64 tpw = (u64)kernel_info[L.kid].tasks_per_wave, units = L.count / tpw;
@@ -886,6 +888,8 @@ static void launch_policy(const Launch& L, LaunchParams& p, const int walk_skip,
     if (L.kid == K_O19_CE15 && walk_skip == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_DIAG;   // (gamdp_ctx_set_walk_skip; the eight-task kernel alone has the test)
     if (L.kid == K_P17_CE4 && walk_skip_pair == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_PAIR;   // (gamdp_ctx_set_walk_skip_pair; the two-task kernel, both of its walk paths)
     if (walks_on_i32_images(L.kid) && walk_skip_i32 == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_I32;   // (gamdp_ctx_set_walk_skip_i32; the six int32 direction-free kernels)
+    // (gamdp_ctx_set_walk_skip_backoff: only beside a test to back off from)
+    if (walk_skip_backoff == GAMDP_WALK_BACKOFF_ON && (p.flags & (LP_WALK_SKIP_DIAG | LP_WALK_SKIP_PAIR | LP_WALK_SKIP_I32))) p.flags |= LP_WALK_SKIP_BACKOFF;
     // the end-cell / strip / walk phase of the two- and eight-task kernels issues one level above a steady-state fill in
     // launches of more than two rounds (gamdp_dev.h; GAMDP_WALK_PRIO=0..3 overrides, A/B)
     p.flags |= (tu.walk_prio >= 0 ? (u32)tu.walk_prio : (units > 2ull * L.n_slots ? 1u : 0u)) << LP_WALK_PRIO_SHIFT;
@@ -943,7 +947,7 @@ int Ctx::align_run(AlignCall& a)
         p.scratch = d_scratch + L.scratch_off; p.slot_words = L.slot_words; p.dir_words = L.dir_words; p.ypad = L.ypad;
         p.ckpt_off = L.ckpt_off; p.bnd_off = L.bnd_off;
         p.stats = d_stats + li * LS_COUNT;
-        launch_policy(L, p, walk_skip, walk_skip_pair, walk_skip_i32);
+        launch_policy(L, p, walk_skip, walk_skip_pair, walk_skip_i32, walk_skip_backoff);
         hipStream_t const on = L.aux ? aux_stream : stream;
         HIPCHK(this, hipEventRecord(events[li].first, on));
         const int e = launch_align(L.kid, p, L.n_slots, L.dyn_lds, on);
@@ -1010,6 +1014,7 @@ void Ctx::align_collect(AlignCall& a)
                 W.tests += st[LS_SKIP_TESTS]; W.groups_tested += st[LS_SKIP_TESTED]; W.groups_skipped += st[LS_SKIP_GROUPS];
                 W.rows_skipped += 64ull * st[LS_SKIP_GROUPS] - st[LS_SKIP_SHORT];
                 W.strips += st[LS_STRIPS];
+                last_walk_skip_backoff.held += st[LS_SKIP_HELD];   // gamdp_ctx_walk_skip_backoff_stats, family by family
             }
             if (L.kid == K_P17_CE4) {   // gamdp_ctx_walk_skip_pair_stats: the two-task launches of the call
                 gamdp_walk_skip_pair_stats& W = last_walk_skip_pair;
@@ -1018,6 +1023,7 @@ void Ctx::align_collect(AlignCall& a)
                 W.strips += st[LS_STRIPS];
                 if (walks_side_by_side(L)) W.launches_side_by_side++; else W.launches_one_by_one++;
                 W.mode = (uint32_t)walk_skip_pair;   // (everything stays 0 when the call makes no two-task launch)
+                last_walk_skip_backoff.held_pair += st[LS_SKIP_HELD];
             }
             if (walks_on_i32_images(L.kid)) {   // gamdp_ctx_walk_skip_i32_stats: the call's launches of the six int32 direction-free kernels
                 gamdp_walk_skip_i32_stats& W = last_walk_skip_i32;
@@ -1026,6 +1032,7 @@ void Ctx::align_collect(AlignCall& a)
                 W.strips += st[LS_STRIPS];
                 W.launches++;
                 W.mode = (uint32_t)walk_skip_i32;   // (everything stays 0 when the call makes no such launch)
+                last_walk_skip_backoff.held_i32 += st[LS_SKIP_HELD];
             }
             r.piece = log_piece;
             r.rounds = L.n_slots ? (double)r.units / (double)L.n_slots : 0.0;
@@ -1362,6 +1369,8 @@ int Ctx::align_fp(const gamdp_task* tasks, const SeqSet* sa, const SeqSet* sb, c
         last_walk_skip.mode = (uint32_t)walk_skip;
         last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
         last_walk_skip_i32 = gamdp_walk_skip_i32_stats{};
+        last_walk_skip_backoff = gamdp_walk_skip_backoff_stats{};
+        last_walk_skip_backoff.mode = (uint32_t)walk_skip_backoff;
         if ((rc_ = align(src, cnt, out + first, nullptr, caps.data() + first))) return rc_;
         // the strings of the chunk: where align() put them (w_prep), how long the walks made them (out)
         fpt.clear(); seg_first.clear();
@@ -1628,6 +1637,26 @@ int gamdp_ctx_walk_skip_i32_stats(const gamdp_ctx* ctx, gamdp_walk_skip_i32_stat
     return 0;
 }
 
+static_assert(sizeof(gamdp_walk_skip_backoff_stats) == 32 && offsetof(gamdp_walk_skip_backoff_stats, held_pair) == 8 &&
+              offsetof(gamdp_walk_skip_backoff_stats, held_i32) == 16 && offsetof(gamdp_walk_skip_backoff_stats, mode) == 24,
+              "gamdp_walk_skip_backoff_stats: the layout include/gamdp.h documents (gam_ngs_amd/lib.py WalkSkipBackoffStats mirrors it)");
+
+int gamdp_ctx_set_walk_skip_backoff(gamdp_ctx* ctx, int mode)
+{
+    if ((mode != GAMDP_WALK_BACKOFF_OFF && mode != GAMDP_WALK_BACKOFF_ON) || !ctx) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->walk_skip_backoff = mode;
+    return 0;
+}
+
+uint32_t gamdp_walk_skip_backoff_hold(uint32_t fails) { return walk_backoff_hold(fails); }   // (gamdp_dev.h: what the walks read)
+
+int gamdp_ctx_walk_skip_backoff_stats(const gamdp_ctx* ctx, gamdp_walk_skip_backoff_stats* out)
+{
+    if (!ctx || !out) return GAMDP_EINVAL;
+    *out = reinterpret_cast<const Ctx*>(ctx)->last_walk_skip_backoff;
+    return 0;
+}
+
 int gamdp_seqset_create(gamdp_ctx* ctx, const uint8_t* const* seqs, const uint64_t* lens, uint32_t n, int is_ascii,
                         gamdp_seqset** out)
 {
@@ -1670,6 +1699,8 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     c->last_walk_skip.mode = (uint32_t)c->walk_skip;
     c->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
     c->last_walk_skip_i32 = gamdp_walk_skip_i32_stats{};
+    c->last_walk_skip_backoff = gamdp_walk_skip_backoff_stats{};
+    c->last_walk_skip_backoff.mode = (uint32_t)c->walk_skip_backoff;
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; for (Ctx* h : c->helpers) h->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {
@@ -1707,6 +1738,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     cc[1]->walk_skip = c->walk_skip; cc[1]->last_walk_skip = gamdp_walk_skip_stats{};
     cc[1]->walk_skip_pair = c->walk_skip_pair; cc[1]->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
     cc[1]->walk_skip_i32 = c->walk_skip_i32; cc[1]->last_walk_skip_i32 = gamdp_walk_skip_i32_stats{};
+    cc[1]->walk_skip_backoff = c->walk_skip_backoff; cc[1]->last_walk_skip_backoff = gamdp_walk_skip_backoff_stats{};
     int rc[2] = {0, 0};
     auto worker = [&](int t) noexcept {
         for (size_t k = (size_t)t; k < 4 && rc[t] == 0; k += 2) {
@@ -1740,6 +1772,11 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
         W.tests += H.tests; W.groups_tested += H.groups_tested; W.groups_skipped += H.groups_skipped; W.rows_skipped += H.rows_skipped; W.strips += H.strips;
         W.launches += H.launches;
         W.mode |= H.mode;   // (the same)
+    }
+    {
+        gamdp_walk_skip_backoff_stats& W = c->last_walk_skip_backoff;
+        const gamdp_walk_skip_backoff_stats& H = cc[1]->last_walk_skip_backoff;
+        W.held += H.held; W.held_pair += H.held_pair; W.held_i32 += H.held_i32;
     }
     std::stable_sort(c->launch_log.begin(), c->launch_log.end(), [](const gamdp_launch_info& x, const gamdp_launch_info& y) { return x.piece < y.piece; });
     if (rc[1]) c->set_error(cc[1]->err);
@@ -1850,6 +1887,8 @@ int gamdp_align_batch_fp(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_
     c->last_walk_skip.mode = (uint32_t)c->walk_skip;
     c->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
     c->last_walk_skip_i32 = gamdp_walk_skip_i32_stats{};
+    c->last_walk_skip_backoff = gamdp_walk_skip_backoff_stats{};
+    c->last_walk_skip_backoff.mode = (uint32_t)c->walk_skip_backoff;
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {

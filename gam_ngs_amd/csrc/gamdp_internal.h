@@ -60,6 +60,7 @@ struct Tuning {
     bool walk_skip = false;             // GAMDP_WALK_SKIP=1: new contexts start in GAMDP_WALK_SKIP_DIAG mode (gamdp_ctx_set_walk_skip)
     bool walk_skip_pair = false;        // GAMDP_WALK_SKIP_PAIR=1: ... and in GAMDP_WALK_SKIP_DIAG mode of gamdp_ctx_set_walk_skip_pair
     bool walk_skip_i32 = false;         // GAMDP_WALK_SKIP_I32=1: ... and of gamdp_ctx_set_walk_skip_i32
+    bool walk_skip_backoff = false;     // GAMDP_WALK_SKIP_BACKOFF=1: new contexts start in GAMDP_WALK_BACKOFF_ON mode (gamdp_ctx_set_walk_skip_backoff)
 };
 const Tuning& tuning();
 
@@ -229,6 +230,10 @@ struct Ctx {
     // ... and for the int32 direction-free kernels, a third property (gamdp_ctx_set_walk_skip_i32 -> LP_WALK_SKIP_I32)
     int walk_skip_i32 = GAMDP_WALK_STRIPS;
     gamdp_walk_skip_i32_stats last_walk_skip_i32{};
+    // whether the walks of those three back off from the test after failures, a fourth property that applies to whichever of them is
+    // on (gamdp_ctx_set_walk_skip_backoff -> LP_WALK_SKIP_BACKOFF), and the candidate points the last gamdp_align_batch did not test
+    int walk_skip_backoff = GAMDP_WALK_BACKOFF_OFF;
+    gamdp_walk_skip_backoff_stats last_walk_skip_backoff{};
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }

@@ -374,7 +374,7 @@ __device__ __forceinline__ void finish_many(const LaunchParams& p, const u32 fir
                     if (p.flags & LP_WALK_SKIP_PAIR) { walk_pair_skip<C, CE>(&ta, &tb, wcs, skip, lane, &p); need = 0; }
                     else need = (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
                 } else if constexpr (PK && NT == 8 && LPT == QL) {
-                    need = skip_diag ? (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT, true>(&ta, &tb, wcs, skip, lane, lds_tk, p.stats))
+                    need = skip_diag ? (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT, true>(&ta, &tb, wcs, skip | ((p.flags & LP_WALK_SKIP_BACKOFF) ? WM_BACKOFF : 0), lane, lds_tk, p.stats))
                                      : (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
                 } else need = (u32)uni((int)walk_many<C, CE, HASN, PK, NT, LPT>(&ta, &tb, wcs, skip, lane, lds_tk));
                 if (need == 0) break;

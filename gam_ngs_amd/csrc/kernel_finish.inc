@@ -205,7 +205,15 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
             // what this walk counted (LS_SKIP_*).  Diagnostics that count strips keep their strips.
             [[maybe_unused]] int sk_fail_at = -1;
             [[maybe_unused]] const bool sk_on = !(dt_flags & TF_DIAG_COUNT_MAT);
-            [[maybe_unused]] u32 sk_tests = 0, sk_tested = 0, sk_groups = 0, sk_short = 0;
+            [[maybe_unused]] u32 sk_tests = 0, sk_tested = 0, sk_groups = 0, sk_short = 0, sk_held = 0;
+            // LP_WALK_SKIP_BACKOFF (gamdp_dev.h has the rule): tests in a row that skipped nothing, and the candidate points that still pass
+            // without a test.  A walk that walk_many began goes on from what that left in the carry (0 | 0 from end_cell else).
+            [[maybe_unused]] const bool backoff = SKIP && (uni((int)pp->flags) & (int)LP_WALK_SKIP_BACKOFF) != 0;
+            [[maybe_unused]] u32 bo_fails = 0, bo_hold = 0;
+            if constexpr (SKIP) {
+                const u32 bo0 = (u32)uni(wcp->early_seq);
+                bo_fails = bo0 & 63u; bo_hold = bo0 >> WALK_BACKOFF_HOLD_SHIFT;
+            }
             auto get_word = [&](const int blk, const int l_, const int c_) -> u32 {
                 const int g = c_ >> 2;
                 int k = cblk0 - blk;
@@ -342,8 +350,12 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                         // into the untagged ring of do_block_df.  With four tasks per wavefront the lanes of the row are lane_base + l;
                         // all 64 lanes of the wavefront still take a span each, the walk has the wavefront to itself.
                         const int strip = ST::strip_of(lane_base + l, t.sshift);
-                        if (sk_on && blk >= t.df_lo && blk < t.df_hi && sk_fail_at != mat_calls && !(blk >= mat_lo && blk <= mat_hi) &&
-                            !(strip == old_q && blk >= old_lo && blk <= old_hi)) {
+                        const bool sk_cand = sk_on && blk >= t.df_lo && blk < t.df_hi && sk_fail_at != mat_calls && !(blk >= mat_lo && blk <= mat_hi) &&
+                                             !(strip == old_q && blk >= old_lo && blk <= old_hi);
+                        if (sk_cand && backoff && bo_hold != 0u) {   // held: no test, no load -- on as after a failed one
+                            bo_hold--; sk_held++;
+                            sk_fail_at = mat_calls;
+                        } else if (sk_cand) {
                             constexpr int UNIT = PK ? 1 : 4;                                 // what the checkpoint rows count in: G or G4
                             const int gi = blk >> 2, d0 = (tau & 63) + 1;                    // checkpoint gi: d0 steps below the walk
                             const int g_lo = t.df_lo >> 2, g_top = (t.df_hi >> 2) - 1;       // the groups whose checkpoint rows the fill stored
@@ -447,9 +459,14 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                                 x -= n; pos -= n; len += (u32)n;
                                 sk_groups += (u32)np; sk_short += (u32)(64 - d0);
                                 cblk0 = -1; cl = -1; cg = -1;   // the cached direction words are those of the blocks the walk has left
+                                bo_fails = 0u;
                                 continue;                       // round again: the next test, directions, or row 0 / pos == 0
                             }
                             sk_fail_at = mat_calls;
+                            if (backoff) {
+                                bo_fails = bo_fails < WALK_BACKOFF_FAILS_CAP ? bo_fails + 1u : WALK_BACKOFF_FAILS_CAP;
+                                bo_hold = walk_backoff_hold(bo_fails);
+                            }
                         }
                     }
                     const u32 w_here = get_word(blk, l, c);  // (re)fills the cache / materialises the strip if needed
@@ -573,6 +590,7 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                     atomicAdd(unip(pp->stats) + LS_SKIP_GROUPS, sk_groups);
                     if (sk_short != 0) atomicAdd(unip(pp->stats) + LS_SKIP_SHORT, sk_short);
                 }
+                if (pp->stats != nullptr && lane == 0 && sk_held != 0) atomicAdd(unip(pp->stats) + LS_SKIP_HELD, sk_held);   // (gamdp_ctx_walk_skip_backoff_stats)
             }
             if (dt_flags & TF_DIAG_COUNT_MAT) {  // diagnostics only: result unusable
                 res.n_match = (u32)mat_calls;

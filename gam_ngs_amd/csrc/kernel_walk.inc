@@ -30,6 +30,11 @@
 // the default one holds none of it): a walk that stands on a block without directions first asks whether the groups below it hold
 // nothing but diagonal steps, and jumps over those that do (the test sits where the inner loop finds `need`) before it is reported as
 // waiting for a strip.  skip_stats: the launch's statistics words (LS_SKIP_*), nullptr = not counted.
+// SKIP with WM_BACKOFF in skip_mask_ (LP_WALK_SKIP_BACKOFF, gamdp_dev.h has the rule): a task that is held passes its candidate point as
+// after a failed test, and an iteration whose candidate tasks are all held does not enter the test at all -- no load, no round trip.
+// The two values of a task's walk live in its carry's early_seq between calls (the chain walkers' field: no multi-task walk uses it,
+// end_cell zeroes it), as one word (walk_backoff_after_fail).
+constexpr int WM_BACKOFF = 1 << 8;   // (above the NT <= 8 task bits of skip_mask_)
 template <int C, int CE, bool HASN, bool PK, int NT, int LPT = QL, bool SKIP = false>
 __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* wcs, const int skip_mask_, const int lane, const Tk* tks = nullptr, u32* skip_stats = nullptr)
 {
@@ -76,14 +81,20 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
     bool active = g < NT && w0.status == 2 && !((skip_mask >> gt) & 1);
     // SKIP: a task whose test found no passing group waits for its strip (no second test before it has one); what this call counted
     [[maybe_unused]] bool stuck = false;
-    [[maybe_unused]] u32 sk_tests = 0, sk_tested = 0, sk_groups = 0, sk_short = 0;
+    [[maybe_unused]] u32 sk_tests = 0, sk_tested = 0, sk_groups = 0, sk_short = 0, sk_held = 0;
+    // ... and with WM_BACKOFF the task's fails | hold word (never touched without it)
+    [[maybe_unused]] const bool backoff = SKIP && (skip_mask & WM_BACKOFF) != 0;
+    [[maybe_unused]] u32 bo = SKIP ? (u32)w0.early_seq : 0u;
     [[maybe_unused]] auto count_skips = [&]() {
         if constexpr (SKIP) {
-            if (skip_stats != nullptr && j == 0 && g < NT && sk_tests != 0) {
-                atomicAdd(skip_stats + LS_SKIP_TESTS, sk_tests);
-                atomicAdd(skip_stats + LS_SKIP_TESTED, sk_tested);
-                atomicAdd(skip_stats + LS_SKIP_GROUPS, sk_groups);
-                if (sk_short != 0) atomicAdd(skip_stats + LS_SKIP_SHORT, sk_short);
+            if (skip_stats != nullptr && j == 0 && g < NT) {
+                if (sk_tests != 0) {
+                    atomicAdd(skip_stats + LS_SKIP_TESTS, sk_tests);
+                    atomicAdd(skip_stats + LS_SKIP_TESTED, sk_tested);
+                    atomicAdd(skip_stats + LS_SKIP_GROUPS, sk_groups);
+                    if (sk_short != 0) atomicAdd(skip_stats + LS_SKIP_SHORT, sk_short);
+                }
+                if (sk_held != 0) atomicAdd(skip_stats + LS_SKIP_HELD, sk_held);
             }
         }
     };
@@ -125,7 +136,12 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
             // 21), so the stored values are compared as they are.  Lane j of the task's 8 tests the j-th span below the walk (the
             // first one down to the next checkpoint row, 64 rows each after that); the walk jumps over the passing prefix.
             // (A strip change inside materialised groups -- blk0 within [mat_lo, mat_hi] -- is left to the strips.)
-            const bool cand = active && need && !stuck && !(blk0 >= mat_lo && blk0 <= mat_hi);
+            bool cand = active && need && !stuck && !(blk0 >= mat_lo && blk0 <= mat_hi);
+            if (backoff) {
+                // a held task passes the point as after a failed test; when every candidate task is held nobody enters the test below
+                const bool held = cand && (bo >> WALK_BACKOFF_HOLD_SHIFT) != 0u;
+                if (held) { bo -= 1u << WALK_BACKOFF_HOLD_SHIFT; stuck = true; sk_held++; cand = false; }
+            }
             if (__ballot(cand) != 0) {
                 typedef PairFmt<C, LPT> FMT;
                 gptr const ckpt = (gptr)pick64((u64)tap->ckpt, (u64)tbq->ckpt);   // the slot's checkpoint rows
@@ -204,7 +220,11 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
                         const int n = d0 + 64 * (k - 1);
                         x -= n; pos -= n; len += (u32)n;
                         sk_short += (u32)(64 - d0);
-                    } else stuck = true;
+                        if (backoff) bo = 0u;
+                    } else {
+                        stuck = true;
+                        if (backoff) bo = walk_backoff_after_fail(bo);
+                    }
                 }
                 if (__ballot(cand && k > 0) != 0) continue;   // round again: the next test, directions, or a task that has dropped out
             }
@@ -294,6 +314,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
             w.old_q = __builtin_amdgcn_readlane(old_q, L0); w.old_lo = __builtin_amdgcn_readlane(old_lo, L0); w.old_hi = __builtin_amdgcn_readlane(old_hi, L0);
             w.mat_calls = __builtin_amdgcn_readlane(mat_calls, L0);
             w.need_q = __builtin_amdgcn_readlane(strip, L0); w.need_ghi = __builtin_amdgcn_readlane(blk0 >> 2, L0);
+            w.early_seq = __builtin_amdgcn_readlane((int)bo, L0);
         }
         count_skips();
         u32 need = 0;
@@ -310,6 +331,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
             w.mat_q = mat_q; w.mat_lo = mat_lo; w.mat_hi = mat_hi; w.old_q = old_q; w.old_lo = old_lo; w.old_hi = old_hi;
             w.mat_calls = mat_calls;
             w.need_q = strip; w.need_ghi = blk0 >> 2;
+            if constexpr (SKIP) w.early_seq = (int)bo;
         }
         count_skips();
         u32 need = 0;
@@ -346,6 +368,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
             w.la = la; w.lb = lb; w.fa = fa; w.fb = fb; w.have = have;
             w.mat_q = mat_q; w.mat_lo = mat_lo; w.mat_hi = mat_hi; w.old_q = old_q; w.old_lo = old_lo; w.old_hi = old_hi;
             w.mat_calls = mat_calls;
+            if constexpr (SKIP) w.early_seq = (int)bo;
         }
         count_skips();
         return 0u;
@@ -362,6 +385,7 @@ __device__ __noinline__ u32 walk_many(const Tk* tap, const Tk* tbp, WalkCarry* w
         w.mat_q = __builtin_amdgcn_readlane(mat_q, L0); w.mat_lo = __builtin_amdgcn_readlane(mat_lo, L0); w.mat_hi = __builtin_amdgcn_readlane(mat_hi, L0);
         w.old_q = __builtin_amdgcn_readlane(old_q, L0); w.old_lo = __builtin_amdgcn_readlane(old_lo, L0); w.old_hi = __builtin_amdgcn_readlane(old_hi, L0);
         w.mat_calls = __builtin_amdgcn_readlane(mat_calls, L0);
+        if constexpr (SKIP) w.early_seq = __builtin_amdgcn_readlane((int)bo, L0);
     }
     return 0u;
 }
@@ -376,8 +400,9 @@ __device__ __noinline__ void walk_pair_skip(const Tk* tap, const Tk* tbp, WalkCa
 {
     typedef Strip<64, true> ST;
     u32* const skip_stats = unip(unip(pp)->stats);
+    const int mask = skip_mask | ((uni((int)unip(pp)->flags) & (int)LP_WALK_SKIP_BACKOFF) ? WM_BACKOFF : 0);
     for (;;) {
-        const u32 need = (u32)uni((int)walk_many<C, CE, false, true, 2, 64, true>(tap, tbp, wcs, skip_mask, lane, nullptr, skip_stats));
+        const u32 need = (u32)uni((int)walk_many<C, CE, false, true, 2, 64, true>(tap, tbp, wcs, mask, lane, nullptr, skip_stats));
         if (need == 0) break;
 #pragma unroll 1
         for (u32 rest = need; rest != 0; rest &= rest - 1) {

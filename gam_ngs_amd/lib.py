@@ -27,6 +27,7 @@ SYMBOLS = [
     "gamdp_ctx_set_l1_chain", "gamdp_ctx_l1_chain_stats", "gamdp_ctx_set_l1_walk_bands",
     "gamdp_ctx_set_walk_skip", "gamdp_ctx_walk_skip_stats", "gamdp_ctx_set_walk_skip_pair", "gamdp_ctx_walk_skip_pair_stats",
     "gamdp_ctx_set_walk_skip_i32", "gamdp_ctx_walk_skip_i32_stats",
+    "gamdp_ctx_set_walk_skip_backoff", "gamdp_walk_skip_backoff_hold", "gamdp_ctx_walk_skip_backoff_stats",
     "gamdp_ops_fingerprint", "gamdp_carry_ops_batch", "gamdp_ctx_carry_ops_info",
     "gamdp_task_ops_cap", "gamdp_align_batch_fp", "gamdp_ctx_set_ops_chunk_bytes", "gamdp_ops_fingerprint_batch",
     "gamdp_ctx_ops_fp_info",
@@ -39,6 +40,7 @@ L1_HITS_HOST, L1_HITS_DEVICE = 0, 1   # gamdp_ctx_set_l1_hits
 L1_CHAIN_WALK, L1_CHAIN_CARRY = 0, 1   # gamdp_ctx_set_l1_chain
 L1_WALK_BAND_150, L1_WALK_ANY_BAND = 0, 1   # gamdp_ctx_set_l1_walk_bands
 WALK_STRIPS, WALK_SKIP_DIAG = 0, 1   # gamdp_ctx_set_walk_skip, gamdp_ctx_set_walk_skip_pair, gamdp_ctx_set_walk_skip_i32
+WALK_BACKOFF_OFF, WALK_BACKOFF_ON = 0, 1   # gamdp_ctx_set_walk_skip_backoff
 ST_DIAG_RANGE = 9   # diagnostics build only: a packed-f16 block left the exact range (never expected)
 
 
@@ -186,6 +188,15 @@ class WalkSkipI32Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class WalkSkipBackoffStats(C.Structure):
+    """gamdp_walk_skip_backoff_stats: the candidate points the walks of the last gamdp_align_batch passed without a test, per kernel
+    family (static_assert in gamdp_host.cpp)."""
+    _fields_ = [("held", C.c_uint64), ("held_pair", C.c_uint64), ("held_i32", C.c_uint64), ("mode", C.c_uint32), ("pad_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class L1TailCall(C.Structure):
     """gamdp_l1_tail_call: the seed of one tail alignment of the last gamdp_align_merge_blocks (static_assert in gamdp_hits.hip)."""
     _fields_ = [("begin_a", C.c_uint64), ("merge_block", C.c_uint32), ("right", C.c_uint8), ("source", C.c_uint8),
@@ -328,6 +339,13 @@ def load_library():
         lib.gamdp_ctx_set_walk_skip_i32.restype = C.c_int
         lib.gamdp_ctx_walk_skip_i32_stats.argtypes = [vp, C.POINTER(WalkSkipI32Stats)]
         lib.gamdp_ctx_walk_skip_i32_stats.restype = C.c_int
+    if hasattr(lib, "gamdp_ctx_set_walk_skip_backoff"):   # (the same)
+        lib.gamdp_ctx_set_walk_skip_backoff.argtypes = [vp, C.c_int]
+        lib.gamdp_ctx_set_walk_skip_backoff.restype = C.c_int
+        lib.gamdp_walk_skip_backoff_hold.argtypes = [C.c_uint32]
+        lib.gamdp_walk_skip_backoff_hold.restype = C.c_uint32
+        lib.gamdp_ctx_walk_skip_backoff_stats.argtypes = [vp, C.POINTER(WalkSkipBackoffStats)]
+        lib.gamdp_ctx_walk_skip_backoff_stats.restype = C.c_int
     lib.gamdp_ctx_l1_hits_stats.argtypes = [vp, C.POINTER(L1HitsStats)]
     lib.gamdp_ctx_l1_hits_stats.restype = C.c_int
     lib.gamdp_ctx_l1_tail_calls.argtypes = [vp, C.POINTER(L1TailCall), C.c_size_t, C.POINTER(C.c_size_t)]

@@ -244,6 +244,33 @@ typedef struct gamdp_walk_skip_i32_stats {
 } gamdp_walk_skip_i32_stats;   /* 48 bytes */
 int gamdp_ctx_walk_skip_i32_stats(const gamdp_ctx* ctx, gamdp_walk_skip_i32_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
 
+/* Whether walks in GAMDP_WALK_SKIP_DIAG mode back off from the test after failures, a fourth property: it applies to whichever
+ * of the three properties above is in SKIP_DIAG mode and does nothing where none is.  A failed test is a memory round trip in
+ * front of the strip call it did not save, and the indel rate of a pair is about the same all along it.
+ *   GAMDP_WALK_BACKOFF_OFF  the default: every point where a walk runs out of directions is tested.
+ *   GAMDP_WALK_BACKOFF_ON   each walk counts the tests in a row that skipped nothing (`fails`).  After such a test its next
+ *       gamdp_walk_skip_backoff_hold(fails) = min(2^fails - 1, a cap) such points pass without a test and without a load: the
+ *       walk asks for its strip at once, as after a failed test.  A test that skips at least one group puts fails back to 0.
+ * Results do not depend on the mode.  A task whose edit string is wanted never tests and never holds.  gamdp_multi_* honours
+ * each context's own setting; GAMDP_WALK_SKIP_BACKOFF=1 in the environment (read once per process) makes ON the mode of new
+ * contexts. */
+#define GAMDP_WALK_BACKOFF_OFF 0   /* default */
+#define GAMDP_WALK_BACKOFF_ON  1
+int gamdp_ctx_set_walk_skip_backoff(gamdp_ctx* ctx, int mode);   /* GAMDP_EINVAL for NULL / unknown mode (mode checked first) */
+/* The schedule itself (host only, no context): 0 for fails == 0, non-decreasing, 2^fails - 1 up to the cap the device code uses. */
+uint32_t gamdp_walk_skip_backoff_hold(uint32_t fails);
+/* The points the walks of the last gamdp_align_batch on this context passed without a test, per kernel family (the families of
+ * the three properties above), summed over the call's launches and pieces: tests of gamdp_walk_skip*_stats + held = the points a
+ * walk in BACKOFF_OFF mode would have tested on the same path.  Everything 0 before the first call. */
+typedef struct gamdp_walk_skip_backoff_stats {
+    uint64_t held;             /* eight-task launches ("k_align_o<19,15>") */
+    uint64_t held_pair;        /* two-task launches ("k_align_p<17,4>"), both ways it walks */
+    uint64_t held_i32;         /* launches of the six int32 direction-free kernels */
+    uint32_t mode;             /* GAMDP_WALK_BACKOFF_* the call ran in */
+    uint32_t pad_;
+} gamdp_walk_skip_backoff_stats;   /* 32 bytes */
+int gamdp_ctx_walk_skip_backoff_stats(const gamdp_ctx* ctx, gamdp_walk_skip_backoff_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
+
 /* ---- sequences ---------------------------------------------------------------------------- */
 /* seqs[i] points to lens[i] bytes: ASCII bases when is_ascii!=0 (normalised like Nucleotide(char)),
  * else base codes A=0 T=1 C=2 G=3 N=4.  Packs to 2 bit + N mask and uploads to the ctx's GPU. */

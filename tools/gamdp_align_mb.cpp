@@ -14,6 +14,8 @@
 // (gamdp_ctx_set_walk_skip; it matters for the big batches of the round loop; the output does not change).
 // --walk-skip-i32 does the same for the int32 direction-free kernels (gamdp_ctx_set_walk_skip_i32: the round loop's launches at bands
 // 160 - 543, N-holding band-150 batches on the four-task kernel; the output does not change).
+// --walk-skip-backoff lets the walks of either stop testing for a while after tests that skipped nothing
+// (gamdp_ctx_set_walk_skip_backoff; it does nothing without --walk-skip / --walk-skip-i32; the output does not change).
 // --devices runs the step on several GPUs of the node (gamdp_multi_*: merge blocks partitioned statically by predicted
 // cells, one host thread + context per device, no collective); a device may be listed twice.  The output is the same
 // whatever the device list -- unlike gam-merge --threads N, whose paired-contig order depends on thread timing.
@@ -59,18 +61,19 @@ static int region_vote(void*, int32_t, int32_t, int32_t, int32_t, int32_t, int32
 int main(int argc, char** argv)
 {
     if (argc < 5) die("usage: gamdp-align-mb <master.fasta> <slave.fasta> <mergeblocks.tsv> <out.tsv> [--band N] [--device D] [--repeat K] "
-                      "[--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]] [--device-hits] [--carry-chains] [--walk-any-band] [--walk-skip] [--walk-skip-i32]");
+                      "[--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]] [--device-hits] [--carry-chains] [--walk-any-band] [--walk-skip] [--walk-skip-i32] [--walk-skip-backoff]");
     unsigned band = GAMDP_DEFAULT_BAND;
     int device = 0, repeat = 1;
     std::vector<int> devices;
     std::string pctg_prefix, blocks_path, filtered_path;
-    bool device_hits = false, carry_chains = false, walk_any_band = false, walk_skip = false, walk_skip_i32 = false;
+    bool device_hits = false, carry_chains = false, walk_any_band = false, walk_skip = false, walk_skip_i32 = false, walk_skip_backoff = false;
     for (int i = 5; i < argc; i += 2) {
         if (!std::strcmp(argv[i], "--device-hits")) { device_hits = true; i--; continue; }   // (a flag: no value follows)
         if (!std::strcmp(argv[i], "--carry-chains")) { carry_chains = true; i--; continue; }
         if (!std::strcmp(argv[i], "--walk-any-band")) { walk_any_band = true; i--; continue; }
         if (!std::strcmp(argv[i], "--walk-skip")) { walk_skip = true; i--; continue; }
         if (!std::strcmp(argv[i], "--walk-skip-i32")) { walk_skip_i32 = true; i--; continue; }
+        if (!std::strcmp(argv[i], "--walk-skip-backoff")) { walk_skip_backoff = true; i--; continue; }
         if (i + 1 >= argc) die(std::string("option ") + argv[i] + " needs a value");
         if (!std::strcmp(argv[i], "--band")) band = (unsigned)std::atoi(argv[i + 1]);
         else if (!std::strcmp(argv[i], "--device")) device = std::atoi(argv[i + 1]);
@@ -177,6 +180,11 @@ int main(int argc, char** argv)
         if (ctx && gamdp_ctx_set_walk_skip_i32(ctx, GAMDP_WALK_SKIP_DIAG)) die("gamdp_ctx_set_walk_skip_i32 failed");
         for (int d = 0; multi && d < gamdp_multi_size(multi); d++)
             if (gamdp_ctx_set_walk_skip_i32(gamdp_multi_ctx(multi, d), GAMDP_WALK_SKIP_DIAG)) die("gamdp_ctx_set_walk_skip_i32 failed");
+    }
+    if (walk_skip_backoff) {   // ... and either stops testing for a while after tests that skipped nothing (identical results)
+        if (ctx && gamdp_ctx_set_walk_skip_backoff(ctx, GAMDP_WALK_BACKOFF_ON)) die("gamdp_ctx_set_walk_skip_backoff failed");
+        for (int d = 0; multi && d < gamdp_multi_size(multi); d++)
+            if (gamdp_ctx_set_walk_skip_backoff(gamdp_multi_ctx(multi, d), GAMDP_WALK_BACKOFF_ON)) die("gamdp_ctx_set_walk_skip_backoff failed");
     }
 
     std::vector<gamdp_mb_out> out(in.size());

@@ -13,7 +13,8 @@ score, n_match, length, first and last match, homology, status -- and cells must
 carry_mismatches, carry_kernels, carry_kernel_ms and carry_gcups.  Without the flag the output is what it was.
 --carry --walk-skip-pair / --walk-skip-i32: gamdp_align_batch runs with that walk-skip property on (gamdp_ctx_set_walk_skip_pair,
 gamdp_ctx_set_walk_skip_i32), so every field of its results is checked against a kernel that has no walk at all; the line then
-also holds the property's statistics of the last call.
+also holds the property's statistics of the last call.  --walk-skip does the same for the eight-task kernel (gamdp_ctx_set_walk_skip), and
+--walk-skip-backoff switches gamdp_ctx_set_walk_skip_backoff on beside whichever of the three is given (walk_skip_backoff: its statistics).
 
 With --ops the edit strings are checked too.  gamdp_align_batch runs once more with edit strings (one buffer of |a| + |b| + 2 band +
 64 bytes per call, on the device and on the host: what limits the batch), the host fingerprints the bytes it returned
@@ -65,6 +66,8 @@ def main():
     ap.add_argument("--first-pair", type=int, default=0)
     ap.add_argument("--seed", type=int, default=20261019)
     ap.add_argument("--carry", action="store_true", help="also run gamdp_carry_batch and compare whole results")
+    ap.add_argument("--walk-skip", action="store_true", help="with --carry: gamdp_align_batch runs with gamdp_ctx_set_walk_skip(GAMDP_WALK_SKIP_DIAG)")
+    ap.add_argument("--walk-skip-backoff", action="store_true", help="with one of --walk-skip, --walk-skip-pair, --walk-skip-i32: gamdp_ctx_set_walk_skip_backoff(GAMDP_WALK_BACKOFF_ON)")
     ap.add_argument("--walk-skip-pair", action="store_true", help="with --carry: gamdp_align_batch runs with gamdp_ctx_set_walk_skip_pair(GAMDP_WALK_SKIP_DIAG)")
     ap.add_argument("--walk-skip-i32", action="store_true", help="with --carry: gamdp_align_batch runs with gamdp_ctx_set_walk_skip_i32(GAMDP_WALK_SKIP_DIAG)")
     ap.add_argument("--ops", action="store_true", help="also run gamdp_carry_ops_batch and compare the fingerprints of gamdp_align_batch's edit strings")
@@ -80,7 +83,16 @@ def main():
         ap.error("--walk-skip-pair goes with --carry")
     if args.walk_skip_i32 and not args.carry:
         ap.error("--walk-skip-i32 goes with --carry")
+    if args.walk_skip and not args.carry:
+        ap.error("--walk-skip goes with --carry")
+    if args.walk_skip_backoff and not (args.walk_skip or args.walk_skip_pair or args.walk_skip_i32):
+        ap.error("--walk-skip-backoff goes with --walk-skip, --walk-skip-pair or --walk-skip-i32")
     ctx = gam.Context(0)
+    skip_octo = skip_backoff = None
+    if args.walk_skip:        # the eight-task kernel's walks jump over indel-free groups
+        ctx.set_walk_skip(L.WALK_SKIP_DIAG)
+    if args.walk_skip_backoff:   # ... and the walks of whichever kernels test back off after failures
+        ctx.set_walk_skip_backoff(L.WALK_BACKOFF_ON)
     skip_pair = None
     if args.walk_skip_pair:   # the two-task kernel's walks jump over indel-free groups: checked call by call against gamdp_carry_batch
         ctx.set_walk_skip_pair(L.WALK_SKIP_DIAG)
@@ -135,6 +147,10 @@ def main():
         rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res, None)
         assert rc == 0, ("gamdp_align_batch", rc, ctx.last_error())
         a_ms = ctx.kernel_time(reset=True)[0]
+        if args.walk_skip:
+            skip_octo = ctx.walk_skip_stats()
+        if args.walk_skip_backoff:
+            skip_backoff = ctx.walk_skip_backoff_stats()
         if args.walk_skip_pair:
             skip_pair = ctx.walk_skip_pair_stats()
         if args.walk_skip_i32:
@@ -206,6 +222,10 @@ def main():
     if args.carry:
         rec.update(carry_mismatches=carry_mismatches, carry_first_mismatch=carry_first_bad, carry_kernels=[r["kernel"] for r in ctx.carry_info()],
                    carry_kernel_ms=[round(v, 3) for v in carry_ms], carry_gcups=round(cells / med(carry_ms) / 1e6, 1))
+    if args.walk_skip:
+        rec.update(walk_skip=skip_octo)
+    if args.walk_skip_backoff:
+        rec.update(walk_skip_backoff=skip_backoff)
     if args.walk_skip_pair:
         rec.update(walk_skip_pair=skip_pair)
     if args.walk_skip_i32:

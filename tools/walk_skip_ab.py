@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of the eight-task kernel's walk modes (gamdp_ctx_set_walk_skip): GAMDP_WALK_STRIPS against GAMDP_WALK_SKIP_DIAG, alternating
-call by call in ONE process on ONE context, at several divergences.
+"""A/B of the eight-task kernel's walk modes (gamdp_ctx_set_walk_skip): GAMDP_WALK_STRIPS against GAMDP_WALK_SKIP_DIAG and against
+GAMDP_WALK_SKIP_DIAG with gamdp_ctx_set_walk_skip_backoff on, alternating call by call in ONE process on ONE context, at several
+divergences.
 
 Workloads (band 150): 100 000 x 5 kb, 16 384 x 50 kb, and the batch shaped like the merge-block driver's calls (tests/_mixed.py), each
 at the divergences of DIVERGENCES (substitutions / insertions / deletions in per cent of the bases; the first is bench.py's config 5).
@@ -8,8 +9,9 @@ The pairs are made here, in numpy (gamdp_synth_pair's rates are fixed).  Per row
 mode, alternating; kernel time from gamdp_ctx_kernel_time; median and min - max per mode; every call's results are compared byte for
 byte with the first call's; the device's counts (gamdp_ctx_walk_skip_stats, gamdp_ctx_launch_info) of a call in either mode.  With
 --carry every row also runs gamdp_carry_batch once -- a kernel without any walk -- and compares whole results with it.
+--piecewise adds two rows per pair workload: pairs whose divergence changes along the pair (tests/_piecewise.py), in both orders.
 
-    python tools/walk_skip_ab.py [--reps 7] [--scale 1.0] [--workloads 5k,50k,mixed] [--carry] [--json]
+    python tools/walk_skip_ab.py [--reps 7] [--scale 1.0] [--workloads 5k,50k,mixed] [--piecewise] [--rows 0,2,5,6] [--carry] [--json]
 
 --scale shrinks the pair counts (a quick look; the table of DESIGN.md section 6 is --scale 1).  No planner switch is needed at these
 sizes (GAMDP_QUAD_MIN is for small batches)."""
@@ -33,6 +35,9 @@ from srchash import source_hash  # noqa: E402
 BAND = 150
 DIVERGENCES = ((3.0, 1.0, 1.0), (2.0, 0.5, 0.5), (0.3, 0.1, 0.1), (0.05, 0.02, 0.02), (0.0, 0.0, 0.0))
 KERNEL = "k_align_o<19,15>"
+# the three columns: (gamdp_ctx_set_walk_skip, gamdp_ctx_set_walk_skip_backoff)
+OFF, ON, BACKOFF = (L.WALK_STRIPS, L.WALK_BACKOFF_OFF), (L.WALK_SKIP_DIAG, L.WALK_BACKOFF_OFF), (L.WALK_SKIP_DIAG, L.WALK_BACKOFF_ON)
+SETTINGS = (OFF, ON, BACKOFF)
 
 
 def diverged(rng, A, n_pairs, length, sub, ins, dele):
@@ -83,6 +88,26 @@ def pairs_workload(ctx, rng, n_pairs, length, div):
     return sset, tasks, n_pairs
 
 
+def piecewise_workload(ctx, rng, n_pairs, length, reverse, band=BAND):
+    """pairs whose divergence changes along the pair (tests/_piecewise.py: thirds at 3/1/1 %, 0/0/0 and 0.3/0.1/0.1, or the other way round)"""
+    import _piecewise
+    seqs, blens = [], []
+    step = max(1, (32 << 20) // length)
+    for first in range(0, n_pairs, step):
+        A, Bs = _piecewise.batch(rng, min(step, n_pairs - first), length, reverse=reverse)
+        for a, b in zip(A, Bs):
+            seqs.append(a.tobytes())
+            seqs.append(b.tobytes())
+            blens.append(len(b))
+    sset = gam.SequenceSet(ctx, seqs, ascii=False)
+    tasks = (L.Task * n_pairs)()
+    for k in range(n_pairs):
+        t = tasks[k]
+        t.a_id, t.b_id, t.band = 2 * k, 2 * k + 1, band
+        t.begin_a, t.end_a, t.begin_b, t.end_b = 0, length - 1, 0, max(blens[k], 1) - 1
+    return sset, tasks
+
+
 def mixed_workload(ctx, n_pairs, div):
     import _mixed
     sub, ins, dele = (v / 100.0 for v in div)
@@ -99,14 +124,15 @@ def mixed_workload(ctx, n_pairs, div):
 
 
 def one_row(ctx, name, sset, tasks, n, div, reps, carry):
-    outs = {m: (L.Result * n)() for m in (L.WALK_STRIPS, L.WALK_SKIP_DIAG)}
+    outs = {m: (L.Result * n)() for m in SETTINGS}
     first = None
-    ms = {L.WALK_STRIPS: [], L.WALK_SKIP_DIAG: []}
-    stats, strips, octo_tasks = {}, {}, 0
+    ms = {m: [] for m in SETTINGS}
+    stats, strips, held, octo_tasks = {}, {}, 0, 0
     different = 0
     for rep in range(reps + 1):            # (rep 0 warms up)
-        for mode in (L.WALK_STRIPS, L.WALK_SKIP_DIAG):
-            ctx.set_walk_skip(mode)
+        for mode in SETTINGS:
+            ctx.set_walk_skip(mode[0])
+            ctx.set_walk_skip_backoff(mode[1])
             ctx.kernel_time(reset=True)
             rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, outs[mode], None)
             assert rc == 0, (rc, ctx.last_error())
@@ -121,10 +147,12 @@ def one_row(ctx, name, sset, tasks, n, div, reps, carry):
                 info = ctx.launch_info()
                 strips[mode] = sum(r["strips"] for r in info)
                 octo_tasks = sum(r["tasks"] for r in info if r["kernel"] == KERNEL)
+                held = ctx.walk_skip_backoff_stats()["held"]
     ctx.set_walk_skip(L.WALK_STRIPS)
+    ctx.set_walk_skip_backoff(L.WALK_BACKOFF_OFF)
     rec = dict(workload=name, calls=n, eight_task_calls=octo_tasks, sub=div[0], ins=div[1], dele=div[2], results_differ=different,
-               strips_off=strips[L.WALK_STRIPS], strips_on=strips[L.WALK_SKIP_DIAG], stats_on=stats[L.WALK_SKIP_DIAG])
-    for mode, key in ((L.WALK_STRIPS, "off"), (L.WALK_SKIP_DIAG, "on")):
+               strips_off=strips[OFF], strips_on=strips[ON], strips_backoff=strips[BACKOFF], stats_on=stats[ON], stats_backoff=stats[BACKOFF], held=held)
+    for mode, key in ((OFF, "off"), (ON, "on"), (BACKOFF, "backoff")):
         v = sorted(ms[mode])
         rec["ms_" + key] = dict(median=round(v[len(v) // 2], 2), min=round(v[0], 2), max=round(v[-1], 2))
     if carry:
@@ -132,8 +160,7 @@ def one_row(ctx, name, sset, tasks, n, div, reps, carry):
         rc = ctx.lib.gamdp_carry_batch(ctx.handle, sset.handle, sset.handle, tasks, n, ca)
         assert rc == 0, (rc, ctx.last_error())
         whole = lambda r: r.key() + (r.cells,)  # noqa: E731
-        on = outs[L.WALK_SKIP_DIAG]
-        rec["carry_mismatches"] = sum(1 for i in range(n) if whole(on[i]) != whole(ca[i]))
+        rec["carry_mismatches"] = sum(1 for m in (ON, BACKOFF) for i in range(n) if whole(outs[m][i]) != whole(ca[i]))
     return rec
 
 
@@ -142,6 +169,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--workloads", default="5k,50k,mixed")
+    ap.add_argument("--piecewise", action="store_true", help="two more rows per pair workload: the divergence changes along the pair, both orders")
+    ap.add_argument("--rows", default="", help="only these rows of every workload: indices into DIVERGENCES, the two piecewise rows behind them (e.g. 0,2,5,6)")
     ap.add_argument("--carry", action="store_true")
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args()
@@ -149,12 +178,20 @@ def main():
     ctx = gam.Context(0)
     rows = []
     print("source %s, %d calls per mode after a warm-up, kernel ms: median (min - max)" % (source_hash(), args.reps), flush=True)
-    print("%-16s %-15s %9s %9s %12s %12s  %-24s %-24s %s" % ("workload", "sub/ins/del %", "strips", "strips on", "grp tested", "grp skipped",
-                                                          "ms off", "ms on", "on/off"), flush=True)
+    print("%-16s %-15s %9s %9s %9s %12s %12s %9s  %-24s %-24s %-24s %s" % ("workload", "sub/ins/del %", "strips", "strips on", "strips bo", "grp skipped",
+                                                                      "skipped bo", "held", "ms off", "ms on", "ms on + backoff", "on/off  bo/off"), flush=True)
     for w in args.workloads.split(","):
-        for di, div in enumerate(DIVERGENCES):
+        rows_of = list(enumerate(DIVERGENCES)) + ([(len(DIVERGENCES), "piecewise"), (len(DIVERGENCES) + 1, "piecewise rev")] if args.piecewise and w != "mixed" else [])
+        for di, div in rows_of:
+            if args.rows and str(di) not in args.rows.split(","):
+                continue
             rng = np.random.default_rng(20261019 + di)
-            if w == "5k":
+            if isinstance(div, str):
+                n, length = (max(8, int(100000 * args.scale)), 5000) if w == "5k" else (max(8, int(16384 * args.scale)), 50000)
+                sset, tasks = piecewise_workload(ctx, rng, n, length, div.endswith("rev"))
+                name = "%d x %d kb" % (n, length // 1000)
+                div = (div, "", "")
+            elif w == "5k":
                 sset, tasks, n = pairs_workload(ctx, rng, max(8, int(100000 * args.scale)), 5000, div)
                 name = "%d x 5 kb" % n
             elif w == "50k":
@@ -167,9 +204,11 @@ def main():
             sset.close()
             rows.append(rec)
             f = lambda d: "%.2f (%.2f - %.2f)" % (d["median"], d["min"], d["max"])  # noqa: E731
-            print("%-16s %-15s %9d %9d %12d %12d  %-24s %-24s %.3f%s%s" % (
-                name, "%g/%g/%g" % div, rec["strips_off"], rec["strips_on"], rec["stats_on"]["groups_tested"], rec["stats_on"]["groups_skipped"],
-                f(rec["ms_off"]), f(rec["ms_on"]), rec["ms_on"]["median"] / rec["ms_off"]["median"],
+            print("%-16s %-15s %9d %9d %9d %12d %12d %9d  %-24s %-24s %-24s %.3f  %.3f%s%s" % (
+                name, div[0] if isinstance(div[0], str) else "%g/%g/%g" % div, rec["strips_off"], rec["strips_on"], rec["strips_backoff"],
+                rec["stats_on"]["groups_skipped"], rec["stats_backoff"]["groups_skipped"], rec["held"],
+                f(rec["ms_off"]), f(rec["ms_on"]), f(rec["ms_backoff"]), rec["ms_on"]["median"] / rec["ms_off"]["median"],
+                rec["ms_backoff"]["median"] / rec["ms_off"]["median"],
                 "  RESULTS DIFFER in %d calls" % rec["results_differ"] if rec["results_differ"] else "",
                 ("  carry mismatches %d" % rec["carry_mismatches"]) if args.carry else ""), flush=True)
     if args.json:

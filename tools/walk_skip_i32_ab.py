@@ -14,8 +14,10 @@ The tool says which environment a cell needs and stops when the launches of a ro
 Rows: 50 kb and 5 kb pairs, identical, at 0.04 % indels, at 0.2 % indels and at config 5's 3 % substitutions + 1 % + 1 % indels.
 Per row: kernel time of the call (gamdp_ctx_kernel_time) in either mode, median and range; whether the results of the two modes are
 the same bytes; the device's counts; with --carry the results of the `on` mode against gamdp_carry_batch.
+A third column runs GAMDP_WALK_SKIP_DIAG with gamdp_ctx_set_walk_skip_backoff on; --piecewise adds two rows per length: pairs whose
+divergence changes along the pair (tests/_piecewise.py), in both orders; --rows picks rows by index.
 
-    python tools/walk_skip_i32_ab.py --cell gen9 [--reps 5] [--scale 1.0] [--lengths 50k,5k] [--carry] [--json]
+    python tools/walk_skip_i32_ab.py --cell gen9 [--reps 5] [--scale 1.0] [--lengths 50k,5k] [--piecewise] [--rows 0,3,4,5] [--carry] [--json]
 
 --scale shrinks the pair counts (a quick look)."""
 import argparse
@@ -28,12 +30,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import gam_ngs_amd as gam  # noqa: E402
 from gam_ngs_amd import lib as L  # noqa: E402
 from srchash import source_hash  # noqa: E402
-from walk_skip_ab import diverged  # noqa: E402
+from walk_skip_ab import BACKOFF, OFF, ON, SETTINGS, diverged, piecewise_workload  # noqa: E402
 
 DIVERGENCES = ((0.0, 0.0, 0.0), (0.0, 0.02, 0.02), (0.0, 0.1, 0.1), (3.0, 1.0, 1.0))
 # cell -> (kernel, band, every pair holds an N, environment)
@@ -74,14 +77,15 @@ def workload(ctx, rng, n_pairs, length, div, band, with_n):
 
 
 def one_row(ctx, kernel, name, sset, tasks, n, div, reps, carry):
-    modes = (L.WALK_STRIPS, L.WALK_SKIP_DIAG)
+    modes = SETTINGS                       # STRIPS, DIAG, DIAG + gamdp_ctx_set_walk_skip_backoff
     outs = {m: (L.Result * n)() for m in modes}
     first = None
     ms = {m: [] for m in modes}
-    stats, different = {}, 0
+    stats, different, held = {}, 0, 0
     for rep in range(reps + 1):            # (rep 0 warms up)
         for mode in modes:
-            ctx.set_walk_skip_i32(mode)
+            ctx.set_walk_skip_i32(mode[0])
+            ctx.set_walk_skip_backoff(mode[1])
             ctx.kernel_time(reset=True)
             rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, outs[mode], None)
             assert rc == 0, (rc, ctx.last_error())
@@ -93,14 +97,16 @@ def one_row(ctx, kernel, name, sset, tasks, n, div, reps, carry):
             different += raw != first
             if rep == reps:
                 stats[mode] = ctx.walk_skip_i32_stats()
+                held = ctx.walk_skip_backoff_stats()["held_i32"]
                 kernels = sorted({r["kernel"] for r in ctx.launch_info()})
     ctx.set_walk_skip_i32(L.WALK_STRIPS)
+    ctx.set_walk_skip_backoff(L.WALK_BACKOFF_OFF)
     if kernels != [kernel]:
         sys.exit("the row ran %s, not %s alone: set the cell's environment (see --help)" % (kernels, kernel))
-    on = stats[L.WALK_SKIP_DIAG]
+    on, bo = stats[ON], stats[BACKOFF]
     rec = dict(workload=name, kernel=kernel, calls=n, sub=div[0], ins=div[1], dele=div[2], results_differ=different,
-               strips_off=stats[L.WALK_STRIPS]["strips"], strips_on=on["strips"], stats_on=on)
-    for mode, key in ((L.WALK_STRIPS, "off"), (L.WALK_SKIP_DIAG, "on")):
+               strips_off=stats[OFF]["strips"], strips_on=on["strips"], strips_backoff=bo["strips"], stats_on=on, stats_backoff=bo, held=held)
+    for mode, key in ((OFF, "off"), (ON, "on"), (BACKOFF, "backoff")):
         v = sorted(ms[mode])
         rec["ms_" + key] = dict(median=round(v[len(v) // 2], 2), min=round(v[0], 2), max=round(v[-1], 2))
     if carry:
@@ -108,8 +114,7 @@ def one_row(ctx, kernel, name, sset, tasks, n, div, reps, carry):
         rc = ctx.lib.gamdp_carry_batch(ctx.handle, sset.handle, sset.handle, tasks, n, ca)
         assert rc == 0, (rc, ctx.last_error())
         whole = lambda r: r.key() + (r.cells,)  # noqa: E731
-        res = outs[L.WALK_SKIP_DIAG]
-        rec["carry_mismatches"] = sum(1 for i in range(n) if whole(res[i]) != whole(ca[i]))
+        rec["carry_mismatches"] = sum(1 for m in (ON, BACKOFF) for i in range(n) if whole(outs[m][i]) != whole(ca[i]))
     return rec
 
 
@@ -119,6 +124,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--lengths", default="50k,5k")
+    ap.add_argument("--piecewise", action="store_true", help="two more rows per length: the divergence changes along the pair (tests/_piecewise.py), both orders")
+    ap.add_argument("--rows", default="", help="only these rows of every workload: indices into DIVERGENCES, the two piecewise rows behind them (e.g. 0,2,5,6)")
     ap.add_argument("--carry", action="store_true")
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args()
@@ -130,22 +137,30 @@ def main():
     ctx = gam.Context(0)
     rows = []
     print("source %s, %s band %d, %d calls per mode after a warm-up, kernel ms: median (min - max)" % (source_hash(), kernel, band, args.reps), flush=True)
-    print("%-16s %-13s %8s %9s %11s %11s  %-24s %-24s %s" % ("workload", "sub/ins/del %", "strips", "strips on", "grp tested", "grp skipped",
-                                                          "ms off", "ms on", "on/off"), flush=True)
+    divs = list(enumerate(DIVERGENCES)) + ([(len(DIVERGENCES), "piecewise"), (len(DIVERGENCES) + 1, "piecewise rev")] if args.piecewise and not with_n else [])
+    print("%-16s %-13s %8s %9s %9s %11s %11s %8s  %-24s %-24s %-24s %s" % ("workload", "sub/ins/del %", "strips", "strips on", "strips bo", "grp skipped", "skipped bo", "held",
+                                                          "ms off", "ms on", "ms on + backoff", "on/off  bo/off"), flush=True)
     for w in args.lengths.split(","):
         length, n_full = PAIRS[w]
         n = max(8, int(n_full * args.scale)) & ~3
-        for di, div in enumerate(DIVERGENCES):
+        for di, div in divs:
+            if args.rows and str(di) not in args.rows.split(","):
+                continue
             rng = np.random.default_rng(20261020 + di)
-            sset, tasks = workload(ctx, rng, n, length, div, band, with_n)
+            if isinstance(div, str):
+                sset, tasks = piecewise_workload(ctx, rng, n, length, div.endswith("rev"), band)
+                div = (div, "", "")
+            else:
+                sset, tasks = workload(ctx, rng, n, length, div, band, with_n)
             name = "%d x %s" % (n, w.replace("k", " kb"))
             rec = one_row(ctx, kernel, name, sset, tasks, n, div, args.reps, args.carry)
             sset.close()
             rows.append(rec)
             f = lambda d: "%.2f (%.2f - %.2f)" % (d["median"], d["min"], d["max"])  # noqa: E731
-            print("%-16s %-13s %8d %9d %11d %11d  %-24s %-24s %.3f%s%s" % (
-                name, "%g/%g/%g" % div, rec["strips_off"], rec["strips_on"], rec["stats_on"]["groups_tested"],
-                rec["stats_on"]["groups_skipped"], f(rec["ms_off"]), f(rec["ms_on"]), rec["ms_on"]["median"] / rec["ms_off"]["median"],
+            print("%-16s %-13s %8d %9d %9d %11d %11d %8d  %-24s %-24s %-24s %.3f  %.3f%s%s" % (
+                name, div[0] if isinstance(div[0], str) else "%g/%g/%g" % div, rec["strips_off"], rec["strips_on"], rec["strips_backoff"],
+                rec["stats_on"]["groups_skipped"], rec["stats_backoff"]["groups_skipped"], rec["held"], f(rec["ms_off"]), f(rec["ms_on"]),
+                f(rec["ms_backoff"]), rec["ms_on"]["median"] / rec["ms_off"]["median"], rec["ms_backoff"]["median"] / rec["ms_off"]["median"],
                 "  RESULTS DIFFER in %d calls" % rec["results_differ"] if rec["results_differ"] else "",
                 ("  carry mismatches %d" % rec["carry_mismatches"]) if args.carry else ""), flush=True)
     if args.json:
