@@ -76,54 +76,54 @@ class Context:
         _check(self, self.lib.gamdp_ctx_l1_chain_stats(self.handle, C.byref(st)), "gamdp_ctx_l1_chain_stats")
         return st.as_dict()
 
+    def _set_walk_mode(self, name, mode):
+        _check(self, getattr(self.lib, name)(self.handle, mode), name)
+
+    def _walk_stats(self, name, struct):
+        st = struct()
+        _check(self, getattr(self.lib, name)(self.handle, C.byref(st)), name)
+        return st.as_dict()
+
     def set_walk_skip(self, mode: int):
         """How the walks of the eight-task band-150 kernel cross rows without directions: L.WALK_STRIPS (the default: a strip call per
         stretch of the path) or L.WALK_SKIP_DIAG (groups of 64 rows that provably hold diagonal steps only are jumped over;
         gamdp_ctx_set_walk_skip).  The results do not depend on it."""
-        _check(self, self.lib.gamdp_ctx_set_walk_skip(self.handle, mode), "gamdp_ctx_set_walk_skip")
+        self._set_walk_mode("gamdp_ctx_set_walk_skip", mode)
 
     def walk_skip_stats(self):
         """What the eight-task launches of the last gamdp_align_batch on this context counted, as a dict (gamdp_ctx_walk_skip_stats)."""
-        st = L.WalkSkipStats()
-        _check(self, self.lib.gamdp_ctx_walk_skip_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_stats")
-        return st.as_dict()
+        return self._walk_stats("gamdp_ctx_walk_skip_stats", L.WalkSkipStats)
 
     def set_walk_skip_pair(self, mode: int):
         """The same choice for the walks of the two-task band-512 kernel, a property of its own: L.WALK_STRIPS (the default) or
         L.WALK_SKIP_DIAG (gamdp_ctx_set_walk_skip_pair).  The results do not depend on it."""
-        _check(self, self.lib.gamdp_ctx_set_walk_skip_pair(self.handle, mode), "gamdp_ctx_set_walk_skip_pair")
+        self._set_walk_mode("gamdp_ctx_set_walk_skip_pair", mode)
 
     def walk_skip_pair_stats(self):
         """What the two-task launches of the last gamdp_align_batch on this context counted, as a dict (gamdp_ctx_walk_skip_pair_stats)."""
-        st = L.WalkSkipPairStats()
-        _check(self, self.lib.gamdp_ctx_walk_skip_pair_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_pair_stats")
-        return st.as_dict()
+        return self._walk_stats("gamdp_ctx_walk_skip_pair_stats", L.WalkSkipPairStats)
 
     def set_walk_skip_i32(self, mode: int):
         """The same choice for the walks of the int32 direction-free kernels (k_align<17,4>, k_align_q<19,15>, k_align<9,-1,true>,
         k_align<17,-1,true>), a third property: L.WALK_STRIPS (the default) or L.WALK_SKIP_DIAG (gamdp_ctx_set_walk_skip_i32).
         The results do not depend on it."""
-        _check(self, self.lib.gamdp_ctx_set_walk_skip_i32(self.handle, mode), "gamdp_ctx_set_walk_skip_i32")
+        self._set_walk_mode("gamdp_ctx_set_walk_skip_i32", mode)
 
     def walk_skip_i32_stats(self):
         """What the launches of those kernels in the last gamdp_align_batch on this context counted, as a dict (gamdp_ctx_walk_skip_i32_stats)."""
-        st = L.WalkSkipI32Stats()
-        _check(self, self.lib.gamdp_ctx_walk_skip_i32_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_i32_stats")
-        return st.as_dict()
+        return self._walk_stats("gamdp_ctx_walk_skip_i32_stats", L.WalkSkipI32Stats)
 
     def set_walk_skip_backoff(self, mode: int):
         """Whether walks in L.WALK_SKIP_DIAG mode of any of the three properties above back off from the test after failures, a
         fourth property: L.WALK_BACKOFF_OFF (the default: every candidate point is tested) or L.WALK_BACKOFF_ON (after `fails` tests
         in a row that skipped nothing, the next gamdp_walk_skip_backoff_hold(fails) points pass without a test;
         gamdp_ctx_set_walk_skip_backoff).  The results do not depend on it."""
-        _check(self, self.lib.gamdp_ctx_set_walk_skip_backoff(self.handle, mode), "gamdp_ctx_set_walk_skip_backoff")
+        self._set_walk_mode("gamdp_ctx_set_walk_skip_backoff", mode)
 
     def walk_skip_backoff_stats(self):
         """The candidate points the walks of the last gamdp_align_batch on this context passed without a test, per kernel family, as a
         dict (gamdp_ctx_walk_skip_backoff_stats)."""
-        st = L.WalkSkipBackoffStats()
-        _check(self, self.lib.gamdp_ctx_walk_skip_backoff_stats(self.handle, C.byref(st)), "gamdp_ctx_walk_skip_backoff_stats")
-        return st.as_dict()
+        return self._walk_stats("gamdp_ctx_walk_skip_backoff_stats", L.WalkSkipBackoffStats)
 
     def l1_tail_calls(self):
         """The tail alignments of the last alignMergeBlocks on this context and the seed each was given, as
@@ -285,69 +285,51 @@ class MultiContext:
             if self.lib.gamdp_ctx_set_l1_walk_bands(self.lib.gamdp_multi_ctx(self.handle, i), which) != 0:
                 raise L.GamdpError("gamdp_ctx_set_l1_walk_bands(%r) failed on context %d" % (which, i))
 
+    def _set_walk_mode(self, name, mode, which):
+        for i in (range(len(self.devices)) if which is None else (which,)):
+            if getattr(self.lib, name)(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
+                raise L.GamdpError("%s(%r) failed on context %d" % (name, mode, i))
+
+    def _walk_stats(self, name, struct):
+        out = []
+        for i in range(len(self.devices)):
+            st = struct()
+            if getattr(self.lib, name)(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
+                raise L.GamdpError("%s failed on context %d" % (name, i))
+            out.append(st.as_dict())
+        return out
+
     def set_walk_skip(self, mode: int, which=None):
         """Context.set_walk_skip on every context of the handle, or on context `which` alone."""
-        for i in (range(len(self.devices)) if which is None else (which,)):
-            if self.lib.gamdp_ctx_set_walk_skip(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
-                raise L.GamdpError("gamdp_ctx_set_walk_skip(%r) failed on context %d" % (mode, i))
+        self._set_walk_mode("gamdp_ctx_set_walk_skip", mode, which)
 
     def walk_skip_stats(self):
         """Context.walk_skip_stats of every context of the handle (a list of dicts)."""
-        out = []
-        for i in range(len(self.devices)):
-            st = L.WalkSkipStats()
-            if self.lib.gamdp_ctx_walk_skip_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
-                raise L.GamdpError("gamdp_ctx_walk_skip_stats failed on context %d" % i)
-            out.append(st.as_dict())
-        return out
+        return self._walk_stats("gamdp_ctx_walk_skip_stats", L.WalkSkipStats)
 
     def set_walk_skip_pair(self, mode: int, which=None):
         """Context.set_walk_skip_pair on every context of the handle, or on context `which` alone."""
-        for i in (range(len(self.devices)) if which is None else (which,)):
-            if self.lib.gamdp_ctx_set_walk_skip_pair(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
-                raise L.GamdpError("gamdp_ctx_set_walk_skip_pair(%r) failed on context %d" % (mode, i))
+        self._set_walk_mode("gamdp_ctx_set_walk_skip_pair", mode, which)
 
     def walk_skip_pair_stats(self):
         """Context.walk_skip_pair_stats of every context of the handle (a list of dicts)."""
-        out = []
-        for i in range(len(self.devices)):
-            st = L.WalkSkipPairStats()
-            if self.lib.gamdp_ctx_walk_skip_pair_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
-                raise L.GamdpError("gamdp_ctx_walk_skip_pair_stats failed on context %d" % i)
-            out.append(st.as_dict())
-        return out
+        return self._walk_stats("gamdp_ctx_walk_skip_pair_stats", L.WalkSkipPairStats)
 
     def set_walk_skip_i32(self, mode: int, which=None):
         """Context.set_walk_skip_i32 on every context of the handle, or on context `which` alone."""
-        for i in (range(len(self.devices)) if which is None else (which,)):
-            if self.lib.gamdp_ctx_set_walk_skip_i32(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
-                raise L.GamdpError("gamdp_ctx_set_walk_skip_i32(%r) failed on context %d" % (mode, i))
+        self._set_walk_mode("gamdp_ctx_set_walk_skip_i32", mode, which)
 
     def walk_skip_i32_stats(self):
         """Context.walk_skip_i32_stats of every context of the handle (a list of dicts)."""
-        out = []
-        for i in range(len(self.devices)):
-            st = L.WalkSkipI32Stats()
-            if self.lib.gamdp_ctx_walk_skip_i32_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
-                raise L.GamdpError("gamdp_ctx_walk_skip_i32_stats failed on context %d" % i)
-            out.append(st.as_dict())
-        return out
+        return self._walk_stats("gamdp_ctx_walk_skip_i32_stats", L.WalkSkipI32Stats)
 
     def set_walk_skip_backoff(self, mode: int, which=None):
         """Context.set_walk_skip_backoff on every context of the handle, or on context `which` alone."""
-        for i in (range(len(self.devices)) if which is None else (which,)):
-            if self.lib.gamdp_ctx_set_walk_skip_backoff(self.lib.gamdp_multi_ctx(self.handle, i), mode) != 0:
-                raise L.GamdpError("gamdp_ctx_set_walk_skip_backoff(%r) failed on context %d" % (mode, i))
+        self._set_walk_mode("gamdp_ctx_set_walk_skip_backoff", mode, which)
 
     def walk_skip_backoff_stats(self):
         """Context.walk_skip_backoff_stats of every context of the handle (a list of dicts)."""
-        out = []
-        for i in range(len(self.devices)):
-            st = L.WalkSkipBackoffStats()
-            if self.lib.gamdp_ctx_walk_skip_backoff_stats(self.lib.gamdp_multi_ctx(self.handle, i), C.byref(st)) != 0:
-                raise L.GamdpError("gamdp_ctx_walk_skip_backoff_stats failed on context %d" % i)
-            out.append(st.as_dict())
-        return out
+        return self._walk_stats("gamdp_ctx_walk_skip_backoff_stats", L.WalkSkipBackoffStats)
 
     def l1_chain_stats(self):
         """Context.l1_chain_stats of every context of the handle (a list of dicts)."""

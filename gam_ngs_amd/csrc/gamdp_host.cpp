@@ -87,10 +87,9 @@ const Tuning& tuning()
         if ((e = std::getenv("GAMDP_L1_DEVICE_HITS"))) x.l1_device_hits = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_L1_CHAIN_CARRY"))) x.l1_chain_carry = std::atoi(e) == 1;
         if ((e = std::getenv("GAMDP_L1_WALK_ANY_BAND"))) x.l1_walk_any_band = std::atoi(e) == 1;
-        if ((e = std::getenv("GAMDP_WALK_SKIP"))) x.walk_skip = std::atoi(e) == 1;
-        if ((e = std::getenv("GAMDP_WALK_SKIP_PAIR"))) x.walk_skip_pair = std::atoi(e) == 1;
-        if ((e = std::getenv("GAMDP_WALK_SKIP_I32"))) x.walk_skip_i32 = std::atoi(e) == 1;
-        if ((e = std::getenv("GAMDP_WALK_SKIP_BACKOFF"))) x.walk_skip_backoff = std::atoi(e) == 1;
+        for (int f = 0; f < WS_COUNT; f++)
+            if ((e = std::getenv(walk_skip_families[f].env))) x.walk_skip.family[f] = std::atoi(e) == 1 ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
+        if ((e = std::getenv("GAMDP_WALK_SKIP_BACKOFF"))) x.walk_skip.backoff = std::atoi(e) == 1 ? GAMDP_WALK_BACKOFF_ON : GAMDP_WALK_BACKOFF_OFF;
         return x;
     }();
     return t;
@@ -311,10 +310,7 @@ int Ctx::init(int dev)
     l1_hits_mode = tuning().l1_device_hits ? GAMDP_L1_HITS_DEVICE : GAMDP_L1_HITS_HOST;
     l1_chain = tuning().l1_chain_carry ? GAMDP_L1_CHAIN_CARRY : GAMDP_L1_CHAIN_WALK;
     walk_bands = tuning().l1_walk_any_band ? GAMDP_L1_WALK_ANY_BAND : GAMDP_L1_WALK_BAND_150;
-    walk_skip = tuning().walk_skip ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
-    walk_skip_pair = tuning().walk_skip_pair ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
-    walk_skip_i32 = tuning().walk_skip_i32 ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
-    walk_skip_backoff = tuning().walk_skip_backoff ? GAMDP_WALK_BACKOFF_ON : GAMDP_WALK_BACKOFF_OFF;
+    walk_skip = tuning().walk_skip;
     if (hipSetDevice(dev) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("hipGetDeviceProperties failed"); return GAMDP_ENODEV; }
@@ -871,25 +867,18 @@ int Ctx::align_scratch(u64 arena_call)
 // whether a launch of the two-task kernel walks its two tasks side by side (LP_WALK_SIDE_BY_SIDE)
 static bool walks_side_by_side(const Launch& L) { return L.kid == K_P17_CE4 && (u64)L.count / 2 <= tuning().side_walk_rounds * L.n_slots; }
 
-// the int32 direction-free kernels: one or four tasks per wavefront, checkpoint rows as int32 images (gamdp_ctx_set_walk_skip_i32)
-static bool walks_on_i32_images(const int kid)
-{
-    return kid == K_C17_CE4 || kid == K_C17_CE4_N || kid == K_Q19_CE15 || kid == K_Q19_CE15_N || kid == K_GEN_C9 || kid == K_GEN_C17;
-}
-
 // LaunchParams::flags / prio_* of a launch
-static void launch_policy(const Launch& L, LaunchParams& p, const int walk_skip, const int walk_skip_pair, const int walk_skip_i32, const int walk_skip_backoff)
+static void launch_policy(const Launch& L, LaunchParams& p, const WalkSkipModes& walk_skip)
 {
     const Tuning& tu = tuning();
     const u64 tpw = (u64)kernel_info[L.kid].tasks_per_wave, units = L.count / tpw;
     p.flags = walks_side_by_side(L) ? LP_WALK_SIDE_BY_SIDE : 0u;
     if (tu.no_packed_top) p.flags |= LP_NO_PACKED_TOP;
     if (tu.no_packed_top_mixed) p.flags |= LP_NO_PACKED_TOP_MIXED;
-    if (L.kid == K_O19_CE15 && walk_skip == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_DIAG;   // (gamdp_ctx_set_walk_skip; the eight-task kernel alone has the test)
-    if (L.kid == K_P17_CE4 && walk_skip_pair == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_PAIR;   // (gamdp_ctx_set_walk_skip_pair; the two-task kernel, both of its walk paths)
-    if (walks_on_i32_images(L.kid) && walk_skip_i32 == GAMDP_WALK_SKIP_DIAG) p.flags |= LP_WALK_SKIP_I32;   // (gamdp_ctx_set_walk_skip_i32; the six int32 direction-free kernels)
-    // (gamdp_ctx_set_walk_skip_backoff: only beside a test to back off from)
-    if (walk_skip_backoff == GAMDP_WALK_BACKOFF_ON && (p.flags & (LP_WALK_SKIP_DIAG | LP_WALK_SKIP_PAIR | LP_WALK_SKIP_I32))) p.flags |= LP_WALK_SKIP_BACKOFF;
+    // (gamdp_ctx_set_walk_skip, _pair, _i32: the test of the kernel's family; gamdp_ctx_set_walk_skip_backoff: only beside a test to back off from)
+    const int ws = walk_skip_family(L.kid);
+    if (ws >= 0 && walk_skip.family[ws] == GAMDP_WALK_SKIP_DIAG)
+        p.flags |= walk_skip_families[ws].flag | (walk_skip.backoff == GAMDP_WALK_BACKOFF_ON ? LP_WALK_SKIP_BACKOFF : 0u);
     // the end-cell / strip / walk phase of the two- and eight-task kernels issues one level above a steady-state fill in
     // launches of more than two rounds (gamdp_dev.h; GAMDP_WALK_PRIO=0..3 overrides, A/B)
     p.flags |= (tu.walk_prio >= 0 ? (u32)tu.walk_prio : (units > 2ull * L.n_slots ? 1u : 0u)) << LP_WALK_PRIO_SHIFT;
@@ -947,7 +936,7 @@ int Ctx::align_run(AlignCall& a)
         p.scratch = d_scratch + L.scratch_off; p.slot_words = L.slot_words; p.dir_words = L.dir_words; p.ypad = L.ypad;
         p.ckpt_off = L.ckpt_off; p.bnd_off = L.bnd_off;
         p.stats = d_stats + li * LS_COUNT;
-        launch_policy(L, p, walk_skip, walk_skip_pair, walk_skip_i32, walk_skip_backoff);
+        launch_policy(L, p, walk_skip);
         hipStream_t const on = L.aux ? aux_stream : stream;
         HIPCHK(this, hipEventRecord(events[li].first, on));
         const int e = launch_align(L.kid, p, L.n_slots, L.dyn_lds, on);
@@ -1009,30 +998,15 @@ void Ctx::align_collect(AlignCall& a)
             const u32* st = a.hstats.data() + li * LS_COUNT;
             r.units_dirfree = st[LS_DIRFREE]; r.units_packed_top = st[LS_PACKED_TOP]; r.units_packed_top_mixed = st[LS_PACKED_TOP_MIXED];
             r.strips = st[LS_STRIPS]; r.units_top_wanted = st[LS_TOP_WANTED];
-            if (L.kid == K_O19_CE15) {   // gamdp_ctx_walk_skip_stats: the eight-task launches of the call
-                gamdp_walk_skip_stats& W = last_walk_skip;
-                W.tests += st[LS_SKIP_TESTS]; W.groups_tested += st[LS_SKIP_TESTED]; W.groups_skipped += st[LS_SKIP_GROUPS];
-                W.rows_skipped += 64ull * st[LS_SKIP_GROUPS] - st[LS_SKIP_SHORT];
-                W.strips += st[LS_STRIPS];
-                last_walk_skip_backoff.held += st[LS_SKIP_HELD];   // gamdp_ctx_walk_skip_backoff_stats, family by family
-            }
-            if (L.kid == K_P17_CE4) {   // gamdp_ctx_walk_skip_pair_stats: the two-task launches of the call
-                gamdp_walk_skip_pair_stats& W = last_walk_skip_pair;
-                W.tests += st[LS_SKIP_TESTS]; W.groups_tested += st[LS_SKIP_TESTED]; W.groups_skipped += st[LS_SKIP_GROUPS];
-                W.rows_skipped += 64ull * st[LS_SKIP_GROUPS] - st[LS_SKIP_SHORT];
-                W.strips += st[LS_STRIPS];
-                if (walks_side_by_side(L)) W.launches_side_by_side++; else W.launches_one_by_one++;
-                W.mode = (uint32_t)walk_skip_pair;   // (everything stays 0 when the call makes no two-task launch)
-                last_walk_skip_backoff.held_pair += st[LS_SKIP_HELD];
-            }
-            if (walks_on_i32_images(L.kid)) {   // gamdp_ctx_walk_skip_i32_stats: the call's launches of the six int32 direction-free kernels
-                gamdp_walk_skip_i32_stats& W = last_walk_skip_i32;
-                W.tests += st[LS_SKIP_TESTS]; W.groups_tested += st[LS_SKIP_TESTED]; W.groups_skipped += st[LS_SKIP_GROUPS];
-                W.rows_skipped += 64ull * st[LS_SKIP_GROUPS] - st[LS_SKIP_SHORT];
-                W.strips += st[LS_STRIPS];
-                W.launches++;
-                W.mode = (uint32_t)walk_skip_i32;   // (everything stays 0 when the call makes no such launch)
-                last_walk_skip_backoff.held_i32 += st[LS_SKIP_HELD];
+            if (const int ws = walk_skip_family(L.kid); ws >= 0) {   // gamdp_ctx_walk_skip*_stats: the call's launches of the kernel's family
+                WalkSkipCount one;
+                one.tests = st[LS_SKIP_TESTS]; one.groups_tested = st[LS_SKIP_TESTED]; one.groups_skipped = st[LS_SKIP_GROUPS];
+                one.rows_skipped = 64ull * st[LS_SKIP_GROUPS] - st[LS_SKIP_SHORT];
+                one.strips = st[LS_STRIPS];
+                one.held = st[LS_SKIP_HELD];
+                one.launches = 1; one.launches_side_by_side = walks_side_by_side(L) ? 1u : 0u;
+                one.ran = true;
+                walk_skip_count[ws].add(one);
             }
             r.piece = log_piece;
             r.rounds = L.n_slots ? (double)r.units / (double)L.n_slots : 0.0;
@@ -1365,12 +1339,7 @@ int Ctx::align_fp(const gamdp_task* tasks, const SeqSet* sa, const SeqSet* sb, c
         TaskSrc src;
         src.gt = tasks + first; src.sa = sa; src.sb = sb;
         launch_log.clear();
-        last_walk_skip = gamdp_walk_skip_stats{};
-        last_walk_skip.mode = (uint32_t)walk_skip;
-        last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
-        last_walk_skip_i32 = gamdp_walk_skip_i32_stats{};
-        last_walk_skip_backoff = gamdp_walk_skip_backoff_stats{};
-        last_walk_skip_backoff.mode = (uint32_t)walk_skip_backoff;
+        reset_walk_skip_counts();
         if ((rc_ = align(src, cnt, out + first, nullptr, caps.data() + first))) return rc_;
         // the strings of the chunk: where align() put them (w_prep), how long the walks made them (out)
         fpt.clear(); seg_first.clear();
@@ -1526,6 +1495,30 @@ static bool batch_pieces(const gamdp_task* tasks, size_t n, const SeqSet* sb, in
     return true;
 }
 
+// ---- walk skip: what the three setters and the four getters of the C ABI share ----------------------------
+
+static int set_walk_skip_mode(gamdp_ctx* ctx, int family, int mode)
+{
+    if ((mode != GAMDP_WALK_STRIPS && mode != GAMDP_WALK_SKIP_DIAG) || !ctx) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->walk_skip.family[family] = mode;
+    return 0;
+}
+
+// The counters every family's public struct has, and the GAMDP_WALK_* the call ran in: of the eight-task kernel's struct at every
+// call, of the others while the call made a launch of the family (everything stays 0 otherwise).  The rest of *out is zeroed.
+template <class S>
+static const WalkSkipCount* walk_skip_stats(const gamdp_ctx* ctx, int family, S* out)
+{
+    if (!ctx || !out) return nullptr;
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    const WalkSkipCount& n = c->walk_skip_count[family];
+    *out = S{};
+    out->tests = n.tests; out->groups_tested = n.groups_tested; out->groups_skipped = n.groups_skipped; out->rows_skipped = n.rows_skipped;
+    out->strips = n.strips;
+    out->mode = (family == WS_O19 || n.ran) ? (uint32_t)c->walk_skip_ran.family[family] : 0u;
+    return &n;
+}
+
 }  // namespace gamdp
 
 // ---- C ABI ----------------------------------------------------------------------------------------
@@ -1587,35 +1580,21 @@ int gamdp_ctx_launch_info(const gamdp_ctx* ctx, gamdp_launch_info* out, size_t c
 static_assert(sizeof(gamdp_walk_skip_stats) == 48 && offsetof(gamdp_walk_skip_stats, strips) == 32 && offsetof(gamdp_walk_skip_stats, mode) == 40,
               "gamdp_walk_skip_stats: the layout include/gamdp.h documents (gam_ngs_amd/lib.py WalkSkipStats mirrors it)");
 
-int gamdp_ctx_set_walk_skip(gamdp_ctx* ctx, int mode)
-{
-    if ((mode != GAMDP_WALK_STRIPS && mode != GAMDP_WALK_SKIP_DIAG) || !ctx) return GAMDP_EINVAL;
-    reinterpret_cast<Ctx*>(ctx)->walk_skip = mode;
-    return 0;
-}
+int gamdp_ctx_set_walk_skip(gamdp_ctx* ctx, int mode) { return set_walk_skip_mode(ctx, WS_O19, mode); }
 
-int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out)
-{
-    if (!ctx || !out) return GAMDP_EINVAL;
-    *out = reinterpret_cast<const Ctx*>(ctx)->last_walk_skip;
-    return 0;
-}
+int gamdp_ctx_walk_skip_stats(const gamdp_ctx* ctx, gamdp_walk_skip_stats* out) { return walk_skip_stats(ctx, WS_O19, out) ? 0 : GAMDP_EINVAL; }
 
 static_assert(sizeof(gamdp_walk_skip_pair_stats) == 56 && offsetof(gamdp_walk_skip_pair_stats, strips) == 32 && offsetof(gamdp_walk_skip_pair_stats, mode) == 40 &&
               offsetof(gamdp_walk_skip_pair_stats, launches_side_by_side) == 44 && offsetof(gamdp_walk_skip_pair_stats, launches_one_by_one) == 48,
               "gamdp_walk_skip_pair_stats: the layout include/gamdp.h documents (gam_ngs_amd/lib.py WalkSkipPairStats mirrors it)");
 
-int gamdp_ctx_set_walk_skip_pair(gamdp_ctx* ctx, int mode)
-{
-    if ((mode != GAMDP_WALK_STRIPS && mode != GAMDP_WALK_SKIP_DIAG) || !ctx) return GAMDP_EINVAL;
-    reinterpret_cast<Ctx*>(ctx)->walk_skip_pair = mode;
-    return 0;
-}
+int gamdp_ctx_set_walk_skip_pair(gamdp_ctx* ctx, int mode) { return set_walk_skip_mode(ctx, WS_P17, mode); }
 
 int gamdp_ctx_walk_skip_pair_stats(const gamdp_ctx* ctx, gamdp_walk_skip_pair_stats* out)
 {
-    if (!ctx || !out) return GAMDP_EINVAL;
-    *out = reinterpret_cast<const Ctx*>(ctx)->last_walk_skip_pair;
+    const WalkSkipCount* n = walk_skip_stats(ctx, WS_P17, out);
+    if (!n) return GAMDP_EINVAL;
+    out->launches_side_by_side = n->launches_side_by_side; out->launches_one_by_one = n->launches - n->launches_side_by_side;
     return 0;
 }
 
@@ -1623,17 +1602,13 @@ static_assert(sizeof(gamdp_walk_skip_i32_stats) == 48 && offsetof(gamdp_walk_ski
               offsetof(gamdp_walk_skip_i32_stats, launches) == 44,
               "gamdp_walk_skip_i32_stats: the layout include/gamdp.h documents (gam_ngs_amd/lib.py WalkSkipI32Stats mirrors it)");
 
-int gamdp_ctx_set_walk_skip_i32(gamdp_ctx* ctx, int mode)
-{
-    if ((mode != GAMDP_WALK_STRIPS && mode != GAMDP_WALK_SKIP_DIAG) || !ctx) return GAMDP_EINVAL;
-    reinterpret_cast<Ctx*>(ctx)->walk_skip_i32 = mode;
-    return 0;
-}
+int gamdp_ctx_set_walk_skip_i32(gamdp_ctx* ctx, int mode) { return set_walk_skip_mode(ctx, WS_I32, mode); }
 
 int gamdp_ctx_walk_skip_i32_stats(const gamdp_ctx* ctx, gamdp_walk_skip_i32_stats* out)
 {
-    if (!ctx || !out) return GAMDP_EINVAL;
-    *out = reinterpret_cast<const Ctx*>(ctx)->last_walk_skip_i32;
+    const WalkSkipCount* n = walk_skip_stats(ctx, WS_I32, out);
+    if (!n) return GAMDP_EINVAL;
+    out->launches = n->launches;
     return 0;
 }
 
@@ -1644,7 +1619,7 @@ static_assert(sizeof(gamdp_walk_skip_backoff_stats) == 32 && offsetof(gamdp_walk
 int gamdp_ctx_set_walk_skip_backoff(gamdp_ctx* ctx, int mode)
 {
     if ((mode != GAMDP_WALK_BACKOFF_OFF && mode != GAMDP_WALK_BACKOFF_ON) || !ctx) return GAMDP_EINVAL;
-    reinterpret_cast<Ctx*>(ctx)->walk_skip_backoff = mode;
+    reinterpret_cast<Ctx*>(ctx)->walk_skip.backoff = mode;
     return 0;
 }
 
@@ -1653,7 +1628,10 @@ uint32_t gamdp_walk_skip_backoff_hold(uint32_t fails) { return walk_backoff_hold
 int gamdp_ctx_walk_skip_backoff_stats(const gamdp_ctx* ctx, gamdp_walk_skip_backoff_stats* out)
 {
     if (!ctx || !out) return GAMDP_EINVAL;
-    *out = reinterpret_cast<const Ctx*>(ctx)->last_walk_skip_backoff;
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    *out = gamdp_walk_skip_backoff_stats{};
+    out->held = c->walk_skip_count[WS_O19].held; out->held_pair = c->walk_skip_count[WS_P17].held; out->held_i32 = c->walk_skip_count[WS_I32].held;
+    out->mode = (uint32_t)c->walk_skip_ran.backoff;
     return 0;
 }
 
@@ -1695,12 +1673,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     const SeqSet* sa = reinterpret_cast<const SeqSet*>(set_a);
     const SeqSet* sb = reinterpret_cast<const SeqSet*>(set_b);
     c->launch_log.clear();
-    c->last_walk_skip = gamdp_walk_skip_stats{};
-    c->last_walk_skip.mode = (uint32_t)c->walk_skip;
-    c->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
-    c->last_walk_skip_i32 = gamdp_walk_skip_i32_stats{};
-    c->last_walk_skip_backoff = gamdp_walk_skip_backoff_stats{};
-    c->last_walk_skip_backoff.mode = (uint32_t)c->walk_skip_backoff;
+    c->reset_walk_skip_counts();
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; for (Ctx* h : c->helpers) h->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {
@@ -1735,10 +1708,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     cc[0]->trim_scratch(); cc[1]->trim_scratch();
     cc[1]->kernel_ms = 0; cc[1]->kernel_launches = 0;
     cc[1]->launch_log.clear(); cc[1]->log_launches = true;
-    cc[1]->walk_skip = c->walk_skip; cc[1]->last_walk_skip = gamdp_walk_skip_stats{};
-    cc[1]->walk_skip_pair = c->walk_skip_pair; cc[1]->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
-    cc[1]->walk_skip_i32 = c->walk_skip_i32; cc[1]->last_walk_skip_i32 = gamdp_walk_skip_i32_stats{};
-    cc[1]->walk_skip_backoff = c->walk_skip_backoff; cc[1]->last_walk_skip_backoff = gamdp_walk_skip_backoff_stats{};
+    copy_walk_skip_modes(cc[1], c);
     int rc[2] = {0, 0};
     auto worker = [&](int t) noexcept {
         for (size_t k = (size_t)t; k < 4 && rc[t] == 0; k += 2) {
@@ -1754,30 +1724,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     }
     c->kernel_ms += cc[1]->kernel_ms; c->kernel_launches += cc[1]->kernel_launches;
     c->launch_log.insert(c->launch_log.end(), cc[1]->launch_log.begin(), cc[1]->launch_log.end());
-    {
-        gamdp_walk_skip_stats& W = c->last_walk_skip;
-        const gamdp_walk_skip_stats& H = cc[1]->last_walk_skip;
-        W.tests += H.tests; W.groups_tested += H.groups_tested; W.groups_skipped += H.groups_skipped; W.rows_skipped += H.rows_skipped; W.strips += H.strips;
-    }
-    {
-        gamdp_walk_skip_pair_stats& W = c->last_walk_skip_pair;
-        const gamdp_walk_skip_pair_stats& H = cc[1]->last_walk_skip_pair;
-        W.tests += H.tests; W.groups_tested += H.groups_tested; W.groups_skipped += H.groups_skipped; W.rows_skipped += H.rows_skipped; W.strips += H.strips;
-        W.launches_side_by_side += H.launches_side_by_side; W.launches_one_by_one += H.launches_one_by_one;
-        W.mode |= H.mode;   // (the helper runs in the owner's mode)
-    }
-    {
-        gamdp_walk_skip_i32_stats& W = c->last_walk_skip_i32;
-        const gamdp_walk_skip_i32_stats& H = cc[1]->last_walk_skip_i32;
-        W.tests += H.tests; W.groups_tested += H.groups_tested; W.groups_skipped += H.groups_skipped; W.rows_skipped += H.rows_skipped; W.strips += H.strips;
-        W.launches += H.launches;
-        W.mode |= H.mode;   // (the same)
-    }
-    {
-        gamdp_walk_skip_backoff_stats& W = c->last_walk_skip_backoff;
-        const gamdp_walk_skip_backoff_stats& H = cc[1]->last_walk_skip_backoff;
-        W.held += H.held; W.held_pair += H.held_pair; W.held_i32 += H.held_i32;
-    }
+    for (int f = 0; f < WS_COUNT; f++) c->walk_skip_count[f].add(cc[1]->walk_skip_count[f]);   // (the helper ran in the owner's modes)
     std::stable_sort(c->launch_log.begin(), c->launch_log.end(), [](const gamdp_launch_info& x, const gamdp_launch_info& y) { return x.piece < y.piece; });
     if (rc[1]) c->set_error(cc[1]->err);
     return rc[0] ? rc[0] : rc[1];
@@ -1883,12 +1830,7 @@ int gamdp_align_batch_fp(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_
     if (!ctx || !set_a || !set_b || !out || !ops_fp || (n && !tasks)) return GAMDP_EINVAL;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     c->launch_log.clear();
-    c->last_walk_skip = gamdp_walk_skip_stats{};
-    c->last_walk_skip.mode = (uint32_t)c->walk_skip;
-    c->last_walk_skip_pair = gamdp_walk_skip_pair_stats{};
-    c->last_walk_skip_i32 = gamdp_walk_skip_i32_stats{};
-    c->last_walk_skip_backoff = gamdp_walk_skip_backoff_stats{};
-    c->last_walk_skip_backoff.mode = (uint32_t)c->walk_skip_backoff;
+    c->reset_walk_skip_counts();
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {

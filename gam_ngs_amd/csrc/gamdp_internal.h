@@ -34,6 +34,61 @@ struct Diag {
 };
 const Diag& diag();
 
+// The kernel families whose walks can jump over indel-free groups, one property of the C ABI each (gamdp_ctx_set_walk_skip, _pair,
+// _i32): the launch flag that switches the test on, the environment variable that makes GAMDP_WALK_SKIP_DIAG the mode of new
+// contexts, and the family's kernels.
+enum WalkSkipFamilyId : int {
+    WS_O19 = 0,   // the eight-task kernel
+    WS_P17,       // the two-task kernel, both of its walk paths
+    WS_I32,       // the six int32 direction-free kernels: one or four tasks per wavefront, checkpoint rows as int32 images
+    WS_COUNT
+};
+struct WalkSkipFamily {
+    u32 flag;
+    const char* env;
+    bool (*has)(int kid);
+};
+constexpr WalkSkipFamily walk_skip_families[WS_COUNT] = {
+    {LP_WALK_SKIP_DIAG, "GAMDP_WALK_SKIP", [](int kid) { return kid == K_O19_CE15; }},
+    {LP_WALK_SKIP_PAIR, "GAMDP_WALK_SKIP_PAIR", [](int kid) { return kid == K_P17_CE4; }},
+    {LP_WALK_SKIP_I32, "GAMDP_WALK_SKIP_I32", [](int kid) { return kid == K_C17_CE4 || kid == K_C17_CE4_N || kid == K_Q19_CE15 || kid == K_Q19_CE15_N || kid == K_GEN_C9 || kid == K_GEN_C17; }},
+};
+// the family of a kernel, -1 for a kernel whose walks have no test
+constexpr int walk_skip_family(int kid)
+{
+    for (int f = 0; f < WS_COUNT; f++)
+        if (walk_skip_families[f].has(kid)) return f;
+    return -1;
+}
+static_assert([] {
+    for (int kid = 0; kid < K_COUNT; kid++) {
+        int n = 0;
+        for (int f = 0; f < WS_COUNT; f++) n += walk_skip_families[f].has(kid) ? 1 : 0;
+        if (n > 1) return false;
+    }
+    return true;
+}(), "walk_skip_families: no kernel is in two families");
+
+// The four properties of a context: GAMDP_WALK_* per family, GAMDP_WALK_BACKOFF_* for whichever of them is on
+static_assert(GAMDP_WALK_STRIPS == 0 && GAMDP_WALK_BACKOFF_OFF == 0, "WalkSkipModes: the defaults are 0");
+struct WalkSkipModes {
+    int family[WS_COUNT] = {};
+    int backoff = 0;
+};
+// What a family's launches of one gamdp_align_batch counted (the LS_SKIP_* words of gamdp_dev.h, summed): what the four public
+// statistics structs are filled from
+struct WalkSkipCount {
+    u64 tests = 0, groups_tested = 0, groups_skipped = 0, rows_skipped = 0, strips = 0;
+    u64 held = 0;                                  // points passed without a test (backoff)
+    u32 launches = 0, launches_side_by_side = 0;   // (side by side: the two-task kernel)
+    bool ran = false;                              // the call launched a kernel of the family
+    void add(const WalkSkipCount& o)
+    {
+        tests += o.tests; groups_tested += o.groups_tested; groups_skipped += o.groups_skipped; rows_skipped += o.rows_skipped; strips += o.strips;
+        held += o.held; launches += o.launches; launches_side_by_side += o.launches_side_by_side; ran |= o.ran;
+    }
+};
+
 // Product-library switches (environment, read once per process: gamdp_host.cpp).  None changes a result: each takes the planner
 // to the other side of a threshold that real inputs also reach (A/B measurements, and a second way through the tests).
 struct Tuning {
@@ -57,10 +112,7 @@ struct Tuning {
     bool l1_device_hits = false;        // GAMDP_L1_DEVICE_HITS=1: new contexts start in GAMDP_L1_HITS_DEVICE mode (gamdp_ctx_set_l1_hits)
     bool l1_chain_carry = false;        // GAMDP_L1_CHAIN_CARRY=1: new contexts start in GAMDP_L1_CHAIN_CARRY mode (gamdp_ctx_set_l1_chain)
     bool l1_walk_any_band = false;      // GAMDP_L1_WALK_ANY_BAND=1: new contexts start with GAMDP_L1_WALK_ANY_BAND (gamdp_ctx_set_l1_walk_bands)
-    bool walk_skip = false;             // GAMDP_WALK_SKIP=1: new contexts start in GAMDP_WALK_SKIP_DIAG mode (gamdp_ctx_set_walk_skip)
-    bool walk_skip_pair = false;        // GAMDP_WALK_SKIP_PAIR=1: ... and in GAMDP_WALK_SKIP_DIAG mode of gamdp_ctx_set_walk_skip_pair
-    bool walk_skip_i32 = false;         // GAMDP_WALK_SKIP_I32=1: ... and of gamdp_ctx_set_walk_skip_i32
-    bool walk_skip_backoff = false;     // GAMDP_WALK_SKIP_BACKOFF=1: new contexts start in GAMDP_WALK_BACKOFF_ON mode (gamdp_ctx_set_walk_skip_backoff)
+    WalkSkipModes walk_skip;            // GAMDP_WALK_SKIP=1, _PAIR=1, _I32=1 (walk_skip_families), GAMDP_WALK_SKIP_BACKOFF=1: the modes new contexts start in
 };
 const Tuning& tuning();
 
@@ -220,20 +272,17 @@ struct Ctx {
     int l1_chain = GAMDP_L1_CHAIN_WALK;
     int walk_bands = GAMDP_L1_WALK_BAND_150;   // WALK mode: the bands that have a chain kernel (gamdp_ctx_set_l1_walk_bands); CARRY ignores it
     gamdp_l1_chain_stats last_l1_chain{};
-    // whether the eight-task kernel's walks jump over indel-free groups (gamdp_ctx_set_walk_skip -> LP_WALK_SKIP_DIAG), and what the
-    // eight-task launches of the last gamdp_align_batch counted (align_collect adds while log_launches is set)
-    int walk_skip = GAMDP_WALK_STRIPS;
-    gamdp_walk_skip_stats last_walk_skip{};
-    // the same for the two-task band-512 kernel, a property of its own (gamdp_ctx_set_walk_skip_pair -> LP_WALK_SKIP_PAIR)
-    int walk_skip_pair = GAMDP_WALK_STRIPS;
-    gamdp_walk_skip_pair_stats last_walk_skip_pair{};
-    // ... and for the int32 direction-free kernels, a third property (gamdp_ctx_set_walk_skip_i32 -> LP_WALK_SKIP_I32)
-    int walk_skip_i32 = GAMDP_WALK_STRIPS;
-    gamdp_walk_skip_i32_stats last_walk_skip_i32{};
-    // whether the walks of those three back off from the test after failures, a fourth property that applies to whichever of them is
-    // on (gamdp_ctx_set_walk_skip_backoff -> LP_WALK_SKIP_BACKOFF), and the candidate points the last gamdp_align_batch did not test
-    int walk_skip_backoff = GAMDP_WALK_BACKOFF_OFF;
-    gamdp_walk_skip_backoff_stats last_walk_skip_backoff{};
+    // whether the walks of a family's kernels jump over indel-free groups (gamdp_ctx_set_walk_skip, _pair, _i32 -> the family's launch
+    // flag) and back off from the test after failures (gamdp_ctx_set_walk_skip_backoff -> LP_WALK_SKIP_BACKOFF); the modes the last
+    // gamdp_align_batch ran in (all 0 before the first) and what its launches counted, family by family (align_collect adds while
+    // log_launches is set): gamdp_ctx_walk_skip*_stats
+    WalkSkipModes walk_skip, walk_skip_ran;
+    WalkSkipCount walk_skip_count[WS_COUNT];
+    void reset_walk_skip_counts()   // at the start of a gamdp_align_batch
+    {
+        for (WalkSkipCount& n : walk_skip_count) n = WalkSkipCount{};
+        walk_skip_ran = walk_skip;
+    }
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }
@@ -310,6 +359,12 @@ struct Ctx {
     int align(const std::vector<ITask>& tasks, gamdp_result* out, const gamdp_ops* ops) { return align(tasks.data(), tasks.size(), out, ops); }
     ~Ctx();
 };
+// a helper context launches for its owner: in the owner's modes, its counts from zero
+inline void copy_walk_skip_modes(Ctx* to, const Ctx* from)
+{
+    to->walk_skip = from->walk_skip;
+    to->reset_walk_skip_counts();
+}
 
 // what gamdp_fasta points to: the host-side RefSequence (names + 1 B/base codes), no GPU involved
 struct Fasta {

@@ -1157,7 +1157,7 @@ extern "C" int gamdp_align_merge_blocks(gamdp_ctx* ctx, const gamdp_seqset* mast
             if (!h || h->init(c->device) != 0) { c->set_error("helper context: " + (h ? h->err : std::string("out of memory"))); delete h; return GAMDP_ENODEV; }
             c->helpers.push_back(h);
         }
-        for (Ctx* h : c->helpers) { h->walk_skip = c->walk_skip; h->walk_skip_pair = c->walk_skip_pair; h->walk_skip_i32 = c->walk_skip_i32; h->walk_skip_backoff = c->walk_skip_backoff; }   // (gamdp_ctx_set_walk_skip, _pair, _i32, _backoff: the helpers launch for this context)
+        for (Ctx* h : c->helpers) copy_walk_skip_modes(h, c);   // (gamdp_ctx_set_walk_skip, _pair, _i32, _backoff: the helpers launch for this context)
         if (c->arena_budget(true) == 0) { c->set_error("hipMemGetInfo failed"); return GAMDP_EHIP; }
         ArenaSplit arena(c, K);
         std::vector<u32> part(n, 0);

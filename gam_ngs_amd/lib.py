@@ -324,28 +324,19 @@ def load_library():
     lib.gamdp_ctx_set_l1_walk_bands.restype = C.c_int
     lib.gamdp_ctx_l1_chain_stats.argtypes = [vp, C.POINTER(L1ChainStats)]
     lib.gamdp_ctx_l1_chain_stats.restype = C.c_int
-    if hasattr(lib, "gamdp_ctx_set_walk_skip"):   # (tools/ab_kernel.py loads older builds through GAMDP_LIB, for A/B against them)
-        lib.gamdp_ctx_set_walk_skip.argtypes = [vp, C.c_int]
-        lib.gamdp_ctx_set_walk_skip.restype = C.c_int
-        lib.gamdp_ctx_walk_skip_stats.argtypes = [vp, C.POINTER(WalkSkipStats)]
-        lib.gamdp_ctx_walk_skip_stats.restype = C.c_int
-    if hasattr(lib, "gamdp_ctx_set_walk_skip_pair"):   # (the same)
-        lib.gamdp_ctx_set_walk_skip_pair.argtypes = [vp, C.c_int]
-        lib.gamdp_ctx_set_walk_skip_pair.restype = C.c_int
-        lib.gamdp_ctx_walk_skip_pair_stats.argtypes = [vp, C.POINTER(WalkSkipPairStats)]
-        lib.gamdp_ctx_walk_skip_pair_stats.restype = C.c_int
-    if hasattr(lib, "gamdp_ctx_set_walk_skip_i32"):   # (the same)
-        lib.gamdp_ctx_set_walk_skip_i32.argtypes = [vp, C.c_int]
-        lib.gamdp_ctx_set_walk_skip_i32.restype = C.c_int
-        lib.gamdp_ctx_walk_skip_i32_stats.argtypes = [vp, C.POINTER(WalkSkipI32Stats)]
-        lib.gamdp_ctx_walk_skip_i32_stats.restype = C.c_int
-    if hasattr(lib, "gamdp_ctx_set_walk_skip_backoff"):   # (the same)
-        lib.gamdp_ctx_set_walk_skip_backoff.argtypes = [vp, C.c_int]
-        lib.gamdp_ctx_set_walk_skip_backoff.restype = C.c_int
+    # (a guard per pair: tools/ab_kernel.py loads older builds through GAMDP_LIB, for A/B against them)
+    for setter, getter, struct in (("gamdp_ctx_set_walk_skip", "gamdp_ctx_walk_skip_stats", WalkSkipStats),
+                                   ("gamdp_ctx_set_walk_skip_pair", "gamdp_ctx_walk_skip_pair_stats", WalkSkipPairStats),
+                                   ("gamdp_ctx_set_walk_skip_i32", "gamdp_ctx_walk_skip_i32_stats", WalkSkipI32Stats),
+                                   ("gamdp_ctx_set_walk_skip_backoff", "gamdp_ctx_walk_skip_backoff_stats", WalkSkipBackoffStats)):
+        if hasattr(lib, setter):
+            getattr(lib, setter).argtypes = [vp, C.c_int]
+            getattr(lib, setter).restype = C.c_int
+            getattr(lib, getter).argtypes = [vp, C.POINTER(struct)]
+            getattr(lib, getter).restype = C.c_int
+    if hasattr(lib, "gamdp_walk_skip_backoff_hold"):
         lib.gamdp_walk_skip_backoff_hold.argtypes = [C.c_uint32]
         lib.gamdp_walk_skip_backoff_hold.restype = C.c_uint32
-        lib.gamdp_ctx_walk_skip_backoff_stats.argtypes = [vp, C.POINTER(WalkSkipBackoffStats)]
-        lib.gamdp_ctx_walk_skip_backoff_stats.restype = C.c_int
     lib.gamdp_ctx_l1_hits_stats.argtypes = [vp, C.POINTER(L1HitsStats)]
     lib.gamdp_ctx_l1_hits_stats.restype = C.c_int
     lib.gamdp_ctx_l1_tail_calls.argtypes = [vp, C.POINTER(L1TailCall), C.c_size_t, C.POINTER(C.c_size_t)]

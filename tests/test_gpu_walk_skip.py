@@ -11,130 +11,26 @@ Sizes: the direction-free range of a call begins behind the ramp and the top blo
 64 row-times; SHORT is the shortest length (a multiple of 16 bases, identical pair, whole sequences) at which the range holds at
 least 3 groups -- found on the device by the child itself and asserted -- and the cases use SHORT, about twice SHORT and pairs of
 3 - 6 kb."""
-import functools
 import os
 import random
-import subprocess
-import sys
 
 import pytest
 
 import _cases
 import _oracle as O
+import _walkskip as W
 import gam_ngs_amd as gam
+from _walkskip import both, case, ctx, gap_free, one_indel, oracle_all, run, short_length, sizes, substituted
 from gam_ngs_amd import lib as L
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-DIAG_LIB = os.path.join(ROOT, "gam_ngs_amd", "libgamdp_diag.so")
+FAMILY = "o19"           # of tests/_walkskip.py: every child of this file runs as that family (GAMDP_QUAD_MIN=1)
 BAND, C = 150, 19
-KERNEL = "k_align_o<19,15>"
-SWITCHES = ("GAMDP_QUAD_MIN", "GAMDP_NO_PAIR", "GAMDP_NO_MERGE_N", "GAMDP_WALK_SKIP", "GAMDP_LIB", "GAMDP_OCTO_MIN_ROWS", "GAMDP_NO_PACKED_TOP",
-            "GAMDP_NO_PACKED_TOP_MIXED")
-SHORT_SCAN = range(448, 1217, 16)   # where SHORT is looked for: by the block plan it lies near 35 blocks of 16 rows
+KERNEL = W.O19
 
 
 # ---- in the child ------------------------------------------------------------------------------------------------------------------
-
-@functools.lru_cache(maxsize=1)
-def ctx():
-    return gam.Context(0)
-
-
-def case(a, b, begin_a=0, end_a=None, begin_b=0, end_b=None, fs=False, fe=False):
-    return dict(a=a.encode(), b=b.encode(), band=BAND, begin_a=begin_a, end_a=len(a) - 1 if end_a is None else end_a, begin_b=begin_b,
-                end_b=len(b) - 1 if end_b is None else end_b, fs=fs, fe=fe)
-
-
-def run(cases, want_ops):
-    import _gpu
-    _gpu.ctx = ctx          # (run_cases on this module's context)
-    return _gpu.run_cases(cases, want_ops=want_ops)
-
-
-def oracle_all(cases):
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(16) as ex:   # (the oracle's C code runs outside the GIL)
-        return list(ex.map(lambda cs: O.oracle_align(O.encode(cs["a"]), O.encode(cs["b"]), cs["band"], cs["begin_a"], cs["end_a"], cs["begin_b"],
-                                                     cs["end_b"], cs["fs"], cs["fe"], want_ops=True), cases))
-
-
-def both(cases, want_ops=False, want=None, only_octo=True):
-    """The batch with the property off, then on, on one context.  Every result equals the oracle's and the other mode's.
-    -> (oracle answers, launch info off, launch info on, stats off, stats on)"""
-    c = ctx()
-    want = want or oracle_all(cases)
-    flags = list(want_ops) if isinstance(want_ops, (list, tuple)) else [bool(want_ops)] * len(cases)
-    out = {}
-    for mode in (L.WALK_STRIPS, L.WALK_SKIP_DIAG):
-        c.set_walk_skip(mode)
-        try:
-            res = run(cases, want_ops)
-        finally:
-            c.set_walk_skip(L.WALK_STRIPS)
-        info, st = c.launch_info(), c.walk_skip_stats()
-        assert st["mode"] == mode, st
-        if only_octo:
-            assert {r["kernel"] for r in info} == {KERNEL}, info
-        for k, (cs, r, (o, ops), f) in enumerate(zip(cases, res, want, flags)):
-            assert r.status != L.ST_DIAG_RANGE, (k, "a packed value left the exact range")
-            assert r.key() == o.key(), (mode, k, len(cs["a"]), len(cs["b"]), r.key(), o.key())
-            assert r.ops == (ops if f else None), (mode, k, "edit string")
-        out[mode] = (res, info, st)
-    for k, (r0, r1) in enumerate(zip(out[0][0], out[1][0])):
-        assert r0.key() == r1.key() and r0.ops == r1.ops and r0.cells == r1.cells, (k, r0.key(), r1.key())
-    st0, st1 = out[0][2], out[1][2]
-    assert st0["tests"] == st0["groups_tested"] == st0["groups_skipped"] == st0["rows_skipped"] == 0, st0
-    octo = lambda info: sum(r["strips"] for r in info if r["kernel"] == KERNEL)
-    assert st0["strips"] == octo(out[0][1]) and st1["strips"] == octo(out[1][1]), (st0, st1)
-    assert st1["groups_skipped"] <= st1["groups_tested"] <= 8 * st1["tests"], st1
-    assert 64 * st1["groups_skipped"] - 63 * st1["tests"] <= st1["rows_skipped"] <= 64 * st1["groups_skipped"], st1
-    print("  %d calls: strips off %d on %d, tests %d, groups tested %d skipped %d, rows skipped %d" %
-          (len(cases), st0["strips"], st1["strips"], st1["tests"], st1["groups_tested"], st1["groups_skipped"], st1["rows_skipped"]))
-    return want, out[0][1], out[1][1], st0, st1
-
-
-def gap_free(ops):
-    return set(ops) <= {"M", "X"}
-
-
-@functools.lru_cache(maxsize=1)
-def short_length():
-    """The shortest length of SHORT_SCAN at which an identical pair has a direction-free range of 3 groups or more: with the property
-    on an identical pair's walk jumps over every group of the range below its end cell, so groups_skipped counts them."""
-    c = ctx()
-    rng = random.Random(64150)
-    seen = []
-    c.set_walk_skip(L.WALK_SKIP_DIAG)
-    try:
-        for n in SHORT_SCAN:
-            a = _cases.rand_seq(rng, n)
-            run([case(a, a)], False)
-            info, st = c.launch_info(), c.walk_skip_stats()
-            assert [r["kernel"] for r in info] == [KERNEL], info
-            seen.append((n, info[0]["units_dirfree"], st["groups_skipped"]))
-            if info[0]["units_dirfree"] > 0 and st["groups_skipped"] >= 3:
-                break
-    finally:
-        c.set_walk_skip(L.WALK_STRIPS)
-    n, df, groups = seen[-1]
-    assert df > 0 and groups >= 3, seen
-    assert all(not (d > 0 and g >= 3) for _, d, g in seen[:-1])
-    assert n > SHORT_SCAN[0], ("the scan must begin below the shortest length", seen)
-    print("  SHORT = %d (%s)" % (n, seen[-3:]))
-    return n
-
-
-def sizes():
-    s = short_length()
-    return (s, 2 * s + 21, 3000, 4700, 6000)
-
-
-def substituted(rng, a, rate):
-    return _cases.mutate(rng, a, rate, 0.0, 0.0)
-
 
 def child_gap_free():
     """1. identical pairs and pairs with substitutions only: no strip at all with the property on"""
@@ -154,15 +50,6 @@ def child_gap_free():
         # every row of the direction-free range is jumped over: all rows but the ramp, the top blocks and a tagged block in front
         assert st1["rows_skipped"] >= 2 * (n - 400), (st1, n)
         both(cases, True, want)
-
-
-def one_indel(rng, n, row, kind):
-    a = _cases.rand_seq(rng, n)
-    if kind == "ins":     # a base only b has
-        b = a[:row] + {"A": "C", "C": "G", "G": "T", "T": "A"}[a[row]] + a[row:]
-    else:                 # a base only a has
-        b = a[:row] + a[row + 1:]
-    return case(a, b)
 
 
 def child_one_indel():
@@ -219,10 +106,10 @@ def child_tie_rich():
     assert len(cases) >= 40 and {cs["tag"][0] for cs in cases} >= {"homopolymer", "ac_shift1", "tandem19", "complement"}
     want = TW.wants("long", BAND)
     want = [w for cs, w in zip(TW.long_cases(BAND), want) if b"N" not in cs["a"] + cs["b"]]
-    _, info0, info1, st0, st1 = both(cases, False, want, only_octo=False)
+    _, info0, info1, st0, st1 = both(cases, False, want, only=False)
     assert sum(r["tasks"] for r in info1 if r["kernel"] == KERNEL) >= 40, info1
     assert st1["groups_skipped"] > 0 and st1["groups_tested"] > st1["groups_skipped"], st1
-    both(cases, True, want, only_octo=False)
+    both(cases, True, want, only=False)
 
 
 def displaced(rng, y, n, begin_a, rate=0.02):
@@ -279,9 +166,9 @@ def child_clamps():
         b = substituted(rng, a, 0.01)
         cases.append(case(a, b, fs=fs, fe=fe))
         cases.append(case(a, b, begin_a=40, end_a=len(a) - 70, begin_b=35, end_b=len(b) - 90, fs=fs, fe=fe))
-    _, info0, info1, st0, st1 = both(cases, False, only_octo=False)
+    _, info0, info1, st0, st1 = both(cases, False, only=False)
     assert st1["groups_skipped"] > 0, st1
-    both(cases, True, only_octo=False)
+    both(cases, True, only=False)
     # views: the o19 cell of tests/_views.py (all 16 view kinds, two 20 kb pairs), view call and copy call, both modes
     import _views as V
     import test_gpu_views as TV
@@ -328,7 +215,7 @@ def child_mixed_units():
         b = list(_cases.mutate(rng, a, 0.01, 0.001, 0.001))
         b[len(b) // 2] = "N"
         ncases.append(case(a, "".join(b)))
-    _, info0, info1, st0m, st1m = both(cases + ncases, False, only_octo=False)
+    _, info0, info1, st0m, st1m = both(cases + ncases, False, only=False)
     for info in (info0, info1):
         assert sorted((r["n_aware"], r["tasks"]) for r in info) == [(0, len(cases)), (1, len(ncases))], info
         assert [r["kernel"] for r in info if not r["n_aware"]] == [KERNEL], info
@@ -423,18 +310,8 @@ CHILDREN = {f.__name__[len("child_"):]: f for f in (child_gap_free, child_one_in
 
 # ---- the tests: one fresh child each (never exec) --------------------------------------------------------------------------------
 
-def run_child(name, diag=False, extra=None, timeout=600):
-    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-            "import test_gpu_walk_skip as T\nT.CHILDREN[%r]()\nprint('CHILD_OK')\n") % (ROOT, HERE, name)
-    env = {k: v for k, v in os.environ.items() if k not in SWITCHES and not k.startswith("GAMDP_DIAG_")}
-    env["GAMDP_QUAD_MIN"] = "1"
-    if diag:
-        env["GAMDP_LIB"] = DIAG_LIB
-    env.update(extra or {})
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=timeout)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0 and "CHILD_OK" in r.stdout, (name, diag, r.stdout[-3000:] + r.stderr[-3000:])
-    return r.stdout
+def run_child(name, diag=False, extra=None):
+    return W.run_child("test_gpu_walk_skip", name, FAMILY, diag, extra)
 
 
 LIBS = pytest.mark.parametrize("diag", (False, True), ids=("product", "diag"))

@@ -5,7 +5,7 @@ include/gamdp.h and, as ten lines of Python, in tests/_backoffmodel.py).
 Every case runs on ONE context in three settings -- STRIPS, DIAG, DIAG + backoff: every field of every result equals the oracle's, and
 the three runs are equal field by field (edit strings where asked for).  What the walks did is read from the family's
 gamdp_ctx_walk_skip*_stats and from gamdp_ctx_walk_skip_backoff_stats.  The kernel families, each reached as its own test file reaches
-it (the helpers of those files are used as they are):
+it (the families and helpers of tests/_walkskip.py):
 
     o19       k_align_o<19,15>         band 150, GAMDP_QUAD_MIN=1                      test_gpu_walk_skip
     p17_one   k_align_p<17,4>          band 512, one task after the other              test_gpu_walk_skip_pair, GAMDP_SIDE_WALK_ROUNDS=0
@@ -16,11 +16,8 @@ it (the helpers of those files are used as they are):
 
 The cases run in fresh child processes (never exec), each with a timeout of its own.  The cap of the schedule is not known here: the
 expected counts come from tests/_backoffmodel.py driven by the library's own gamdp_walk_skip_backoff_hold."""
-import importlib
 import os
 import random
-import subprocess
-import sys
 
 import pytest
 
@@ -28,26 +25,16 @@ import _backoffmodel as M
 import _cases
 import _oracle as O
 import _piecewise as P
+import _walkskip as W
 import gam_ngs_amd as gam
+from _walkskip import F, setup
 from gam_ngs_amd import lib as L
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-DIAG_LIB = os.path.join(ROOT, "gam_ngs_amd", "libgamdp_diag.so")
-# family -> (module whose helpers reach the kernel, its cell, environment, the family's skip property, its field of the backoff stats, copies)
-FAMILIES = {
-    "o19":      ("test_gpu_walk_skip", None, {"GAMDP_QUAD_MIN": "1"}, "walk_skip", "held", 16),
-    "p17_one":  ("test_gpu_walk_skip_pair", None, {"GAMDP_SIDE_WALK_ROUNDS": "0"}, "walk_skip_pair", "held_pair", 8),
-    "p17_side": ("test_gpu_walk_skip_pair", None, {"GAMDP_SIDE_WALK_ROUNDS": "1000000"}, "walk_skip_pair", "held_pair", 8),
-    "q19":      ("test_gpu_walk_skip_i32", "q19", {"GAMDP_NO_PAIR": "1", "GAMDP_QUAD_MIN": "1"}, "walk_skip_i32", "held_i32", 8),
-    "gen9":     ("test_gpu_walk_skip_i32", "gen9", {}, "walk_skip_i32", "held_i32", 8),
-    "c17n":     ("test_gpu_walk_skip_i32", "c17n", {}, "walk_skip_i32", "held_i32", 8),
-}
-SWITCHES = ("GAMDP_QUAD_MIN", "GAMDP_NO_PAIR", "GAMDP_NO_MERGE_N", "GAMDP_WALK_SKIP", "GAMDP_WALK_SKIP_PAIR", "GAMDP_WALK_SKIP_I32",
-            "GAMDP_WALK_SKIP_BACKOFF", "GAMDP_LIB", "GAMDP_SIDE_WALK_ROUNDS", "GAMDP_NO_PACKED_TOP", "GAMDP_NO_PACKED_TOP_MIXED",
-            "GAMDP_OCTO_MIN_ROWS", "GAMDP_NO_AUX_LAUNCH")
+# family of tests/_walkskip.py -> copies of the all-fail pair in its batch
+COPIES = {"o19": 16, "p17_one": 8, "p17_side": 8, "q19": 8, "gen9": 8, "c17n": 8}
+FAMILIES = {name: W.FAMILIES[name] for name in COPIES}
 COUNTERS = ("tests", "groups_tested", "groups_skipped", "rows_skipped", "strips")
 SETTINGS = ((L.WALK_STRIPS, L.WALK_BACKOFF_OFF), (L.WALK_SKIP_DIAG, L.WALK_BACKOFF_OFF), (L.WALK_SKIP_DIAG, L.WALK_BACKOFF_ON))
 ALL_FAIL_LEN = 11000     # at 32 groups a strip call (16 in the int32 kernels) a walk asks for 5 strips or more
@@ -56,21 +43,6 @@ PIECEWISE_LEN = 9000
 
 # ---- in the child ------------------------------------------------------------------------------------------------------------------
 
-class F:                 # the family this child is about (setup())
-    name = T = prop = held = kernel = None
-    copies = 0
-
-
-def setup(name):
-    mod, cell, _, F.prop, F.held, F.copies = FAMILIES[name]
-    F.name, F.T = name, importlib.import_module(mod)
-    if cell:
-        F.T.setup(cell)
-        F.kernel = F.T.K.kernel
-    else:
-        F.kernel = F.T.KERNEL
-
-
 def hold_of(f):
     return L.load_library().gamdp_walk_skip_backoff_hold(f)
 
@@ -78,39 +50,34 @@ def hold_of(f):
 def three(cases, want_ops=False, want=None):
     """The batch in the three SETTINGS on the family's context.  Every result equals the oracle's and the other settings'.
     -> (oracle answers, [(family stats, backoff stats, launch info)] per setting)"""
-    c = F.T.ctx()
-    want = want or F.T.oracle_all(cases)
+    c = W.ctx()
+    want = want or W.oracle_all(cases)
     flags = list(want_ops) if isinstance(want_ops, (list, tuple)) else [bool(want_ops)] * len(cases)
-    setter, getter = getattr(c, "set_" + F.prop), getattr(c, F.prop + "_stats")
     seen, results = [], []
     for skip, backoff in SETTINGS:
-        setter(skip)
+        F.set(c, skip)
         c.set_walk_skip_backoff(backoff)
         try:
-            res = F.T.run(cases, want_ops)
+            res = W.run(cases, want_ops)
         finally:
-            setter(L.WALK_STRIPS)
+            F.set(c, L.WALK_STRIPS)
             c.set_walk_skip_backoff(L.WALK_BACKOFF_OFF)
-        st, bo, info = getter(), c.walk_skip_backoff_stats(), c.launch_info()
+        st, bo, info = F.stats(c), c.walk_skip_backoff_stats(), c.launch_info()
         assert st["mode"] == skip and bo["mode"] == backoff, (st, bo)
         assert F.kernel in {r["kernel"] for r in info}, (F.kernel, info)
         if F.prop == "walk_skip_pair":
-            F.T.check_path(st, info)         # the walk path this child's environment asks for
-        assert st["strips"] == sum(r["strips"] for r in info if r["kernel"] == F.kernel or F.prop == "walk_skip_i32" and r["kernel"] in F.T.SIX)
+            W.check_path(st, info)           # the walk path this child's environment asks for
+        assert st["strips"] == W.family_strips(info)
         assert all(v == 0 for k, v in bo.items() if k not in ("mode", F.held)), bo
         if backoff == L.WALK_BACKOFF_OFF:
             assert bo[F.held] == 0, bo
         if skip == L.WALK_STRIPS:
             assert st["tests"] == st["groups_tested"] == st["groups_skipped"] == st["rows_skipped"] == 0, st
-        for k, (cs, r, (o, ops), f) in enumerate(zip(cases, res, want, flags)):
-            assert r.status != L.ST_DIAG_RANGE, (k, "a packed value left the exact range")
-            assert r.key() == o.key(), (F.name, skip, backoff, k, len(cs["a"]), len(cs["b"]), r.key(), o.key())
-            assert r.ops == (ops if f else None), (F.name, skip, backoff, k, "edit string")
+        W.check_results(cases, res, want, flags, (skip, backoff))
         seen.append((st, bo, info))
         results.append(res)
     for other in results[1:]:
-        for k, (r0, r1) in enumerate(zip(results[0], other)):
-            assert r0.key() == r1.key() and r0.ops == r1.ops and r0.cells == r1.cells, (k, r0.key(), r1.key())
+        W.check_equal(results[0], other)
     print("  %s %d calls: strips %s, tests %s, groups skipped %s, held %d" %
           (F.name, len(cases), [s[0]["strips"] for s in seen], [s[0]["tests"] for s in seen], [s[0]["groups_skipped"] for s in seen], seen[2][1][F.held]))
     return want, seen
@@ -119,15 +86,11 @@ def three(cases, want_ops=False, want=None):
 def child_gap_free():
     """1. the shapes on which the family's own test asserts strips == 0: nothing is held, and backoff changes no counter"""
     rng = random.Random(1)
-    fit = getattr(F.T, "fit", lambda n: n)
-    for n in F.T.sizes():
-        a = _cases.rand_seq(rng, fit(n))
-        if F.prop == "walk_skip_i32":
-            cases = [F.T.case(a, a, same=True), F.T.case(a, F.T.substituted(rng, a, 0.02))]
-        else:
-            cases = [F.T.case(a, a), F.T.case(a, F.T.substituted(rng, a, 0.02))]
-        want = F.T.oracle_all(cases)
-        assert all(o.status == O.OK and F.T.gap_free(ops) for o, ops in want)
+    for n in W.sizes():
+        a = _cases.rand_seq(rng, W.fit(n))
+        cases = [W.case(a, a, same=True), W.case(a, W.substituted(rng, a, 0.02))]
+        want = W.oracle_all(cases)
+        assert all(o.status == O.OK and W.gap_free(ops) for o, ops in want)
         for want_ops in (False, True):
             _, ((st0, _, _), (st1, bo1, _), (st2, bo2, _)) = three(cases, want_ops, want)
             assert bo2[F.held] == 0, bo2
@@ -170,15 +133,15 @@ def child_all_fail():
     are those of the model"""
     rng = random.Random(2)
     a, b = all_fail_pair(rng, ALL_FAIL_LEN)
-    cs = F.T.case(a, b)
-    (o, ops), = F.T.oracle_all([cs])
+    cs = W.case(a, b)
+    (o, ops), = W.oracle_all([cs])
     runs = diagonal_runs(ops)
     # on the CPU: no 64 consecutive diagonal steps anywhere on the path, so every 64-row window of it holds a gap -- the span below the
     # end cell (1 .. 64 rows, down to the next stored row) is the only one that can pass
     assert o.status == O.OK and o.length >= ALL_FAIL_LEN - 200 and max(runs) < 64 and len(runs) > ALL_FAIL_LEN // 50, (o.length, max(runs), len(runs))
-    cases, want = [cs] * F.copies, [(o, ops)] * F.copies
+    n = COPIES[F.name]
+    cases, want = [cs] * n, [(o, ops)] * n
     _, ((st0, _, _), (st1, bo1, _), (st2, bo2, _)) = three(cases, False, want)
-    n = F.copies
     assert st1["strips"] >= 4 * n, st1
     assert st1["strips"] == st2["strips"] and st1["groups_skipped"] == st2["groups_skipped"], (st1, st2)
     held = bo2[F.held]
@@ -199,8 +162,8 @@ def child_piecewise():
     """3. pairs whose divergence changes along the pair (tests/_piecewise.py), both orders: backoff still skips, never more than the
     plain test does, and asks for no more strips than a walk without the test"""
     for reverse in (False, True):
-        cases = [F.T.case(*P.pair(100 + k, PIECEWISE_LEN, reverse=reverse)) for k in range(4)]
-        want = F.T.oracle_all(cases)
+        cases = [W.case(*P.pair(100 + k, PIECEWISE_LEN, reverse=reverse)) for k in range(4)]
+        want = W.oracle_all(cases)
         assert all(o.status == O.OK and 10 * o.length >= 9 * PIECEWISE_LEN for o, _ in want), [o.length for o, _ in want]
         _, ((st0, _, _), (st1, _, _), (st2, bo2, _)) = three(cases, False, want)
         assert st2["groups_skipped"] > 0, st2
@@ -219,7 +182,7 @@ def child_properties():
     st = L.WalkSkipBackoffStats()
     assert l.gamdp_ctx_set_walk_skip_backoff(None, L.WALK_BACKOFF_OFF) == L.EINVAL and l.gamdp_ctx_set_walk_skip_backoff(None, L.WALK_BACKOFF_ON) == L.EINVAL
     assert l.gamdp_ctx_walk_skip_backoff_stats(None, ctypes.byref(st)) == L.EINVAL
-    c = F.T.ctx()
+    c = W.ctx()
     assert l.gamdp_ctx_walk_skip_backoff_stats(c.handle, None) == L.EINVAL
     for mode in (-1, 2, 7):
         assert l.gamdp_ctx_set_walk_skip_backoff(c.handle, mode) == L.EINVAL
@@ -230,11 +193,11 @@ def child_properties():
     want_mode = L.WALK_BACKOFF_ON if os.environ.get("GAMDP_WALK_SKIP_BACKOFF") == "1" else L.WALK_BACKOFF_OFF
     rng = random.Random(4)
     a, b = all_fail_pair(rng, ALL_FAIL_LEN)
-    fail8 = [F.T.case(a, b)] * 8
-    want8 = F.T.oracle_all(fail8[:1]) * 8
+    fail8 = [W.case(a, b)] * 8
+    want8 = W.oracle_all(fail8[:1]) * 8
     c.set_walk_skip(L.WALK_SKIP_DIAG)
     try:
-        res = F.T.run(fail8, False)
+        res = W.run(fail8, False)
     finally:
         c.set_walk_skip(L.WALK_STRIPS)
     bo = c.walk_skip_backoff_stats()
@@ -249,13 +212,13 @@ def child_properties():
     xn = x[:2500] + "N" + x[2501:]
     mk = lambda p, q, band: dict(a=p.encode(), b=q.encode(), band=band, begin_a=0, end_a=len(p) - 1, begin_b=0, end_b=len(q) - 1, fs=False, fe=False)
     mixed = fail8 + [mk(x, y, 512), mk(x, x, 512), mk(xn, y, 150), mk(x, y, 200)]
-    wantm = want8 + F.T.oracle_all(mixed[8:])
+    wantm = want8 + W.oracle_all(mixed[8:])
     timeless = lambda info: [{k: v for k, v in r.items() if "ms" not in k} for r in info]
     seen = []
     for backoff in (L.WALK_BACKOFF_OFF, L.WALK_BACKOFF_ON):
         c.set_walk_skip_backoff(backoff)
         try:
-            res = F.T.run(mixed, False)
+            res = W.run(mixed, False)
         finally:
             c.set_walk_skip_backoff(L.WALK_BACKOFF_OFF)
         assert [r.key() for r in res] == [o.key() for o, _ in wantm]
@@ -272,13 +235,13 @@ def child_properties():
     try:
         fail512 = [dict(cs, band=512) for cs in fail8[:2]]
         fail200 = [dict(cs, band=200) for cs in fail8[:1]]
-        res = F.T.run(fail8 + fail512 + fail200, False)
+        res = W.run(fail8 + fail512 + fail200, False)
         bo = c.walk_skip_backoff_stats()
     finally:
         for name in ("walk_skip", "walk_skip_pair", "walk_skip_i32"):
             getattr(c, "set_" + name)(L.WALK_STRIPS)
         c.set_walk_skip_backoff(L.WALK_BACKOFF_OFF)
-    assert [r.key() for r in res] == [o.key() for o, _ in want8 + F.T.oracle_all(fail512 + fail200)]
+    assert [r.key() for r in res] == [o.key() for o, _ in want8 + W.oracle_all(fail512 + fail200)]
     assert bo["held"] > 0 and bo["held_pair"] > 0 and bo["held_i32"] > 0 and bo["mode"] == 1, bo
     # gamdp_multi: two contexts on one device, both with the test, one of them with backoff
     seqs = []
@@ -321,19 +284,8 @@ CHILDREN = {f.__name__[len("child_"):]: f for f in (child_gap_free, child_all_fa
 
 # ---- the tests: one fresh child each (never exec) --------------------------------------------------------------------------------
 
-def run_child(name, family=None, diag=False, extra=None, timeout=300):
-    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-            "import test_gpu_walk_skip_backoff as B\nif %r: B.setup(%r)\nB.CHILDREN[%r]()\nprint('CHILD_OK')\n") % (ROOT, HERE, family, family, name)
-    env = {k: v for k, v in os.environ.items() if k not in SWITCHES and not k.startswith("GAMDP_DIAG_")}
-    if family:
-        env.update(FAMILIES[family][2])
-    if diag:
-        env["GAMDP_LIB"] = DIAG_LIB
-    env.update(extra or {})
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=timeout)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0 and "CHILD_OK" in r.stdout, (name, family, diag, r.stdout[-3000:] + r.stderr[-3000:])
-    return r.stdout
+def run_child(name, family=None, diag=False, extra=None):
+    return W.run_child("test_gpu_walk_skip_backoff", name, family, diag, extra, timeout=300)
 
 
 FAMS = pytest.mark.parametrize("family", sorted(FAMILIES))

@@ -27,62 +27,28 @@ value for its first span and takes one strip there (16 groups) before it tests a
 its upper value, so a walk whose end cell lies inside the range needs no strip at all.  "Gap-free pairs need no strip" is that second
 statement, so the lengths of the cases that assert it are rounded up by fit(): rows + LE a multiple of 64 (LE = the lane of the
 band's last column), which makes the task's last block the last block of a group -- the whole END run lies in the range."""
-import functools
 import os
 import random
-import subprocess
-import sys
 
 import pytest
 
 import _cases
 import _oracle as O
+import _walkskip as W
 import gam_ngs_amd as gam
+from _walkskip import (SIX, both, case, check_stats, ctx, fit, gap_free, mine, one_indel, oracle_all, run, setup, short_length, sizes, substituted,
+                       trimmed)
+from _walkskip import F as K     # the kernel this child is about (setup()): cell, kernel, band, C, lpt, need_n, LE, lc
 from gam_ngs_amd import lib as L
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-DIAG_LIB = os.path.join(ROOT, "gam_ngs_amd", "libgamdp_diag.so")
-# cell of tests/_views.py -> (kernel, band, columns per lane, lanes per task, N: False never / True needed / None either, environment)
-KERNELS = {
-    "c17":   ("k_align<17,4,false>", 512, 17, 64, False, {"GAMDP_NO_PAIR": "1"}),
-    "c17n":  ("k_align<17,4,true>", 512, 17, 64, True, {}),
-    "q19":   ("k_align_q<19,15,false>", 150, 19, 16, False, {"GAMDP_NO_PAIR": "1", "GAMDP_QUAD_MIN": "1"}),
-    "q19n":  ("k_align_q<19,15,true>", 150, 19, 16, True, {"GAMDP_QUAD_MIN": "1"}),
-    "gen9":  ("k_align<9,-1,true>", 200, 9, 64, None, {}),
-    "gen17": ("k_align<17,-1,true>", 300, 17, 64, None, {}),
-}
-SIX = {k[0] for k in KERNELS.values()}
-SWITCHES = ("GAMDP_QUAD_MIN", "GAMDP_NO_PAIR", "GAMDP_NO_MERGE_N", "GAMDP_WALK_SKIP", "GAMDP_WALK_SKIP_PAIR", "GAMDP_WALK_SKIP_I32", "GAMDP_LIB",
-            "GAMDP_SIDE_WALK_ROUNDS", "GAMDP_NO_PACKED_TOP", "GAMDP_NO_PACKED_TOP_MIXED", "GAMDP_OCTO_MIN_ROWS", "GAMDP_NO_AUX_LAUNCH")
+KERNELS = {cell: W.FAMILIES[cell] for cell in W.I32}    # the families of tests/_walkskip.py that are named after their cell of tests/_views.py
 ZERO = dict(tests=0, groups_tested=0, groups_skipped=0, rows_skipped=0, strips=0, mode=0, launches=0)
 STRIP_GROUPS = 16        # groups one strip call re-creates in these kernels (strips of 4 lanes: kernel_fill.inc Strip::groups_of)
 
 
 # ---- in the child ------------------------------------------------------------------------------------------------------------------
-
-class K:                 # the kernel this child is about (setup())
-    cell = kernel = band = C = lpt = need_n = None
-    LE = lc = 0          # the lanes (within the task) of the band's last and of its centre column
-
-
-def setup(cell):
-    K.cell = cell
-    K.kernel, K.band, K.C, K.lpt, K.need_n, _ = KERNELS[cell]
-    K.LE, K.lc = 2 * K.band // K.C, K.band // K.C
-
-
-@functools.lru_cache(maxsize=1)
-def ctx():
-    return gam.Context(0)
-
-
-def fit(n):
-    """the shortest length >= n whose last block is the last block of a group (module docstring)"""
-    return n + (-(n + K.LE)) % 64
-
 
 def range_rows(n):
     """rows of an identical pair of length n = fit(n) between the first row-time of the direction-free range and the end cell
@@ -92,129 +58,14 @@ def range_rows(n):
     return (n - 1 + K.lc) - 16 * lo + 1
 
 
-def route(a, b, same=False):
-    """the pair as the kernel under test takes it: an N for the two kernels that only N-holding calls reach"""
-    if K.need_n and "N" not in a + b:
-        a = a[:5] + "N" + a[6:]
-        if same:
-            b = a
-    assert not (K.need_n is False and "N" in a + b)
-    return a, b
-
-
-def case(a, b, begin_a=0, end_a=None, begin_b=0, end_b=None, fs=False, fe=False, same=False):
-    a, b = route(a, b, same)
-    return dict(a=a.encode(), b=b.encode(), band=K.band, begin_a=begin_a, end_a=len(a) - 1 if end_a is None else end_a, begin_b=begin_b,
-                end_b=len(b) - 1 if end_b is None else end_b, fs=fs, fe=fe)
-
-
 def takes(cs):
     """whether the kernel under test takes this call by its bases (a window without N inside an N-holding pair: the launch record tells)"""
     has_n = b"N" in cs["a"] + cs["b"]
     return K.need_n is None or K.need_n == has_n
 
 
-def run(cases, want_ops):
-    import _gpu
-    _gpu.ctx = ctx          # (run_cases on this module's context)
-    return _gpu.run_cases(cases, want_ops=want_ops)
-
-
-def oracle_all(cases):
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(16) as ex:   # (the oracle's C code runs outside the GIL)
-        return list(ex.map(lambda cs: O.oracle_align(O.encode(cs["a"]), O.encode(cs["b"]), cs["band"], cs["begin_a"], cs["end_a"], cs["begin_b"],
-                                                     cs["end_b"], cs["fs"], cs["fe"], want_ops=True), cases))
-
-
-def mine(info):
-    return [r for r in info if r["kernel"] == K.kernel]
-
-
 def six_strips(info):
     return sum(r["strips"] for r in info if r["kernel"] in SIX)
-
-
-def check_stats(st, info, mode):
-    """the invariants of every case"""
-    assert st["mode"] == mode and st["launches"] == sum(1 for r in info if r["kernel"] in SIX) > 0, (st, info)
-    assert st["strips"] == six_strips(info), (st, info)
-    assert st["groups_skipped"] <= st["groups_tested"] <= 64 * st["tests"], st
-    assert 64 * st["groups_skipped"] - 63 * st["tests"] <= st["rows_skipped"] <= 64 * st["groups_skipped"], st
-    if mode == L.WALK_STRIPS:
-        assert st["tests"] == st["groups_tested"] == st["groups_skipped"] == st["rows_skipped"] == 0, st
-
-
-def both(cases, want_ops=False, want=None, only=True):
-    """The batch with the property off, then on, on one context.  Every result equals the oracle's and the other mode's.
-    -> (oracle answers, launch info off, launch info on, stats off, stats on)"""
-    c = ctx()
-    want = want or oracle_all(cases)
-    flags = list(want_ops) if isinstance(want_ops, (list, tuple)) else [bool(want_ops)] * len(cases)
-    out = {}
-    for mode in (L.WALK_STRIPS, L.WALK_SKIP_DIAG):
-        c.set_walk_skip_i32(mode)
-        try:
-            res = run(cases, want_ops)
-        finally:
-            c.set_walk_skip_i32(L.WALK_STRIPS)
-        info, st = c.launch_info(), c.walk_skip_i32_stats()
-        assert mine(info), (K.kernel, info)
-        if only:
-            assert {r["kernel"] for r in info} == {K.kernel}, info
-        check_stats(st, info, mode)
-        for k, (cs, r, (o, ops), f) in enumerate(zip(cases, res, want, flags)):
-            assert r.status != L.ST_DIAG_RANGE, (k, "a packed value left the exact range")
-            assert r.key() == o.key(), (K.cell, mode, k, len(cs["a"]), len(cs["b"]), r.key(), o.key())
-            assert r.ops == (ops if f else None), (K.cell, mode, k, "edit string")
-        out[mode] = (res, info, st)
-    for k, (r0, r1) in enumerate(zip(out[0][0], out[1][0])):
-        assert r0.key() == r1.key() and r0.ops == r1.ops and r0.cells == r1.cells, (k, r0.key(), r1.key())
-    st0, st1 = out[0][2], out[1][2]
-    print("  %s %d calls: strips off %d on %d, tests %d, groups tested %d skipped %d, rows skipped %d" %
-          (K.cell, len(cases), st0["strips"], st1["strips"], st1["tests"], st1["groups_tested"], st1["groups_skipped"], st1["rows_skipped"]))
-    return want, out[0][1], out[1][1], st0, st1
-
-
-def gap_free(ops):
-    return set(ops) <= {"M", "X"}
-
-
-@functools.lru_cache(maxsize=1)
-def short_length():
-    """The shortest length of the scan at which an identical pair has a direction-free range of 3 groups or more: with the property on
-    an identical pair's walk jumps over every group of the range below its end cell, so groups_skipped counts them."""
-    c = ctx()
-    rng = random.Random(64512)
-    scan = range(fit(192), 2049, 64)
-    seen = []
-    c.set_walk_skip_i32(L.WALK_SKIP_DIAG)
-    try:
-        for n in scan:
-            a = _cases.rand_seq(rng, n)
-            run([case(a, a, same=True)], False)
-            info, st = c.launch_info(), c.walk_skip_i32_stats()
-            assert [r["kernel"] for r in info] == [K.kernel], info
-            seen.append((n, info[0]["units_dirfree"], st["groups_skipped"]))
-            if info[0]["units_dirfree"] > 0 and st["groups_skipped"] >= 3:
-                break
-    finally:
-        c.set_walk_skip_i32(L.WALK_STRIPS)
-    n, df, groups = seen[-1]
-    assert df > 0 and groups >= 3, seen
-    assert all(not (d > 0 and g >= 3) for _, d, g in seen[:-1])
-    assert n > scan[0], ("the scan must begin below the shortest length", seen)
-    print("  %s SHORT = %d (%s)" % (K.cell, n, seen[-3:]))
-    return n
-
-
-def sizes():
-    s = short_length()
-    return (s, fit(2 * s + 21), fit(3000), fit(4700), fit(6000))
-
-
-def substituted(rng, a, rate):
-    return _cases.mutate(rng, a, rate, 0.0, 0.0)
 
 
 def sprinkled(a, b, every=37):
@@ -230,13 +81,6 @@ def sprinkled(a, b, every=37):
         kinds.add(k % 3)
     assert kinds == {0, 1, 2}
     return "".join(a), "".join(b)
-
-
-def trimmed(a, b):
-    """the pair without the last few bases of both (an unchanged stretch): rows + LE a multiple of 64, as fit() makes it for equal lengths"""
-    t = (len(b) + K.LE) % 64
-    assert len(b) - t <= len(a) - t + K.band
-    return a[:len(a) - t], b[:len(b) - t]
 
 
 def child_gap_free():
@@ -259,15 +103,6 @@ def child_gap_free():
         # every row of the direction-free range below the end cells is jumped over
         assert st1["rows_skipped"] >= len(cases) * range_rows(n), (st1, n, range_rows(n))
         both(cases, True, want)
-
-
-def one_indel(rng, n, row, kind):
-    a = _cases.rand_seq(rng, n)
-    if kind == "ins":     # a base only b has
-        b = a[:row] + {"A": "C", "C": "G", "G": "T", "T": "A"}[a[row]] + a[row:]
-    else:                 # a base only a has
-        b = a[:row] + a[row + 1:]
-    return case(*trimmed(a, b))
 
 
 def child_one_indel():
@@ -584,19 +419,8 @@ CHILDREN = {f.__name__[len("child_"):]: f for f in (child_gap_free, child_one_in
 
 # ---- the tests: one fresh child each (never exec) --------------------------------------------------------------------------------
 
-def run_child(name, cell=None, diag=False, extra=None, timeout=600):
-    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-            "import test_gpu_walk_skip_i32 as T\nif %r: T.setup(%r)\nT.CHILDREN[%r]()\nprint('CHILD_OK')\n") % (ROOT, HERE, cell, cell, name)
-    env = {k: v for k, v in os.environ.items() if k not in SWITCHES and not k.startswith("GAMDP_DIAG_")}
-    if cell:
-        env.update(KERNELS[cell][5])
-    if diag:
-        env["GAMDP_LIB"] = DIAG_LIB
-    env.update(extra or {})
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=timeout)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0 and "CHILD_OK" in r.stdout, (name, cell, diag, r.stdout[-3000:] + r.stderr[-3000:])
-    return r.stdout
+def run_child(name, cell=None, diag=False, extra=None):
+    return W.run_child("test_gpu_walk_skip_i32", name, cell, diag, extra)
 
 
 CELLS = pytest.mark.parametrize("cell", sorted(KERNELS))

@@ -12,145 +12,30 @@ is asserted from launches_one_by_one / launches_side_by_side -- on the product l
 Sizes: SHORT is the shortest length (scanning upward in steps of 64 bases, identical pair, whole sequences) at which the
 direction-free range holds at least 3 groups -- found on the device by the child itself and asserted -- and the cases use SHORT, about
 twice SHORT and pairs of 3 - 6 kb."""
-import functools
 import os
 import random
-import subprocess
-import sys
 
 import pytest
 
 import _cases
 import _oracle as O
+import _walkskip as W
 import gam_ngs_amd as gam
+from _walkskip import both, case, check_path, ctx, gap_free, one_indel, oracle_all, run, short_length, sizes, substituted
 from gam_ngs_amd import lib as L
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-DIAG_LIB = os.path.join(ROOT, "gam_ngs_amd", "libgamdp_diag.so")
+FAMILIES = ("p17_one", "p17_side")   # of tests/_walkskip.py: GAMDP_SIDE_WALK_ROUNDS=0 and =1000000, every child runs as both in turn
 BAND, C = 512, 17
-KERNEL = "k_align_p<17,4>"
-SWITCHES = ("GAMDP_QUAD_MIN", "GAMDP_NO_PAIR", "GAMDP_NO_MERGE_N", "GAMDP_WALK_SKIP", "GAMDP_WALK_SKIP_PAIR", "GAMDP_LIB", "GAMDP_SIDE_WALK_ROUNDS",
-            "GAMDP_NO_PACKED_TOP", "GAMDP_NO_PACKED_TOP_MIXED")
-SHORT_SCAN = range(192, 1601, 64)   # where SHORT is looked for: the range begins with block 8 (behind the ramp of 61 lanes)
+KERNEL = W.P17
 ZERO = dict(tests=0, groups_tested=0, groups_skipped=0, rows_skipped=0, strips=0, mode=0, launches_side_by_side=0, launches_one_by_one=0)
 
 
 # ---- in the child ------------------------------------------------------------------------------------------------------------------
 
-@functools.lru_cache(maxsize=1)
-def ctx():
-    return gam.Context(0)
-
-
-def side_by_side():
-    return int(os.environ["GAMDP_SIDE_WALK_ROUNDS"]) > 0
-
-
-def case(a, b, begin_a=0, end_a=None, begin_b=0, end_b=None, fs=False, fe=False):
-    return dict(a=a.encode(), b=b.encode(), band=BAND, begin_a=begin_a, end_a=len(a) - 1 if end_a is None else end_a, begin_b=begin_b,
-                end_b=len(b) - 1 if end_b is None else end_b, fs=fs, fe=fe)
-
-
-def run(cases, want_ops):
-    import _gpu
-    _gpu.ctx = ctx          # (run_cases on this module's context)
-    return _gpu.run_cases(cases, want_ops=want_ops)
-
-
-def oracle_all(cases):
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(16) as ex:   # (the oracle's C code runs outside the GIL)
-        return list(ex.map(lambda cs: O.oracle_align(O.encode(cs["a"]), O.encode(cs["b"]), cs["band"], cs["begin_a"], cs["end_a"], cs["begin_b"],
-                                                     cs["end_b"], cs["fs"], cs["fe"], want_ops=True), cases))
-
-
 def pair_strips(info):
     return sum(r["strips"] for r in info if r["kernel"] == KERNEL)
-
-
-def check_path(st, info):
-    """the walk path of the call's two-task launches is the one this child's environment asks for"""
-    n = sum(1 for r in info if r["kernel"] == KERNEL)
-    assert n > 0, info
-    assert (st["launches_side_by_side"], st["launches_one_by_one"]) == ((n, 0) if side_by_side() else (0, n)), (st, info)
-
-
-def both(cases, want_ops=False, want=None, only_pair=True):
-    """The batch with the property off, then on, on one context.  Every result equals the oracle's and the other mode's.
-    -> (oracle answers, launch info off, launch info on, stats off, stats on)"""
-    c = ctx()
-    want = want or oracle_all(cases)
-    flags = list(want_ops) if isinstance(want_ops, (list, tuple)) else [bool(want_ops)] * len(cases)
-    out = {}
-    for mode in (L.WALK_STRIPS, L.WALK_SKIP_DIAG):
-        c.set_walk_skip_pair(mode)
-        try:
-            res = run(cases, want_ops)
-        finally:
-            c.set_walk_skip_pair(L.WALK_STRIPS)
-        info, st = c.launch_info(), c.walk_skip_pair_stats()
-        assert st["mode"] == mode, st
-        check_path(st, info)
-        if only_pair:
-            assert {r["kernel"] for r in info} == {KERNEL}, info
-        for k, (cs, r, (o, ops), f) in enumerate(zip(cases, res, want, flags)):
-            assert r.status != L.ST_DIAG_RANGE, (k, "a packed value left the exact range")
-            assert r.key() == o.key(), (mode, k, len(cs["a"]), len(cs["b"]), r.key(), o.key())
-            assert r.ops == (ops if f else None), (mode, k, "edit string")
-        out[mode] = (res, info, st)
-    for k, (r0, r1) in enumerate(zip(out[0][0], out[1][0])):
-        assert r0.key() == r1.key() and r0.ops == r1.ops and r0.cells == r1.cells, (k, r0.key(), r1.key())
-    st0, st1 = out[0][2], out[1][2]
-    assert st0["tests"] == st0["groups_tested"] == st0["groups_skipped"] == st0["rows_skipped"] == 0, st0
-    assert st0["strips"] == pair_strips(out[0][1]) and st1["strips"] == pair_strips(out[1][1]), (st0, st1)
-    assert st1["groups_skipped"] <= st1["groups_tested"] <= (8 if side_by_side() else 64) * st1["tests"], st1
-    assert 64 * st1["groups_skipped"] - 63 * st1["tests"] <= st1["rows_skipped"] <= 64 * st1["groups_skipped"], st1
-    print("  %d calls: strips off %d on %d, tests %d, groups tested %d skipped %d, rows skipped %d" %
-          (len(cases), st0["strips"], st1["strips"], st1["tests"], st1["groups_tested"], st1["groups_skipped"], st1["rows_skipped"]))
-    return want, out[0][1], out[1][1], st0, st1
-
-
-def gap_free(ops):
-    return set(ops) <= {"M", "X"}
-
-
-@functools.lru_cache(maxsize=1)
-def short_length():
-    """The shortest length of SHORT_SCAN at which an identical pair has a direction-free range of 3 groups or more: with the property
-    on an identical pair's walk jumps over every group of the range below its end cell, so groups_skipped counts them (two tasks)."""
-    c = ctx()
-    rng = random.Random(64512)
-    seen = []
-    c.set_walk_skip_pair(L.WALK_SKIP_DIAG)
-    try:
-        for n in SHORT_SCAN:
-            a = _cases.rand_seq(rng, n)
-            run([case(a, a), case(a, a)], False)
-            info, st = c.launch_info(), c.walk_skip_pair_stats()
-            assert [r["kernel"] for r in info] == [KERNEL], info
-            seen.append((n, info[0]["units_dirfree"], st["groups_skipped"] // 2))
-            if info[0]["units_dirfree"] > 0 and st["groups_skipped"] >= 2 * 3:
-                break
-    finally:
-        c.set_walk_skip_pair(L.WALK_STRIPS)
-    n, df, groups = seen[-1]
-    assert df > 0 and groups >= 3, seen
-    assert all(not (d > 0 and g >= 3) for _, d, g in seen[:-1])
-    assert n > SHORT_SCAN[0], ("the scan must begin below the shortest length", seen)
-    print("  SHORT = %d (%s)" % (n, seen[-3:]))
-    return n
-
-
-def sizes():
-    s = short_length()
-    return (s, 2 * s + 21, 3000, 4700, 6000)
-
-
-def substituted(rng, a, rate):
-    return _cases.mutate(rng, a, rate, 0.0, 0.0)
 
 
 def child_gap_free():
@@ -171,15 +56,6 @@ def child_gap_free():
         # every row of the direction-free range is jumped over: all rows but the ramp, the first eight blocks and a partial group
         assert st1["rows_skipped"] >= 2 * (n - 300), (st1, n)
         both(cases, True, want)
-
-
-def one_indel(rng, n, row, kind):
-    a = _cases.rand_seq(rng, n)
-    if kind == "ins":     # a base only b has
-        b = a[:row] + {"A": "C", "C": "G", "G": "T", "T": "A"}[a[row]] + a[row:]
-    else:                 # a base only a has
-        b = a[:row] + a[row + 1:]
-    return case(a, b)
 
 
 def child_one_indel():
@@ -236,10 +112,10 @@ def child_tie_rich():
     assert len(cases) >= 40 and {cs["tag"][0] for cs in cases} >= {"homopolymer", "ac_shift1", "tandem19", "complement"}
     allw = TW.wants("long", BAND)
     want = [allw[k] for k in keep]
-    _, info0, info1, st0, st1 = both(cases, False, want, only_pair=False)
+    _, info0, info1, st0, st1 = both(cases, False, want, only=False)
     assert sum(r["tasks"] for r in info1 if r["kernel"] == KERNEL) >= 40, info1
     assert st1["groups_skipped"] > 0 and st1["groups_tested"] > st1["groups_skipped"], st1
-    both(cases, True, want, only_pair=False)
+    both(cases, True, want, only=False)
 
 
 def child_displaced():
@@ -280,9 +156,9 @@ def child_clamps():
         b = substituted(rng, a, 0.01)
         cases.append(case(a, b, fs=fs, fe=fe))
         cases.append(case(a, b, begin_a=40, end_a=len(a) - 70, begin_b=35, end_b=len(b) - 90, fs=fs, fe=fe))
-    _, info0, info1, st0, st1 = both(cases, False, only_pair=False)
+    _, info0, info1, st0, st1 = both(cases, False, only=False)
     assert st1["groups_skipped"] > 0, st1
-    both(cases, True, only_pair=False)
+    both(cases, True, only=False)
     # views: the p17 cell of tests/_views.py (all view kinds), view call and copy call, both modes
     import _views as V
     import test_gpu_views as TV
@@ -324,7 +200,7 @@ def child_mixed_units():
     assert st1a["tests"] == 0 and st1a["groups_skipped"] == 0, st1a
     # an odd batch: the last task goes to another kernel, and its launch record is what it was
     odd = cases[:5]
-    _, oinfo0, oinfo1, ost0, ost1 = both(odd, False, only_pair=False)
+    _, oinfo0, oinfo1, ost0, ost1 = both(odd, False, only=False)
     rest = lambda info: sorted((r["kernel"], r["tasks"], r["units"], r["strips"], r["units_dirfree"]) for r in info if r["kernel"] != KERNEL)
     assert rest(oinfo0) == rest(oinfo1), (oinfo0, oinfo1)
     assert sum(r["tasks"] for r in oinfo1) == 5 and ost1["groups_skipped"] > 0, (oinfo1, ost1)
@@ -335,7 +211,7 @@ def child_mixed_units():
         b = list(_cases.mutate(rng, a, 0.01, 0.001, 0.001))
         b[len(b) // 2] = "N"
         ncases.append(case(a, "".join(b)))
-    _, info0, info1, st0m, st1m = both(cases + ncases, False, only_pair=False)
+    _, info0, info1, st0m, st1m = both(cases + ncases, False, only=False)
     nrec = lambda info: sorted((r["kernel"], r["tasks"], r["strips"]) for r in info if r["n_aware"])
     assert nrec(info0) == nrec(info1) and sum(t for _, t, _ in nrec(info1)) == len(ncases), (info0, info1)
     assert (st1m["tests"], st1m["groups_tested"], st1m["groups_skipped"], st1m["rows_skipped"], st1m["strips"]) == \
@@ -439,21 +315,8 @@ CHILDREN = {f.__name__[len("child_"):]: f for f in (child_gap_free, child_one_in
 
 # ---- the tests: fresh children (never exec), one per walk path -------------------------------------------------------------------
 
-def run_child(name, diag=False, extra=None, rounds=("0", "1000000"), timeout=600):
-    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-            "import test_gpu_walk_skip_pair as T\nT.CHILDREN[%r]()\nprint('CHILD_OK')\n") % (ROOT, HERE, name)
-    outs = []
-    for sw in rounds:
-        env = {k: v for k, v in os.environ.items() if k not in SWITCHES and not k.startswith("GAMDP_DIAG_")}
-        env["GAMDP_SIDE_WALK_ROUNDS"] = sw
-        if diag:
-            env["GAMDP_LIB"] = DIAG_LIB
-        env.update(extra or {})
-        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=timeout)
-        print("GAMDP_SIDE_WALK_ROUNDS=%s\n%s" % (sw, r.stdout[-4000:]))
-        assert r.returncode == 0 and "CHILD_OK" in r.stdout, (name, diag, sw, r.stdout[-3000:] + r.stderr[-3000:])
-        outs.append(r.stdout)
-    return outs
+def run_child(name, diag=False, extra=None, families=FAMILIES):
+    return [W.run_child("test_gpu_walk_skip_pair", name, f, diag, extra) for f in families]
 
 
 LIBS = pytest.mark.parametrize("diag", (False, True), ids=("product", "diag"))
@@ -508,5 +371,5 @@ def test_refusals_defaults_and_two_contexts_in_different_modes():
 def test_the_environment_default():
     for out in run_child("defaults", extra={"GAMDP_WALK_SKIP_PAIR": "1", "GAMDP_WALK_SKIP_PAIR_TEST_ENV_ONLY": "1"}):
         assert "ENV_MODE 1" in out
-    for out in run_child("defaults", extra={"GAMDP_WALK_SKIP_PAIR": "0", "GAMDP_WALK_SKIP_PAIR_TEST_ENV_ONLY": "1"}, rounds=("0",)):
+    for out in run_child("defaults", extra={"GAMDP_WALK_SKIP_PAIR": "0", "GAMDP_WALK_SKIP_PAIR_TEST_ENV_ONLY": "1"}, families=FAMILIES[:1]):
         assert "ENV_MODE 0" in out
