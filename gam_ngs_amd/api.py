@@ -139,37 +139,30 @@ class Context:
         self.lib.gamdp_ctx_kernel_time(self.handle, C.byref(ms), C.byref(n), int(reset))
         return ms.value, n.value
 
+    def _launches(self, getter_name, struct):
+        """One of the context's launch logs, as dicts: its length first, then that many records."""
+        getter = getattr(self.lib, getter_name)
+        n = C.c_size_t()
+        getter(self.handle, None, 0, C.byref(n))
+        arr = (struct * max(1, n.value))()
+        getter(self.handle, arr, n.value, C.byref(n))
+        return [arr[i].as_dict() for i in range(n.value)]
+
     def launch_info(self):
         """The launches of the last gamdp_align_batch call on this context, as dicts (gamdp_ctx_launch_info)."""
-        n = C.c_size_t()
-        self.lib.gamdp_ctx_launch_info(self.handle, None, 0, C.byref(n))
-        arr = (L.LaunchInfo * max(1, n.value))()
-        self.lib.gamdp_ctx_launch_info(self.handle, arr, n.value, C.byref(n))
-        return [arr[i].as_dict() for i in range(n.value)]
+        return self._launches("gamdp_ctx_launch_info", L.LaunchInfo)
 
     def score_info(self):
         """The launches of the last gamdp_score_batch call on this context, as dicts (gamdp_ctx_score_info)."""
-        n = C.c_size_t()
-        self.lib.gamdp_ctx_score_info(self.handle, None, 0, C.byref(n))
-        arr = (L.ScoreLaunchInfo * max(1, n.value))()
-        self.lib.gamdp_ctx_score_info(self.handle, arr, n.value, C.byref(n))
-        return [arr[i].as_dict() for i in range(n.value)]
+        return self._launches("gamdp_ctx_score_info", L.ScoreLaunchInfo)
 
     def carry_info(self):
         """The launches of the last gamdp_carry_batch call on this context, as dicts (gamdp_ctx_carry_info)."""
-        n = C.c_size_t()
-        self.lib.gamdp_ctx_carry_info(self.handle, None, 0, C.byref(n))
-        arr = (L.ScoreLaunchInfo * max(1, n.value))()
-        self.lib.gamdp_ctx_carry_info(self.handle, arr, n.value, C.byref(n))
-        return [arr[i].as_dict() for i in range(n.value)]
+        return self._launches("gamdp_ctx_carry_info", L.ScoreLaunchInfo)
 
     def carry_ops_info(self):
         """The launches of the last gamdp_carry_ops_batch call on this context, as dicts (gamdp_ctx_carry_ops_info)."""
-        n = C.c_size_t()
-        self.lib.gamdp_ctx_carry_ops_info(self.handle, None, 0, C.byref(n))
-        arr = (L.ScoreLaunchInfo * max(1, n.value))()
-        self.lib.gamdp_ctx_carry_ops_info(self.handle, arr, n.value, C.byref(n))
-        return [arr[i].as_dict() for i in range(n.value)]
+        return self._launches("gamdp_ctx_carry_ops_info", L.ScoreLaunchInfo)
 
     def set_ops_chunk_bytes(self, nbytes: int):
         """The bytes of edit strings one chunk of find_alignments_with_ops_fingerprints / ops_fingerprint_many may hold on the device
@@ -494,6 +487,11 @@ def last_match_pos(aln: MyAlignment):
     return aln.last_found, aln.last_match
 
 
+def _no_ops(r):
+    """the MyAlignment of a gamdp_result that comes without an edit string"""
+    return MyAlignment.from_result(r, None)
+
+
 class BandedSmithWaterman:
     """BandedSmithWaterman(band): find_alignment for one call, find_alignments for a batch."""
 
@@ -524,64 +522,49 @@ class BandedSmithWaterman:
             t.begin_a, t.end_a, t.begin_b, t.end_b = begin_a & m64, end_a & m64, begin_b & m64, end_b & m64
         return tasks, sa, sb
 
+    def _fill_only(self, calls, bands, symbol, struct, with_fp, convert, method):
+        """What find_scores, find_results and the two *_with_ops_fingerprints share: one call of `symbol` over the batch into an array
+        of `struct` (and, with_fp, a fingerprint per call beside it) -> [convert(result)], or that and the fingerprints.  method: the
+        public method's name, for its error message."""
+        n = len(calls)
+        if n == 0:
+            return ([], []) if with_fp else []
+        if isinstance(self.ctx, MultiContext):
+            raise L.GamdpError("%s is a single-context call" % method)
+        tasks, sa, sb = self._tasks(calls, bands)
+        out = (struct * n)()
+        extra = [(C.c_uint32 * n)()] if with_fp else []
+        _check(self.ctx, getattr(self.ctx.lib, symbol)(self.ctx.handle, sa.handle, sb.handle, tasks, n, out, *extra), symbol)
+        res = [convert(r) for r in out]
+        return (res, list(extra[0])) if with_fp else res
+
     def find_scores(self, calls, bands=None):
         """Score and end cell of every call without the traceback (gamdp_score_batch: a second, int32-only kernel that uses no
         scratch arena): a list of (score, end_a, end_b, status, cells) for the calls find_alignments takes.  score, status and
         cells equal those of find_alignments; (end_a, end_b) is the cell the alignment ends in."""
-        n = len(calls)
-        if n == 0:
-            return []
-        if isinstance(self.ctx, MultiContext):
-            raise L.GamdpError("find_scores is a single-context call")
-        tasks, sa, sb = self._tasks(calls, bands)
-        out = (L.ScoreResult * n)()
-        _check(self.ctx, self.ctx.lib.gamdp_score_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out), "gamdp_score_batch")
-        return [(r.score, r.end_a, r.end_b, r.status, r.cells) for r in out]
+        return self._fill_only(calls, bands, "gamdp_score_batch", L.ScoreResult, with_fp=False, method="find_scores",
+                               convert=lambda r: (r.score, r.end_a, r.end_b, r.status, r.cells))
 
     def find_results(self, calls, bands=None) -> List[MyAlignment]:
         """Every call's whole result from a fill alone (gamdp_carry_batch: a third, int32-only kernel in which every cell carries the
         summary of the traceback that would start in it; no scratch arena, no walk): a list of MyAlignment without edit strings
         (ops None), field by field what find_alignments returns for the same calls."""
-        n = len(calls)
-        if n == 0:
-            return []
-        if isinstance(self.ctx, MultiContext):
-            raise L.GamdpError("find_results is a single-context call")
-        tasks, sa, sb = self._tasks(calls, bands)
-        out = (L.Result * n)()
-        _check(self.ctx, self.ctx.lib.gamdp_carry_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out), "gamdp_carry_batch")
-        return [MyAlignment.from_result(r, None) for r in out]
+        return self._fill_only(calls, bands, "gamdp_carry_batch", L.Result, with_fp=False, convert=_no_ops, method="find_results")
 
     def find_results_with_ops_fingerprints(self, calls, bands=None):
         """find_results with the fingerprint of every call's edit string (gamdp_carry_ops_batch: the carry kernel with the
         fingerprint as a sixth field of a cell's summary): (results, fingerprints).  fingerprints[i] equals
         ops_fingerprint(find_alignments(calls, want_ops=True)[i].ops) for a call whose status is OK and is 0 otherwise."""
-        n = len(calls)
-        if n == 0:
-            return [], []
-        if isinstance(self.ctx, MultiContext):
-            raise L.GamdpError("find_results_with_ops_fingerprints is a single-context call")
-        tasks, sa, sb = self._tasks(calls, bands)
-        out = (L.Result * n)()
-        fp = (C.c_uint32 * n)()
-        _check(self.ctx, self.ctx.lib.gamdp_carry_ops_batch(self.ctx.handle, sa.handle, sb.handle, tasks, n, out, fp), "gamdp_carry_ops_batch")
-        return [MyAlignment.from_result(r, None) for r in out], list(fp)
+        return self._fill_only(calls, bands, "gamdp_carry_ops_batch", L.Result, with_fp=True, convert=_no_ops,
+                               method="find_results_with_ops_fingerprints")
 
     def find_alignments_with_ops_fingerprints(self, calls, bands=None):
         """find_alignments(calls, want_ops=True) with the fingerprint of every edit string in place of the strings
         (gamdp_align_batch_fp: the strings stay on the device, k_ops_fp folds them there): (results, fingerprints), the results
         without edit strings (ops None).  fingerprints[i] equals ops_fingerprint(find_alignments(calls, want_ops=True)[i].ops) for a
         call whose status is OK and is 0 otherwise.  Any band find_alignments takes."""
-        n = len(calls)
-        if n == 0:
-            return [], []
-        if isinstance(self.ctx, MultiContext):
-            raise L.GamdpError("find_alignments_with_ops_fingerprints is a single-context call")
-        tasks, sa, sb = self._tasks(calls, bands)
-        out = (L.Result * n)()
-        fp = (C.c_uint32 * n)()
-        _check(self.ctx, self.ctx.lib.gamdp_align_batch_fp(self.ctx.handle, sa.handle, sb.handle, tasks, n, out, fp), "gamdp_align_batch_fp")
-        return [MyAlignment.from_result(r, None) for r in out], list(fp)
+        return self._fill_only(calls, bands, "gamdp_align_batch_fp", L.Result, with_fp=True, convert=_no_ops,
+                               method="find_alignments_with_ops_fingerprints")
 
     def find_alignments(self, calls, want_ops=False, bands=None) -> List[MyAlignment]:
         """calls: list of (a, begin_a, end_a, b, begin_b, end_b[, force_start[, force_end]]); all a's

@@ -1101,8 +1101,9 @@ int Ctx::align(const TaskSrc& tasks, size_t n, gamdp_result* out, const gamdp_op
 // The same checks, pre-checks and descriptors as align(); then one launch of the call's kernel per column count C the batch's bands
 // take, each over its tasks by decreasing rows.  No scratch arena, no planner: a wavefront needs nothing but its registers.
 
-// What the calls differ in: the record a wavefront leaves, the kernel that writes it, the caller's result made from it, and whether
-// a fingerprint per task comes back beside the records (set_ops_fp: where the kernel's parameters take that array).
+// What the calls differ in: the record a wavefront leaves, the kernel that writes it, the caller's result made from it, the log its
+// launches go to, and whether a fingerprint per task comes back beside the records (set_ops_fp: where the kernel's parameters take
+// that array).
 struct ScoreCall {
     typedef ScoreRec Rec;
     typedef gamdp_score_result Out;
@@ -1111,6 +1112,7 @@ struct ScoreCall {
     static constexpr bool has_ops_fp = false;
     static void set_ops_fp(Params&, u32*) {}
     static const KernelFamily& family() { return score_family(); }
+    static std::vector<gamdp_score_launch_info>& log(Ctx& c) { return c.score_log; }
     static u32 cols_of(const Rec& r) { return r.info >> 8; }
     static void collect(const Rec& r, u64 cells, Out& o)
     {
@@ -1129,6 +1131,7 @@ struct CarryCall {
     static constexpr bool has_ops_fp = false;
     static void set_ops_fp(Params&, u32*) {}
     static const KernelFamily& family() { return carry_family(); }
+    static std::vector<gamdp_score_launch_info>& log(Ctx& c) { return c.carry_log; }
     static u32 cols_of(const Rec& r) { return r.flags >> CARRY_COLS_SHIFT; }
     static void collect(const Rec& r, u64 cells, Out& o) { fill_result(r, cells, o); }   // as align() makes a gamdp_result of a record
 };
@@ -1138,12 +1141,14 @@ struct CarryOpsCall : CarryCall {   // the record and the result of CarryCall; t
     static constexpr bool has_ops_fp = true;
     static void set_ops_fp(Params& p, u32* d) { p.ops_fp = d; }
     static const KernelFamily& family() { return carry_ops_family(); }
+    static std::vector<gamdp_score_launch_info>& log(Ctx& c) { return c.carry_ops_log; }
 };
 
 template <class K>
-int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log, u32* const ops_fp)
+int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, u32* const ops_fp)
 {
     typedef typename K::Rec Rec;
+    std::vector<gamdp_score_launch_info>& log = K::log(*this);
     if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_EHIP; }
     log.clear();
     if (n == 0) return 0;
@@ -1244,9 +1249,20 @@ int Ctx::fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::ve
     return 0;
 }
 
-int Ctx::score(const TaskSrc& tasks, size_t n, gamdp_score_result* out) { return fill_only<ScoreCall>(tasks, n, out, score_log); }
-int Ctx::carry(const TaskSrc& tasks, size_t n, gamdp_result* out) { return fill_only<CarryCall>(tasks, n, out, carry_log); }
-int Ctx::carry_ops(const TaskSrc& tasks, size_t n, gamdp_result* out, u32* ops_fp) { return fill_only<CarryOpsCall>(tasks, n, out, carry_ops_log, ops_fp); }
+// The C entry point of a fill-only call: `out` is required whatever n (gamdp_align_batch allows NULL with n == 0), and so is ops_fp
+// where the call has one.
+template <class K>
+static int fill_only_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
+                           typename K::Out* out, u32* ops_fp = nullptr)
+{
+    if (!ctx || !set_a || !set_b || !out || (K::has_ops_fp && !ops_fp) || (n && !tasks)) return GAMDP_EINVAL;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    return guarded(c, [&]() -> int {
+        TaskSrc src;   // the caller's array, read in place
+        src.gt = tasks; src.sa = reinterpret_cast<const SeqSet*>(set_a); src.sb = reinterpret_cast<const SeqSet*>(set_b);
+        return c->fill_only<K>(src, n, out, ops_fp);
+    });
+}
 
 // ---- fingerprints of edit strings on the device: gamdp_align_batch_fp, gamdp_ops_fingerprint_batch (k_ops_fp, gamdp_ops_fp.hip) ----
 
@@ -1519,6 +1535,17 @@ static const WalkSkipCount* walk_skip_stats(const gamdp_ctx* ctx, int family, S*
     return &n;
 }
 
+// What the four *_info getters do with their log: its length into *n, its first `cap` records into `out`.
+template <class T>
+static int copy_log(const gamdp_ctx* ctx, std::vector<T> Ctx::*which, T* out, size_t cap, size_t* n)
+{
+    if (!ctx || (cap && !out)) return GAMDP_EINVAL;   // (before the context is touched)
+    const std::vector<T>& log = reinterpret_cast<const Ctx*>(ctx)->*which;
+    if (n) *n = log.size();
+    std::copy_n(log.begin(), std::min(cap, log.size()), out);
+    return 0;
+}
+
 }  // namespace gamdp
 
 // ---- C ABI ----------------------------------------------------------------------------------------
@@ -1570,11 +1597,7 @@ int gamdp_ctx_kernel_time(gamdp_ctx* ctx, double* total_ms, uint64_t* launches, 
 
 int gamdp_ctx_launch_info(const gamdp_ctx* ctx, gamdp_launch_info* out, size_t cap, size_t* n)
 {
-    if (!ctx || (cap && !out)) return GAMDP_EINVAL;
-    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    if (n) *n = c->launch_log.size();
-    for (size_t i = 0; i < c->launch_log.size() && i < cap; i++) out[i] = c->launch_log[i];
-    return 0;
+    return copy_log(ctx, &Ctx::launch_log, out, cap, n);
 }
 
 static_assert(sizeof(gamdp_walk_skip_stats) == 48 && offsetof(gamdp_walk_skip_stats, strips) == 32 && offsetof(gamdp_walk_skip_stats, mode) == 40,
@@ -1734,43 +1757,23 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
 int gamdp_score_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
                       gamdp_score_result* out)
 {
-    if (!ctx || !set_a || !set_b || !out || (n && !tasks)) return GAMDP_EINVAL;
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    return guarded(c, [&]() -> int {
-        TaskSrc src;   // the caller's array, read in place
-        src.gt = tasks; src.sa = reinterpret_cast<const SeqSet*>(set_a); src.sb = reinterpret_cast<const SeqSet*>(set_b);
-        return c->score(src, n, out);
-    });
+    return fill_only_batch<ScoreCall>(ctx, set_a, set_b, tasks, n, out);
 }
 
 int gamdp_ctx_score_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n)
 {
-    if (!ctx || (cap && !out)) return GAMDP_EINVAL;
-    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    if (n) *n = c->score_log.size();
-    for (size_t i = 0; i < c->score_log.size() && i < cap; i++) out[i] = c->score_log[i];
-    return 0;
+    return copy_log(ctx, &Ctx::score_log, out, cap, n);
 }
 
 int gamdp_carry_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
                       gamdp_result* out)
 {
-    if (!ctx || !set_a || !set_b || !out || (n && !tasks)) return GAMDP_EINVAL;
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    return guarded(c, [&]() -> int {
-        TaskSrc src;   // the caller's array, read in place
-        src.gt = tasks; src.sa = reinterpret_cast<const SeqSet*>(set_a); src.sb = reinterpret_cast<const SeqSet*>(set_b);
-        return c->carry(src, n, out);
-    });
+    return fill_only_batch<CarryCall>(ctx, set_a, set_b, tasks, n, out);
 }
 
 int gamdp_ctx_carry_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n)
 {
-    if (!ctx || (cap && !out)) return GAMDP_EINVAL;
-    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    if (n) *n = c->carry_log.size();
-    for (size_t i = 0; i < c->carry_log.size() && i < cap; i++) out[i] = c->carry_log[i];
-    return 0;
+    return copy_log(ctx, &Ctx::carry_log, out, cap, n);
 }
 
 int gamdp_task_preflight(uint64_t alen, uint64_t blen, uint32_t band, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,
@@ -1785,22 +1788,12 @@ int gamdp_task_preflight(uint64_t alen, uint64_t blen, uint32_t band, uint64_t b
 int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
                           gamdp_result* out, uint32_t* ops_fp)
 {
-    if (!ctx || !set_a || !set_b || !out || !ops_fp || (n && !tasks)) return GAMDP_EINVAL;
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    return guarded(c, [&]() -> int {
-        TaskSrc src;   // the caller's array, read in place
-        src.gt = tasks; src.sa = reinterpret_cast<const SeqSet*>(set_a); src.sb = reinterpret_cast<const SeqSet*>(set_b);
-        return c->carry_ops(src, n, out, ops_fp);
-    });
+    return fill_only_batch<CarryOpsCall>(ctx, set_a, set_b, tasks, n, out, ops_fp);
 }
 
 int gamdp_ctx_carry_ops_info(const gamdp_ctx* ctx, gamdp_score_launch_info* out, size_t cap, size_t* n)
 {
-    if (!ctx || (cap && !out)) return GAMDP_EINVAL;
-    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
-    if (n) *n = c->carry_ops_log.size();
-    for (size_t i = 0; i < c->carry_ops_log.size() && i < cap; i++) out[i] = c->carry_ops_log[i];
-    return 0;
+    return copy_log(ctx, &Ctx::carry_ops_log, out, cap, n);
 }
 
 uint64_t gamdp_task_ops_cap(uint64_t alen, uint64_t blen, uint32_t band, uint64_t begin_a, uint64_t end_a, uint64_t begin_b,

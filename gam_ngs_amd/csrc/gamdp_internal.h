@@ -333,13 +333,10 @@ struct Ctx {
     void align_collect(AlignCall& a);
     int grow_staging(u64 base);   // h_tasks / h_results
     // gamdp_score_batch (gamdp_host.cpp; the kernel: gamdp_score.hip), and what its last call launched (gamdp_ctx_score_info)
-    int score(const TaskSrc& tasks, size_t n, gamdp_score_result* out);
     std::vector<gamdp_score_launch_info> score_log;
     // gamdp_carry_batch (the kernel: gamdp_carry.hip), and what its last call launched (gamdp_ctx_carry_info)
-    int carry(const TaskSrc& tasks, size_t n, gamdp_result* out);
     std::vector<gamdp_score_launch_info> carry_log;
     // gamdp_carry_ops_batch (the kernel: gamdp_carry_ops.hip), and what its last call launched (gamdp_ctx_carry_ops_info)
-    int carry_ops(const TaskSrc& tasks, size_t n, gamdp_result* out, u32* ops_fp);
     std::vector<gamdp_score_launch_info> carry_ops_log;
     u32* d_ops_fp = nullptr; u64 cap_ops_fp = 0;   // its fingerprints, one per task of the batch
     // gamdp_align_batch_fp / gamdp_ops_fingerprint_batch (the kernel: gamdp_ops_fp.hip): fingerprints of strings that lie in d_ops, a
@@ -353,8 +350,9 @@ struct Ctx {
     int strings_fp(const uint8_t* ops, const u64* off, const u64* len, size_t n, u32* fp);
     // one launch of k_ops_fp<forward> over `tasks` (strings in d_ops; seg_first as OpsFpParams) and the download of fp[0 .. n_fp)
     int ops_fp_launch(bool forward, const std::vector<OpsFpTask>& tasks, const std::vector<u32>& seg_first, size_t n_fp, u32* fp);
-    // what the three share (gamdp_host.cpp); ops_fp: the caller's fingerprint array of a call that has one
-    template <class K> int fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, std::vector<gamdp_score_launch_info>& log, u32* ops_fp = nullptr);
+    // what the three share (gamdp_host.cpp): K is the call's traits, which name its log; ops_fp: the caller's fingerprint array of a
+    // call that has one
+    template <class K> int fill_only(const TaskSrc& tasks, size_t n, typename K::Out* out, u32* ops_fp = nullptr);
     int align(const ITask* tasks, size_t n, gamdp_result* out, const gamdp_ops* ops) { TaskSrc s; s.it = tasks; return align(s, n, out, ops); }
     int align(const std::vector<ITask>& tasks, gamdp_result* out, const gamdp_ops* ops) { return align(tasks.data(), tasks.size(), out, ops); }
     ~Ctx();

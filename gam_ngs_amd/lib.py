@@ -275,7 +275,6 @@ def load_library():
     lib.gamdp_ctx_stream.argtypes = [vp]
     lib.gamdp_ctx_stream.restype = vp
     lib.gamdp_ctx_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
-    lib.gamdp_ctx_launch_info.argtypes = [vp, C.POINTER(LaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
     lib.gamdp_seqset_create.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(u64), u32, C.c_int, C.POINTER(vp)]
     lib.gamdp_seqset_destroy.argtypes = [vp]
     lib.gamdp_seqset_destroy.restype = None
@@ -286,20 +285,17 @@ def load_library():
     lib.gamdp_align_batch.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(Result), C.POINTER(Ops)]
     lib.gamdp_align_merge_blocks.argtypes = [vp, vp, vp, C.POINTER(MbIn), C.c_size_t, u32, C.POINTER(MbOut),
                                              C.POINTER(Result), u32]
-    lib.gamdp_score_batch.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(ScoreResult)]
-    lib.gamdp_score_batch.restype = C.c_int
-    lib.gamdp_ctx_score_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.gamdp_ctx_score_info.restype = C.c_int
-    lib.gamdp_carry_batch.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(Result)]
-    lib.gamdp_carry_batch.restype = C.c_int
-    lib.gamdp_ctx_carry_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.gamdp_ctx_carry_info.restype = C.c_int
+    # the fill-only calls (result struct, whether a fingerprint array follows it) and the four launch logs (record struct)
+    for call, out, with_fp in (("gamdp_score_batch", ScoreResult, False), ("gamdp_carry_batch", Result, False),
+                               ("gamdp_carry_ops_batch", Result, True)):
+        getattr(lib, call).argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(out)] + [C.POINTER(u32)] * with_fp
+        getattr(lib, call).restype = C.c_int
+    for getter, rec in (("gamdp_ctx_launch_info", LaunchInfo), ("gamdp_ctx_score_info", ScoreLaunchInfo),
+                        ("gamdp_ctx_carry_info", ScoreLaunchInfo), ("gamdp_ctx_carry_ops_info", ScoreLaunchInfo)):
+        getattr(lib, getter).argtypes = [vp, C.POINTER(rec), C.c_size_t, C.POINTER(C.c_size_t)]
+        getattr(lib, getter).restype = C.c_int
     lib.gamdp_ops_fingerprint.argtypes = [C.c_char_p, u64]
     lib.gamdp_ops_fingerprint.restype = u32
-    lib.gamdp_carry_ops_batch.argtypes = [vp, vp, vp, C.POINTER(Task), C.c_size_t, C.POINTER(Result), C.POINTER(u32)]
-    lib.gamdp_carry_ops_batch.restype = C.c_int
-    lib.gamdp_ctx_carry_ops_info.argtypes = [vp, C.POINTER(ScoreLaunchInfo), C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.gamdp_ctx_carry_ops_info.restype = C.c_int
     if hasattr(lib, "gamdp_align_batch_fp"):   # (as gamdp_ctx_set_walk_skip below: older builds through GAMDP_LIB)
         lib.gamdp_task_ops_cap.argtypes = [u64, u64, u32, u64, u64, u64, u64, C.c_int, C.c_int]
         lib.gamdp_task_ops_cap.restype = u64

@@ -193,6 +193,9 @@ def sprinkle_n(rng, s, p):
 TIE_FLAGS = ((False, False), (False, True), (True, False), (True, True))   # (fs, fe)
 
 
+TIE_BANDS, TIE_NS, TIE_PER = (20, 150, 200, 512, 600), (700, 2600), 6   # the `tie_windows` group of tests/test_oracle_vs_ref.py
+
+
 def tie_window_cases(seed, bands, ns, per):
     """`per` windows on adversarial_pair(kind, n, band), for every band, every kind of ADVERSARIAL_KINDS and every n: the tie-rich long
     pairs (homopolymer, dinucleotide, tandem, complement ...) with what the committed adversarial vectors lack -- windows, force flags, N.

@@ -17,9 +17,9 @@ import pytest
 
 import _cases
 import _fpmodel as F
+import _fillonly as S       # coded, cols_for, edge_cases, view_cases, small_set, plain_tasks, fp_of, whole, got_of
 import _golden
 import _oracle as O
-import test_gpu_score_batch as S      # coded, cols_for, edge_cases, view_cases, small_set, plain_tasks
 from _gpu import ctx
 import gam_ngs_amd as gam
 from gam_ngs_amd import api
@@ -27,21 +27,7 @@ from gam_ngs_amd import lib as L
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = tuple(f for f, _ in L.Result._fields_ if f != "pad_")
-
-
-def fp_of(ops):
-    """the definition, of an edit string over O.OPS"""
-    return F.fp_def(O.OPS.index(ch) for ch in ops)
-
-
-def whole(r):
-    """every field of a gamdp_result"""
-    return tuple(getattr(r, f) for f in FIELDS)
-
-
-def got_of(r):
-    return (tuple(r.key()), r.cells)
+fp_of, whole, got_of = S.fp_of, S.whole, S.got_of
 
 
 def geometry(c):

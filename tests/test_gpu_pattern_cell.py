@@ -19,7 +19,7 @@ import pytest
 
 import _cases
 import _oracle as O
-import test_gpu_carry_batch as CB      # run_results / got_of: every field of gamdp_carry_batch's results
+import _fillonly as F       # run / got_of: every field of gamdp_carry_batch's results
 from _gpu import ctx, oracle_for, run_cases
 from gam_ngs_amd import lib as L
 
@@ -128,9 +128,9 @@ def test_batch_against_the_oracle_and_the_carry_kernel(name):
             assert r.key() == o.key(), (name, k, want_ops, r.key(), o.key())
             assert r.cells == o.cells, (name, k)
             assert r.ops == (ops if want_ops else None), (name, k, "edit string")
-    carry = CB.run_results(ctx(), cases, ascii=True)
-    assert carry == [CB.got_of(o) for o, _ in want], name
-    assert carry == [CB.got_of(r) for r in res], name
+    carry = F.run("carry", ctx(), cases, ascii=True)
+    assert carry == [F.got_of(o) for o, _ in want], name
+    assert carry == [F.got_of(r) for r in res], name
     print(name, len(cases), "calls,", sum(r["units_packed_top"] for r in info), "units with packed top blocks,", sum(r["strips"] for r in info), "strip calls")
 
 

@@ -1,4 +1,4 @@
-"""Tie-rich windowed and forced long pairs (tests/_cases.py tie_window_cases) through every alignment kernel and through k_score.
+"""Tie-rich windowed and forced long pairs (tests/_ties.py) through every alignment kernel and through k_score.
 
 The two rules of find_alignment that a kernel restates and can get subtly wrong are tie rules: the end-cell scan takes the FIRST maximum
 (last row left to right, then the pos == end_a anti-diagonal downwards, strict '>': banded_smith_waterman.cc:174-212) and the traceback
@@ -9,76 +9,25 @@ values, the run-skipping summary walk, k_align_w's reduction and k_score's (valu
 Expected values come from the CPU oracle, which tests/test_oracle_vs_ref.py pins to the reference's own code on the whole `tie_windows`
 group.  What ran is taken from gamdp_ctx_launch_info / gamdp_ctx_score_info.  Nothing here is built to fault: every input is a valid call.
 """
-import functools
 import os
-import random
 import subprocess
 import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-import _cases
+import _fillonly as F                 # want_of, run, cols_for: one statement of the end-cell rule
 import _oracle as O
 import _views as V
-import test_gpu_score_batch as S      # end_cell / want_of, run_scores, cols_for: one statement of the end-cell rule
-import test_oracle_vs_ref as T        # the bands, lengths and windows per pair of the group the oracle is pinned on
-from _gpu import ctx, oracle_for, run_cases
+from _gpu import ctx, run_cases
+from _ties import ALIGN_BANDS, LONG_BANDS, SCORE_BANDS, band_cases, long_cases, wants, what
 import gam_ngs_amd as gam
 from gam_ngs_amd import lib as L
 
 pytestmark = pytest.mark.gpu
 
-SEED = 0
-EXTRA_BANDS = (129, 400)          # the generic widths the group's bands leave out: 5 columns per lane (a direction per cell), 17 (direction-free)
-SCORE_ONLY_BANDS = (64,)          # k_score<3>: bands 20, 129 and 150 share k_score<2> and <5>
-ALIGN_BANDS = T.TIE_BANDS + EXTRA_BANDS
-SCORE_BANDS = tuple(b for b in ALIGN_BANDS + SCORE_ONLY_BANDS if b <= 543)
-LONG_BANDS = (150, 512)
-LONG_KINDS = {150: ("homopolymer", "ac_shift1", "tandem19"), 512: ("homopolymer", "ac_shift1", "tandem17")}   # the 20 kb pairs
 DIAG_LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gam_ngs_amd", "libgamdp_diag.so")
 
-assert {S.cols_for(b) for b in SCORE_BANDS} == {2, 3, 5, 9, 17}    # all five k_score<C> over the file
-
-
-# ---- the cases and what the oracle says about them, once per process ------------------------------------------------------------
-
-@functools.lru_cache(maxsize=None)
-def band_cases(band):
-    """(a): the cases of the `tie_windows` group at one of its bands; 2 windows on the 2.6 kb pairs at the other bands"""
-    if band in T.TIE_BANDS:
-        return tuple(_cases.tie_window_cases(SEED, (band,), T.TIE_NS, T.TIE_PER))
-    return tuple(_cases.tie_window_cases(SEED, (band,), (2600,), 2))
-
-
-@functools.lru_cache(maxsize=None)
-def long_cases(band):
-    """(b): 4 windows on every 6 kb pair, 2 on three 20 kb pairs (strips, re-centring, ring refills), each followed by an ordinary
-    related pair of the same lengths and the same window, without flags: the tasks that share a wavefront differ."""
-    tie = _cases.tie_window_cases(SEED, (band,), (6000,), 4)
-    tie += [cs for cs in _cases.tie_window_cases(SEED, (band,), (20000,), 2) if cs["tag"][0] in LONG_KINDS[band]]
-    rng = random.Random(7700 + band)
-    out = []
-    for cs in tie:
-        a = _cases.rand_seq(rng, len(cs["a"]))
-        b = (_cases.mutate(rng, a) + _cases.rand_seq(rng, 64))[:len(cs["b"])]
-        out.append(cs)
-        out.append(dict(cs, a=a.encode(), b=b.encode(), fs=False, fe=False, tag=("partner of",) + cs["tag"]))
-    return tuple(out)
-
-
-@functools.lru_cache(maxsize=None)
-def wants(which, band):
-    """[(oracle result, edit string)] of band_cases / long_cases"""
-    cases = band_cases(band) if which == "band" else long_cases(band)
-    with ThreadPoolExecutor(16) as ex:   # (the oracle's C code runs outside the GIL)
-        out = list(ex.map(oracle_for, cases))
-    assert all(o.status != O.INVALID for o, _ in out)
-    return out
-
-
-def what(cs):
-    return (cs["tag"],) + tuple(cs[k] for k in ("band", "begin_a", "end_a", "begin_b", "end_b", "fs", "fe")) + (len(cs["a"]), len(cs["b"]))
+assert {F.cols_for(b) for b in SCORE_BANDS} == {2, 3, 5, 9, 17}    # all five k_score<C> over the file
 
 
 def check_align(cases, want, want_ops):
@@ -173,12 +122,12 @@ def test_long_tuned_shapes(band):
 # ---- (c) gamdp_score_batch ------------------------------------------------------------------------------------------------------
 
 def check_scores(cases, want, band):
-    got = S.run_scores(ctx(), cases, ascii=True)
+    got = F.run("score", ctx(), cases, ascii=True)
     assert len(got) == len(cases)
     for cs, g, (o, ops) in zip(cases, got, want):
-        assert tuple(g) == S.want_of(o, ops), (what(cs), tuple(g), S.want_of(o, ops))
+        assert tuple(g) == F.want_of(o, ops), (what(cs), tuple(g), F.want_of(o, ops))
     info = ctx().score_info()
-    assert [r["kernel"] for r in info] == ["k_score<%d>" % S.cols_for(band)], info
+    assert [r["kernel"] for r in info] == ["k_score<%d>" % F.cols_for(band)], info
     print("band %d: %d scores, ran %s" % (band, len(cases), info[0]["kernel"]))
 
 

@@ -101,7 +101,7 @@ def child_periodic_indels():
 
 def child_tie_rich():
     """4. homopolymers, dinucleotide and tandem repeats: `up` / `left` tie with `diag` all along the path"""
-    import test_gpu_tie_windows as TW
+    import _ties as TW
     cases = [cs for cs in TW.long_cases(BAND) if b"N" not in cs["a"] + cs["b"]]
     assert len(cases) >= 40 and {cs["tag"][0] for cs in cases} >= {"homopolymer", "ac_shift1", "tandem19", "complement"}
     want = TW.wants("long", BAND)

@@ -151,9 +151,9 @@ def child_periodic_indels():
 
 
 def tie_cases():
-    """test_gpu_tie_windows.long_cases(band) at the two bands it knows (150, 512); the same construction on the 6 kb pairs at the bands
+    """_ties.long_cases(band) at the two bands it knows (150, 512); the same construction on the 6 kb pairs at the bands
     of the generic kernels -> (cases, oracle answers)"""
-    import test_gpu_tie_windows as TW
+    import _ties as TW
     if K.band in TW.LONG_BANDS:
         return list(TW.long_cases(K.band)), list(TW.wants("long", K.band))
     tie = _cases.tie_window_cases(TW.SEED, (K.band,), (6000,), 4)

@@ -105,7 +105,7 @@ def child_periodic_indels():
 
 def child_tie_rich():
     """4. homopolymers, dinucleotide and tandem repeats: `up` / `left` tie with `diag` all along the path"""
-    import test_gpu_tie_windows as TW
+    import _ties as TW
     every = TW.long_cases(BAND)
     keep = [k for k, cs in enumerate(every) if b"N" not in cs["a"] + cs["b"]]
     cases = [every[k] for k in keep]

@@ -46,7 +46,7 @@ def medium_cases():
     return out
 
 
-TIE_BANDS, TIE_NS, TIE_PER = (20, 150, 200, 512, 600), (700, 2600), 6
+TIE_BANDS, TIE_NS, TIE_PER = _cases.TIE_BANDS, _cases.TIE_NS, _cases.TIE_PER   # (tests/_ties.py takes them from there too)
 
 
 def tie_window_cases():
