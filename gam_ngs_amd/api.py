@@ -125,6 +125,17 @@ class Context:
         dict (gamdp_ctx_walk_skip_backoff_stats)."""
         return self._walk_stats("gamdp_ctx_walk_skip_backoff_stats", L.WalkSkipBackoffStats)
 
+    def set_ops_walk(self, mode: int):
+        """How the walks of calls that want an edit string write it: L.OPS_WALK_STEPS (the default: one op per iteration) or
+        L.OPS_WALK_RUNS (a whole run of diagonal steps per iteration, its ops written by the lanes that compared its bases;
+        gamdp_ctx_set_ops_walk).  Results and bytes do not depend on it; k_align_w ignores it."""
+        self._set_walk_mode("gamdp_ctx_set_ops_walk", mode)
+
+    def ops_walk_stats(self):
+        """What the walks of the last gamdp_align_batch / gamdp_align_batch_fp on this context that wrote their string a run at a time
+        counted, as a dict (gamdp_ctx_ops_walk_stats)."""
+        return self._walk_stats("gamdp_ctx_ops_walk_stats", L.OpsWalkStats)
+
     def l1_tail_calls(self):
         """The tail alignments of the last alignMergeBlocks on this context and the seed each was given, as
         (merge_block, right, begin_a, source) tuples ordered by merge block, left before right (gamdp_ctx_l1_tail_calls)."""
@@ -323,6 +334,14 @@ class MultiContext:
     def walk_skip_backoff_stats(self):
         """Context.walk_skip_backoff_stats of every context of the handle (a list of dicts)."""
         return self._walk_stats("gamdp_ctx_walk_skip_backoff_stats", L.WalkSkipBackoffStats)
+
+    def set_ops_walk(self, mode: int, which=None):
+        """Context.set_ops_walk on every context of the handle, or on context `which` alone."""
+        self._set_walk_mode("gamdp_ctx_set_ops_walk", mode, which)
+
+    def ops_walk_stats(self):
+        """Context.ops_walk_stats of every context of the handle (a list of dicts)."""
+        return self._walk_stats("gamdp_ctx_ops_walk_stats", L.OpsWalkStats)
 
     def l1_chain_stats(self):
         """Context.l1_chain_stats of every context of the handle (a list of dicts)."""

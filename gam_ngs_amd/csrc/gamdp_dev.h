@@ -92,7 +92,10 @@ struct LaunchParams {
 // (LS_SKIP_*: the eight-task kernel's walks in LP_WALK_SKIP_DIAG launches -- tests made, groups whose equality was evaluated, groups
 // jumped over, and the rows by which the jumped-over spans fall short of 64 each (the span below a walk's end cell ends on the next
 // checkpoint row: 1 .. 64 rows) -- rows = 64 groups - short, which keeps the words 32 bits wide; gamdp_ctx_walk_skip_stats)
-enum : int { LS_UNITS = 0, LS_DIRFREE, LS_PACKED_TOP, LS_PACKED_TOP_MIXED, LS_STRIPS, LS_TOP_WANTED, LS_SKIP_TESTS, LS_SKIP_TESTED, LS_SKIP_GROUPS, LS_SKIP_SHORT, LS_SKIP_HELD, LS_COUNT = 12 };
+enum : int { LS_UNITS = 0, LS_DIRFREE, LS_PACKED_TOP, LS_PACKED_TOP_MIXED, LS_STRIPS, LS_TOP_WANTED, LS_SKIP_TESTS, LS_SKIP_TESTED, LS_SKIP_GROUPS, LS_SKIP_SHORT, LS_SKIP_HELD,
+              LS_OPS_TASKS, LS_OPS_BY_RUN, LS_OPS_BY_STEP = LS_OPS_BY_RUN + 2, LS_OPS_RUNS = LS_OPS_BY_STEP + 2, LS_COUNT = LS_OPS_RUNS + 2 };
+// (LS_OPS_*: the walks of LP_OPS_WALK_RUNS launches that wrote their edit string a run at a time, below -- the walks, and as 64-bit
+// counters of two words each, low word first: the ops of their run iterations, their other ops, the run iterations; gamdp_ctx_ops_walk_stats)
 // (LS_SKIP_HELD: candidate points a walk passed without a test, LP_WALK_SKIP_BACKOFF below; gamdp_ctx_walk_skip_backoff_stats)
 // the eight-task kernel's walks test for indel-free groups before they ask for a strip (kernel_walk.inc, walk_many<..., SKIP>):
 // set by the host for contexts in GAMDP_WALK_SKIP_DIAG mode; every other kernel ignores it
@@ -111,6 +114,10 @@ constexpr u32 LP_WALK_SKIP_I32 = 128;
 // group puts the count back to 0.  The indel rate of a pair is about the same all along it, and a failed test is a serial memory round
 // trip in front of the strip call it did not save.
 constexpr u32 LP_WALK_SKIP_BACKOFF = 4;
+// The one-task walk writes the edit string of a task with TF_WANT_OPS a diagonal run at a time (kernel_finish.inc, finish_walk<...,
+// OPSRUN>) instead of a step at a time: set by the host for every systolic launch of a context in GAMDP_OPS_WALK_RUNS mode of
+// gamdp_ctx_set_ops_walk.  Tasks without TF_WANT_OPS, k_align_w and the chain walkers ignore it; bytes and results are the same.
+constexpr u32 LP_OPS_WALK_RUNS = 8;
 // ... the schedule: 2^fails - 1 candidate points, WALK_BACKOFF_HOLD_MAX at the most (DESIGN.md section 6 has the sweep behind the value).
 // The device code and gamdp_walk_skip_backoff_hold (gamdp_host.cpp) both read it.
 #ifndef GAMDP_WALK_BACKOFF_HOLD_MAX   // (the sweep builds one library per value)

@@ -89,6 +89,7 @@ const Tuning& tuning()
         if ((e = std::getenv("GAMDP_L1_WALK_ANY_BAND"))) x.l1_walk_any_band = std::atoi(e) == 1;
         for (int f = 0; f < WS_COUNT; f++)
             if ((e = std::getenv(walk_skip_families[f].env))) x.walk_skip.family[f] = std::atoi(e) == 1 ? GAMDP_WALK_SKIP_DIAG : GAMDP_WALK_STRIPS;
+        if ((e = std::getenv("GAMDP_OPS_WALK_RUNS"))) x.ops_walk = std::atoi(e) == 1 ? GAMDP_OPS_WALK_RUNS : GAMDP_OPS_WALK_STEPS;
         if ((e = std::getenv("GAMDP_WALK_SKIP_BACKOFF"))) x.walk_skip.backoff = std::atoi(e) == 1 ? GAMDP_WALK_BACKOFF_ON : GAMDP_WALK_BACKOFF_OFF;
         return x;
     }();
@@ -311,6 +312,7 @@ int Ctx::init(int dev)
     l1_chain = tuning().l1_chain_carry ? GAMDP_L1_CHAIN_CARRY : GAMDP_L1_CHAIN_WALK;
     walk_bands = tuning().l1_walk_any_band ? GAMDP_L1_WALK_ANY_BAND : GAMDP_L1_WALK_BAND_150;
     walk_skip = tuning().walk_skip;
+    ops_walk = tuning().ops_walk;
     if (hipSetDevice(dev) != hipSuccess) { set_error("hipSetDevice failed"); return GAMDP_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("hipGetDeviceProperties failed"); return GAMDP_ENODEV; }
@@ -868,7 +870,7 @@ int Ctx::align_scratch(u64 arena_call)
 static bool walks_side_by_side(const Launch& L) { return L.kid == K_P17_CE4 && (u64)L.count / 2 <= tuning().side_walk_rounds * L.n_slots; }
 
 // LaunchParams::flags / prio_* of a launch
-static void launch_policy(const Launch& L, LaunchParams& p, const WalkSkipModes& walk_skip)
+static void launch_policy(const Launch& L, LaunchParams& p, const WalkSkipModes& walk_skip, const int ops_walk)
 {
     const Tuning& tu = tuning();
     const u64 tpw = (u64)kernel_info[L.kid].tasks_per_wave, units = L.count / tpw;
@@ -879,6 +881,8 @@ static void launch_policy(const Launch& L, LaunchParams& p, const WalkSkipModes&
     const int ws = walk_skip_family(L.kid);
     if (ws >= 0 && walk_skip.family[ws] == GAMDP_WALK_SKIP_DIAG)
         p.flags |= walk_skip_families[ws].flag | (walk_skip.backoff == GAMDP_WALK_BACKOFF_ON ? LP_WALK_SKIP_BACKOFF : 0u);
+    // (gamdp_ctx_set_ops_walk: every systolic kernel has the instance; a task takes it when it wants a string)
+    if (ops_walk == GAMDP_OPS_WALK_RUNS && L.kid != K_WIDE) p.flags |= LP_OPS_WALK_RUNS;
     // the end-cell / strip / walk phase of the two- and eight-task kernels issues one level above a steady-state fill in
     // launches of more than two rounds (gamdp_dev.h; GAMDP_WALK_PRIO=0..3 overrides, A/B)
     p.flags |= (tu.walk_prio >= 0 ? (u32)tu.walk_prio : (units > 2ull * L.n_slots ? 1u : 0u)) << LP_WALK_PRIO_SHIFT;
@@ -936,7 +940,7 @@ int Ctx::align_run(AlignCall& a)
         p.scratch = d_scratch + L.scratch_off; p.slot_words = L.slot_words; p.dir_words = L.dir_words; p.ypad = L.ypad;
         p.ckpt_off = L.ckpt_off; p.bnd_off = L.bnd_off;
         p.stats = d_stats + li * LS_COUNT;
-        launch_policy(L, p, walk_skip);
+        launch_policy(L, p, walk_skip, ops_walk);
         hipStream_t const on = L.aux ? aux_stream : stream;
         HIPCHK(this, hipEventRecord(events[li].first, on));
         const int e = launch_align(L.kid, p, L.n_slots, L.dyn_lds, on);
@@ -1007,6 +1011,12 @@ void Ctx::align_collect(AlignCall& a)
                 one.launches = 1; one.launches_side_by_side = walks_side_by_side(L) ? 1u : 0u;
                 one.ran = true;
                 walk_skip_count[ws].add(one);
+            }
+            if (L.kid != K_WIDE) {   // gamdp_ctx_ops_walk_stats (all 0 in STEPS mode: only the OPSRUN instance counts)
+                auto u64_at = [&](int w) { return (u64)st[w] | ((u64)st[w + 1] << 32); };
+                OpsWalkCount one;
+                one.tasks = st[LS_OPS_TASKS]; one.ops_by_run = u64_at(LS_OPS_BY_RUN); one.ops_by_step = u64_at(LS_OPS_BY_STEP); one.runs = u64_at(LS_OPS_RUNS);
+                ops_walk_count.add(one);
             }
             r.piece = log_piece;
             r.rounds = L.n_slots ? (double)r.units / (double)L.n_slots : 0.0;
@@ -1658,6 +1668,27 @@ int gamdp_ctx_walk_skip_backoff_stats(const gamdp_ctx* ctx, gamdp_walk_skip_back
     return 0;
 }
 
+static_assert(sizeof(gamdp_ops_walk_stats) == 40 && offsetof(gamdp_ops_walk_stats, runs) == 24 && offsetof(gamdp_ops_walk_stats, mode) == 32,
+              "gamdp_ops_walk_stats: the layout include/gamdp.h documents (gam_ngs_amd/lib.py OpsWalkStats mirrors it)");
+
+int gamdp_ctx_set_ops_walk(gamdp_ctx* ctx, int mode)
+{
+    if ((mode != GAMDP_OPS_WALK_STEPS && mode != GAMDP_OPS_WALK_RUNS) || !ctx) return GAMDP_EINVAL;
+    reinterpret_cast<Ctx*>(ctx)->ops_walk = mode;
+    return 0;
+}
+
+int gamdp_ctx_ops_walk_stats(const gamdp_ctx* ctx, gamdp_ops_walk_stats* out)
+{
+    if (!ctx || !out) return GAMDP_EINVAL;
+    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+    *out = gamdp_ops_walk_stats{};
+    out->tasks = c->ops_walk_count.tasks; out->ops_by_run = c->ops_walk_count.ops_by_run; out->ops_by_step = c->ops_walk_count.ops_by_step;
+    out->runs = c->ops_walk_count.runs;
+    out->mode = (uint32_t)c->ops_walk_ran;
+    return 0;
+}
+
 int gamdp_seqset_create(gamdp_ctx* ctx, const uint8_t* const* seqs, const uint64_t* lens, uint32_t n, int is_ascii,
                         gamdp_seqset** out)
 {
@@ -1697,6 +1728,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     const SeqSet* sb = reinterpret_cast<const SeqSet*>(set_b);
     c->launch_log.clear();
     c->reset_walk_skip_counts();
+    c->reset_ops_walk_count();
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; for (Ctx* h : c->helpers) h->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {
@@ -1748,6 +1780,7 @@ int gamdp_align_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seq
     c->kernel_ms += cc[1]->kernel_ms; c->kernel_launches += cc[1]->kernel_launches;
     c->launch_log.insert(c->launch_log.end(), cc[1]->launch_log.begin(), cc[1]->launch_log.end());
     for (int f = 0; f < WS_COUNT; f++) c->walk_skip_count[f].add(cc[1]->walk_skip_count[f]);   // (the helper ran in the owner's modes)
+    c->ops_walk_count.add(cc[1]->ops_walk_count);
     std::stable_sort(c->launch_log.begin(), c->launch_log.end(), [](const gamdp_launch_info& x, const gamdp_launch_info& y) { return x.piece < y.piece; });
     if (rc[1]) c->set_error(cc[1]->err);
     return rc[0] ? rc[0] : rc[1];
@@ -1824,6 +1857,7 @@ int gamdp_align_batch_fp(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     c->launch_log.clear();
     c->reset_walk_skip_counts();
+    c->reset_ops_walk_count();
     struct LogGuard { Ctx* c; ~LogGuard() { c->log_launches = false; } } log_guard{c};
     c->log_launches = true; c->log_piece = 0;
     return guarded(c, [&]() -> int {

@@ -89,6 +89,12 @@ struct WalkSkipCount {
     }
 };
 
+// What the OPSRUN walks of one gamdp_align_batch / gamdp_align_batch_fp counted (the LS_OPS_* words of gamdp_dev.h, summed)
+struct OpsWalkCount {
+    u64 tasks = 0, ops_by_run = 0, ops_by_step = 0, runs = 0;
+    void add(const OpsWalkCount& o) { tasks += o.tasks; ops_by_run += o.ops_by_run; ops_by_step += o.ops_by_step; runs += o.runs; }
+};
+
 // Product-library switches (environment, read once per process: gamdp_host.cpp).  None changes a result: each takes the planner
 // to the other side of a threshold that real inputs also reach (A/B measurements, and a second way through the tests).
 struct Tuning {
@@ -112,6 +118,7 @@ struct Tuning {
     bool l1_device_hits = false;        // GAMDP_L1_DEVICE_HITS=1: new contexts start in GAMDP_L1_HITS_DEVICE mode (gamdp_ctx_set_l1_hits)
     bool l1_chain_carry = false;        // GAMDP_L1_CHAIN_CARRY=1: new contexts start in GAMDP_L1_CHAIN_CARRY mode (gamdp_ctx_set_l1_chain)
     bool l1_walk_any_band = false;      // GAMDP_L1_WALK_ANY_BAND=1: new contexts start with GAMDP_L1_WALK_ANY_BAND (gamdp_ctx_set_l1_walk_bands)
+    int ops_walk = GAMDP_OPS_WALK_STEPS;   // GAMDP_OPS_WALK_RUNS=1: new contexts start in GAMDP_OPS_WALK_RUNS mode (gamdp_ctx_set_ops_walk)
     WalkSkipModes walk_skip;            // GAMDP_WALK_SKIP=1, _PAIR=1, _I32=1 (walk_skip_families), GAMDP_WALK_SKIP_BACKOFF=1: the modes new contexts start in
 };
 const Tuning& tuning();
@@ -283,6 +290,16 @@ struct Ctx {
         for (WalkSkipCount& n : walk_skip_count) n = WalkSkipCount{};
         walk_skip_ran = walk_skip;
     }
+    // whether the walks of calls that want an edit string write it a diagonal run at a time (gamdp_ctx_set_ops_walk -> LP_OPS_WALK_RUNS
+    // for every systolic launch); the mode the last gamdp_align_batch / gamdp_align_batch_fp ran in and what its launches counted
+    // (align_collect adds while log_launches is set; the chunks of an _fp call add up): gamdp_ctx_ops_walk_stats
+    int ops_walk = GAMDP_OPS_WALK_STEPS, ops_walk_ran = GAMDP_OPS_WALK_STEPS;
+    OpsWalkCount ops_walk_count;
+    void reset_ops_walk_count()   // at the start of a gamdp_align_batch / gamdp_align_batch_fp
+    {
+        ops_walk_count = OpsWalkCount{};
+        ops_walk_ran = ops_walk;
+    }
     HitsBuffers* hits = nullptr;   // gamdp_find_hits_batch, created on first use
 
     void set_error(const std::string& s) { err = s; }
@@ -362,6 +379,8 @@ inline void copy_walk_skip_modes(Ctx* to, const Ctx* from)
 {
     to->walk_skip = from->walk_skip;
     to->reset_walk_skip_counts();
+    to->ops_walk = from->ops_walk;   // (gamdp_ctx_set_ops_walk)
+    to->reset_ops_walk_count();
 }
 
 // what gamdp_fasta points to: the host-side RefSequence (names + 1 B/base codes), no GPU involved

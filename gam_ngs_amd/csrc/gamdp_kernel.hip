@@ -406,6 +406,8 @@ __device__ __forceinline__ void finish_many(const LaunchParams& p, const u32 fir
     for (int s = 0; s < NT; ++s) {
         if ((padding >> s) & 1) continue;
         const int lb = (LPT == 64) ? 0 : QL * (s & 3), hs = (LPT == 64) ? s : s >> 2;
+        // (LP_OPS_WALK_RUNS: the instance that writes the edit string a run at a time -- wave-uniform, per task)
+        if (ops_walk_runs(&p, &p.tasks[first_task + (u32)s])) { finish_walk<C, CE, HASN, LPT, PK, false, false, true>(task_tkp(s), &p.tasks[first_task + (u32)s], &p, lane, lb, hs, &wcs[s]); continue; }
         // (two-task kernel, LP_WALK_SKIP_PAIR: the instance whose walk makes the diagonal test -- wave-uniform, per launch)
         if constexpr (PK && NT == 2 && LPT == 64) {
             if (p.flags & LP_WALK_SKIP_PAIR) { finish_walk<C, CE, HASN, LPT, PK, false, true>(task_tkp(s), &p.tasks[first_task + (u32)s], &p, lane, lb, hs, &wcs[s]); continue; }

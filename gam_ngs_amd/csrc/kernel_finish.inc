@@ -36,6 +36,19 @@ __device__ __forceinline__ void mail_post(int* p, const int v, const int lane)
     if (lane == 0) __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// whether a task's walk is the OPSRUN instance of finish_walk: the launch's flag and the task's own
+__device__ __forceinline__ bool ops_walk_runs(const LaunchParams* pp, const DevTask* dtp)
+{
+    return (uni((int)pp->flags) & (int)LP_OPS_WALK_RUNS) != 0 && (uni((int)dtp->flags) & (int)TF_LIVE_MASK & (int)TF_WANT_OPS) != 0;
+}
+// a 64-bit statistics counter in two 32-bit words (the statistics words carry no 8-byte alignment): the carry goes to the high word
+__device__ __forceinline__ void stat_add64(u32* lo, const u32 v)
+{
+    if (v == 0u) return;
+    const u32 old = atomicAdd(lo, v);
+    if (old + v < old) atomicAdd(lo + 1, 1u);
+}
+
 struct WalkCarry {
     int early_seq;                // chain walkers only (finish_walk<..., EARLY>): 1 + the index of this call among the chain's calls
     int status;                   // 0 no end cell (empty alignment), 1 end cell outside a (the reference throws), 2 walk from (x, y, pos)
@@ -132,9 +145,14 @@ __device__ __noinline__ void end_cell(const Tk* tp, const int lane, WalkCarry* w
 // span below the walk and the walk jumps over the passing prefix.  Two formats of checkpoint row: the two-task kernel's patterns
 // (PK, LP_WALK_SKIP_PAIR) and the int32 images of every other direction-free kernel (LP_WALK_SKIP_I32: k_align and k_align_q,
 // N-aware or not, LPT == 64 or one DPP row per task).
+// OPSRUN (a third instance, the default one holds none of it; LP_OPS_WALK_RUNS, taken per task by the ones with TF_WANT_OPS): the edit
+// string a diagonal run at a time.  Interior cells take the run consumer like a task without a string, and the lanes that compared the
+// run's bases write its ops: lane da + j owns steps 16 j .. 16 j + 15 from the top of the run (chunk j of the packed windows), the op
+// of a step is its bit of `eq` -- MATCH where set (an N on either side too), MISMATCH where not.  Row 0, pos == 0 and the gap steps
+// stay single steps.  It never makes the diagonal test and the chain walkers stay without it.
 template <bool PK> struct SkipIdx { typedef int64_t T; };   // a base index of the test's loads (the two-task instance keeps its 32-bit ones)
 template <> struct SkipIdx<true> { typedef int T; };
-template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool EARLY = false, bool SKIP = false>
+template <int C, int CE, bool HASN, int LPT = 64, bool PK = false, bool EARLY = false, bool SKIP = false, bool OPSRUN = false>
 __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, const LaunchParams* pp, const int lane, const int lane_base_, const int pk_half_, WalkCarry* wcp)
 {
     const int lane_base = (LPT == 64) ? 0 : uni(lane_base_);
@@ -142,6 +160,8 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
     typedef Strip<LPT, PK> ST;
     static_assert(!SKIP || (!EARLY && DIRFREE_OK<CE, C, HASN>), "the diagonal test reads checkpoint rows; the chain walkers stay without it");
     static_assert(!SKIP || (PK ? (LPT == 64 && !HASN) : (LPT == 64 || LPT == QL)), "the diagonal test knows the two-task kernel's checkpoint rows (PairFmt<C, 64>) and the int32 images of the one- and four-task kernels");
+    static_assert(!OPSRUN || !EARLY, "the chain walkers write their edit strings a step at a time");
+    static_assert(!OPSRUN || !SKIP, "a task that wants an edit string never makes the diagonal test");
     const Tk t = load_uniform(tp);
     const DevTask* dtp = unip(dtp_);
     const u32 dt_flags = (u32)uni((int)dtp->flags) & TF_LIVE_MASK, dt_res_idx = (u32)uni((int)dtp->res_idx);
@@ -210,6 +230,9 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
             // without a test.  A walk that walk_many began goes on from what that left in the carry (0 | 0 from end_cell else).
             [[maybe_unused]] const bool backoff = SKIP && (uni((int)pp->flags) & (int)LP_WALK_SKIP_BACKOFF) != 0;
             [[maybe_unused]] u32 bo_fails = 0, bo_hold = 0;
+            // OPSRUN: what this walk counted (LS_OPS_*): the ops its run iterations wrote and how many of those wrote any
+            [[maybe_unused]] u32 or_ops = 0, or_runs = 0;
+            [[maybe_unused]] const u32 or_len0 = len;
             if constexpr (SKIP) {
                 const u32 bo0 = (u32)uni(wcp->early_seq);
                 bo_fails = bo0 & 63u; bo_hold = bo0 >> WALK_BACKOFF_HOLD_SHIFT;
@@ -283,7 +306,7 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                 old_q = uni(old_q); old_lo = uni(old_lo); old_hi = uni(old_hi);
                 sa_w0 = uni64(sa_w0); sb_w0 = uni64(sb_w0);
                 if (HASN) { san_w0 = uni64(san_w0); sbn_w0 = uni64(sbn_w0); }
-                if (x == 0 || pos == 0 || want_ops) {
+                if (x == 0 || pos == 0 || (!OPSRUN && want_ops)) {
                     // single step with the reference's exact rules
                     const int pa = HASN ? code_at(t.a2, t.an, t.a_base + pos) : (int)((t.a2[(t.a_base + pos) >> 4] >> (((t.a_base + pos) & 15) * 2)) & 3);
                     const int64_t bi = t.b_base + t.begin_b + x;
@@ -544,11 +567,22 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                             if (!have_last) { have_last = true; la = pos - off_hi; lb = t.begin_b + x - off_hi; post_early((ST_OK << 8) | 2u, la, lb); }
                             have_first = true; fa = pos - off_lo; fb = t.begin_b + x - off_lo;
                         }
+                        if constexpr (OPSRUN) {
+                            // the run's ops, in traceback order: step s = 16 j + 15 - p from the top of the run is base p of this lane's
+                            // chunk, `msk` holds the bases that belong to the run (none for j < 0), `eq` those of them that are a MATCH
+#pragma unroll
+                            for (int p = 0; p < 16; ++p) {
+                                const u64 at = (u64)len + (u64)(16 * j + 15 - p);
+                                if (((msk >> (2 * p)) & 1u) && at < dt_ops_cap) ops[at] = (uint8_t)(3u - ((eq >> (2 * p)) & 1u));
+                            }
+                            or_ops += (u32)n; or_runs++;
+                        }
                         x -= n; pos -= n; len += (u32)n;
                         // the run ended at a gap whose direction word is in the cache: take that step right away
                         if (Ls >= 0 && n == n_run && x >= 1 && pos >= 1) {
                             const u32 w2 = (u32)__builtin_amdgcn_readlane((int)cw, Ls);
                             const u32 tag2 = (w2 >> (((x + l) & 15) * 2)) & 3u;
+                            if constexpr (OPSRUN) { if (len < dt_ops_cap) ops[len] = (tag2 == 1u) ? 0 : 1; }
                             if (tag2 == 1u) {  // GAP_A
                                 x--; y++;
                                 if (++c == C) { c = 0; l++; }
@@ -560,6 +594,7 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                         }
                     } else {
                         const u32 tag = (w_here >> (r * 2)) & 3u;
+                        if constexpr (OPSRUN) { if (len < dt_ops_cap) ops[len] = (tag == 1u) ? 0 : 1; }
                         if (tag == 1u) {  // GAP_A
                             x--; y++;
                             if (++c == C) { c = 0; l++; }
@@ -592,6 +627,13 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                 }
                 if (pp->stats != nullptr && lane == 0 && sk_held != 0) atomicAdd(unip(pp->stats) + LS_SKIP_HELD, sk_held);   // (gamdp_ctx_walk_skip_backoff_stats)
             }
+            if constexpr (OPSRUN) {
+                if (pp->stats != nullptr && lane == 0) {   // (gamdp_ctx_ops_walk_stats: steps, clipped or not)
+                    stat_add64(unip(pp->stats) + LS_OPS_BY_RUN, or_ops);
+                    stat_add64(unip(pp->stats) + LS_OPS_BY_STEP, len - or_len0 - or_ops);
+                    stat_add64(unip(pp->stats) + LS_OPS_RUNS, or_runs);
+                }
+            }
             if (dt_flags & TF_DIAG_COUNT_MAT) {  // diagnostics only: result unusable
                 res.n_match = (u32)mat_calls;
                 res.first_a = (int)mat_ticks + uni(wcp->mat_ticks);
@@ -599,6 +641,9 @@ __device__ __noinline__ void finish_walk(const Tk* tp, const DevTask* dtp_, cons
                 res.last_a = dg_iters; res.last_b = dg_refills;
             }
         }
+    }
+    if constexpr (OPSRUN) {
+        if (pp->stats != nullptr && lane == 0) atomicAdd(unip(pp->stats) + LS_OPS_TASKS, 1u);   // (every status: a task without a walk has no ops)
     }
 #ifdef GAMDP_DIAG
     if (uni(t.pos0[-1]) != 0) res.flags = ST_DIAG_RANGE << 8;   // a packed block of this task left the exact f16 range
@@ -625,6 +670,8 @@ __device__ __forceinline__ void finish_task(const Tk* tp, const DevTask* dtp, co
 {
     WalkCarry wc;
     end_cell<C>(tp, lane, &wc);
+    // (LP_OPS_WALK_RUNS: the instance that writes the edit string a run at a time -- wave-uniform, per task)
+    if (ops_walk_runs(pp, dtp)) { finish_walk<C, CE, HASN, LPT, PK, false, false, true>(tp, dtp, pp, lane, lane_base, pk_half, &wc); return; }
     // (LP_WALK_SKIP_I32: the instance whose walk makes the diagonal test -- wave-uniform, per launch)
     if constexpr (!PK && DIRFREE_OK<CE, C, HASN>) {
         if (pp->flags & LP_WALK_SKIP_I32) { finish_walk<C, CE, HASN, LPT, PK, false, true>(tp, dtp, pp, lane, lane_base, pk_half, &wc); return; }

@@ -32,6 +32,7 @@ SYMBOLS = [
     "gamdp_task_ops_cap", "gamdp_align_batch_fp", "gamdp_ctx_set_ops_chunk_bytes", "gamdp_ops_fingerprint_batch",
     "gamdp_ctx_ops_fp_info",
     "gamdp_task_live_columns",
+    "gamdp_ctx_set_ops_walk", "gamdp_ctx_ops_walk_stats",
 ]
 
 EINVAL, ENODEV, ENOMEM, ENOTSUP, EHIP = -1, -2, -3, -4, -5
@@ -41,6 +42,7 @@ L1_CHAIN_WALK, L1_CHAIN_CARRY = 0, 1   # gamdp_ctx_set_l1_chain
 L1_WALK_BAND_150, L1_WALK_ANY_BAND = 0, 1   # gamdp_ctx_set_l1_walk_bands
 WALK_STRIPS, WALK_SKIP_DIAG = 0, 1   # gamdp_ctx_set_walk_skip, gamdp_ctx_set_walk_skip_pair, gamdp_ctx_set_walk_skip_i32
 WALK_BACKOFF_OFF, WALK_BACKOFF_ON = 0, 1   # gamdp_ctx_set_walk_skip_backoff
+OPS_WALK_STEPS, OPS_WALK_RUNS = 0, 1   # gamdp_ctx_set_ops_walk
 ST_DIAG_RANGE = 9   # diagnostics build only: a packed-f16 block left the exact range (never expected)
 
 
@@ -197,6 +199,16 @@ class WalkSkipBackoffStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
+class OpsWalkStats(C.Structure):
+    """gamdp_ops_walk_stats: what the walks of the last gamdp_align_batch / gamdp_align_batch_fp that wrote their edit string a run at a
+    time counted (static_assert in gamdp_host.cpp)."""
+    _fields_ = [("tasks", C.c_uint64), ("ops_by_run", C.c_uint64), ("ops_by_step", C.c_uint64), ("runs", C.c_uint64),
+                ("mode", C.c_uint32), ("pad_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class L1TailCall(C.Structure):
     """gamdp_l1_tail_call: the seed of one tail alignment of the last gamdp_align_merge_blocks (static_assert in gamdp_hits.hip)."""
     _fields_ = [("begin_a", C.c_uint64), ("merge_block", C.c_uint32), ("right", C.c_uint8), ("source", C.c_uint8),
@@ -324,7 +336,8 @@ def load_library():
     for setter, getter, struct in (("gamdp_ctx_set_walk_skip", "gamdp_ctx_walk_skip_stats", WalkSkipStats),
                                    ("gamdp_ctx_set_walk_skip_pair", "gamdp_ctx_walk_skip_pair_stats", WalkSkipPairStats),
                                    ("gamdp_ctx_set_walk_skip_i32", "gamdp_ctx_walk_skip_i32_stats", WalkSkipI32Stats),
-                                   ("gamdp_ctx_set_walk_skip_backoff", "gamdp_ctx_walk_skip_backoff_stats", WalkSkipBackoffStats)):
+                                   ("gamdp_ctx_set_walk_skip_backoff", "gamdp_ctx_walk_skip_backoff_stats", WalkSkipBackoffStats),
+                                   ("gamdp_ctx_set_ops_walk", "gamdp_ctx_ops_walk_stats", OpsWalkStats)):
         if hasattr(lib, setter):
             getattr(lib, setter).argtypes = [vp, C.c_int]
             getattr(lib, setter).restype = C.c_int

@@ -271,6 +271,33 @@ typedef struct gamdp_walk_skip_backoff_stats {
 } gamdp_walk_skip_backoff_stats;   /* 32 bytes */
 int gamdp_ctx_walk_skip_backoff_stats(const gamdp_ctx* ctx, gamdp_walk_skip_backoff_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
 
+/* How the walks of the thirteen systolic kernels (every kernel of gamdp_launch_info but "k_align_w") write the edit string of a call
+ * that wants one: gamdp_align_batch with a gamdp_ops, every call of gamdp_align_batch_fp.
+ *   GAMDP_OPS_WALK_STEPS  the default: such a walk takes one step per iteration and writes one op.
+ *   GAMDP_OPS_WALK_RUNS   opt-in: away from row 0 and pos == 0 such a walk consumes a whole run of diagonal steps per iteration, as
+ *       the walk of a call without a string does, and the 64 lanes that compared the run's bases write its MATCH / MISMATCH ops, 16
+ *       steps each.  Gap steps, row 0 and pos == 0 stay single steps.
+ * Results and the bytes of every edit string (clipped ones too: nothing is written at or behind a string's capacity) do not depend on
+ * the mode.  "k_align_w", the merge-block chains and calls that want no string ignore it; a walk that wants a string makes no
+ * diagonal test in either mode.  gamdp_multi_* honours each context's own setting; GAMDP_OPS_WALK_RUNS=1 in the environment (read once
+ * per process) makes RUNS the mode of new contexts. */
+#define GAMDP_OPS_WALK_STEPS 0   /* default */
+#define GAMDP_OPS_WALK_RUNS  1
+int gamdp_ctx_set_ops_walk(gamdp_ctx* ctx, int mode);   /* GAMDP_EINVAL for NULL / unknown mode (mode checked first) */
+/* What the walks of the last gamdp_align_batch / gamdp_align_batch_fp on this context that wrote their string in RUNS mode counted
+ * on the device, summed over the call's launches, pieces and chunks.  Steps, not bytes: an op clipped by its string's capacity
+ * counts.  ops_by_run + ops_by_step = the sum of gamdp_result.length over the counted calls with status GAMDP_ST_OK.  In STEPS
+ * mode, and before the first call, the four counters are 0; "k_align_w" calls are never counted. */
+typedef struct gamdp_ops_walk_stats {
+    uint64_t tasks;            /* calls that wanted a string and walked in RUNS mode (whatever their status) */
+    uint64_t ops_by_run;       /* ops of run iterations: the diagonal steps taken from cells with x >= 1 and pos >= 1 */
+    uint64_t ops_by_step;      /* every other op of those walks (gaps, row 0, pos == 0) */
+    uint64_t runs;             /* run iterations that took at least one step */
+    uint32_t mode;             /* GAMDP_OPS_WALK_* the call ran in */
+    uint32_t pad_;
+} gamdp_ops_walk_stats;        /* 40 bytes */
+int gamdp_ctx_ops_walk_stats(const gamdp_ctx* ctx, gamdp_ops_walk_stats* out);   /* GAMDP_EINVAL for NULL ctx / out */
+
 /* ---- sequences ---------------------------------------------------------------------------- */
 /* seqs[i] points to lens[i] bytes: ASCII bases when is_ascii!=0 (normalised like Nucleotide(char)),
  * else base codes A=0 T=1 C=2 G=3 N=4.  Packs to 2 bit + N mask and uploads to the ctx's GPU. */

@@ -23,6 +23,10 @@ int gamdp_ctx_walk_skip_pair_stats(const gamdp_ctx* ctx, gamdp_walk_skip_pair_st
 /* (... and in the int32 direction-free kernels) */
 int gamdp_ctx_set_walk_skip_i32(gamdp_ctx* ctx, int mode) { (void)ctx; (void)mode; return GAMDP_ENODEV; }
 int gamdp_ctx_walk_skip_i32_stats(const gamdp_ctx* ctx, gamdp_walk_skip_i32_stats* out) { (void)ctx; (void)out; return GAMDP_ENODEV; }
+/* (a bridge that opts in to GAMDP_OPS_WALK_RUNS for the edit strings of its batches links against these two) */
+int gamdp_ctx_set_ops_walk(gamdp_ctx* ctx, int mode)
+{ return ((mode != GAMDP_OPS_WALK_STEPS && mode != GAMDP_OPS_WALK_RUNS) || !ctx) ? GAMDP_EINVAL : GAMDP_ENODEV; }
+int gamdp_ctx_ops_walk_stats(const gamdp_ctx* ctx, gamdp_ops_walk_stats* out) { return (!ctx || !out) ? GAMDP_EINVAL : GAMDP_ENODEV; }
 /* (a bridge that checks the edit strings of its batches links against these three; the fingerprint needs no device and is the real one) */
 int gamdp_carry_ops_batch(gamdp_ctx* ctx, const gamdp_seqset* set_a, const gamdp_seqset* set_b, const gamdp_task* tasks, size_t n,
                           gamdp_result* out, uint32_t* ops_fp)

@@ -16,6 +16,7 @@
 // 160 - 543, N-holding band-150 batches on the four-task kernel; the output does not change).
 // --walk-skip-backoff lets the walks of either stop testing for a while after tests that skipped nothing
 // (gamdp_ctx_set_walk_skip_backoff; it does nothing without --walk-skip / --walk-skip-i32; the output does not change).
+// There is no flag for gamdp_ctx_set_ops_walk: a merge-block call never asks for an edit string, and the property is about nothing else.
 // --devices runs the step on several GPUs of the node (gamdp_multi_*: merge blocks partitioned statically by predicted
 // cells, one host thread + context per device, no collective); a device may be listed twice.  The output is the same
 // whatever the device list -- unlike gam-merge --threads N, whose paired-contig order depends on thread timing.
@@ -61,7 +62,8 @@ static int region_vote(void*, int32_t, int32_t, int32_t, int32_t, int32_t, int32
 int main(int argc, char** argv)
 {
     if (argc < 5) die("usage: gamdp-align-mb <master.fasta> <slave.fasta> <mergeblocks.tsv> <out.tsv> [--band N] [--device D] [--repeat K] "
-                      "[--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]] [--device-hits] [--carry-chains] [--walk-any-band] [--walk-skip] [--walk-skip-i32] [--walk-skip-backoff]");
+                      "[--pctgs PREFIX] [--vote master|slave|fail] [--blocks all.blocks [--blocks-filtered kept.blocks]] [--device-hits] [--carry-chains] [--walk-any-band] [--walk-skip] [--walk-skip-i32] [--walk-skip-backoff]\n"
+                      "(no flag for gamdp_ctx_set_ops_walk: merge-block calls never ask for edit strings)");
     unsigned band = GAMDP_DEFAULT_BAND;
     int device = 0, repeat = 1;
     std::vector<int> devices;

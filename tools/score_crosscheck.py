@@ -33,6 +33,13 @@ of the last repetition), align_fp_wall_ms (the whole call) and align_fp_bytes_to
 --ops beside it in every repetition, the two alternating (align_ops_wall_ms: the call, the reversal inside it and the host's
 fingerprints; align_ops_bytes_to_host), for measurements of one against the other in one process.
 
+With --ops --ops-walk-runs every call that returns or fingerprints edit strings runs twice in each repetition, alternating on the one
+context: in GAMDP_OPS_WALK_STEPS and in GAMDP_OPS_WALK_RUNS mode (gamdp_ctx_set_ops_walk: the walks write the strings a diagonal run at
+a time).  Both modes are compared with gamdp_carry_ops_batch (the mismatch counts cover both); the usual keys hold the STEPS figures, and
+ops_walk_runs holds the RUNS ones -- the same kernel-time lists, align_fp_launch_ms (the alignment launches alone: the call without
+k_ops_fp; align_fp_launch_ms at the top level is STEPS's, align_kernel_ms the same launches without strings) and
+gamdp_ctx_ops_walk_stats of the last call.
+
 Workloads:  --pairs N --len L --band B   N synthetic pairs of L bases (SequenceSet.synthetic), whole-sequence windows
             --mixed N                    N calls shaped like the merge-block driver's (tests/_mixed.py), band --band (default 150)
 
@@ -73,10 +80,13 @@ def main():
     ap.add_argument("--ops", action="store_true", help="also run gamdp_carry_ops_batch and compare the fingerprints of gamdp_align_batch's edit strings")
     ap.add_argument("--device-fp", action="store_true", help="with --ops: the align side's fingerprints from gamdp_align_batch_fp (the strings stay on the device)")
     ap.add_argument("--host-fp-too", action="store_true", help="with --ops --device-fp: also the download path of plain --ops, alternating with it")
+    ap.add_argument("--ops-walk-runs", action="store_true", help="with --ops: every edit-string call in GAMDP_OPS_WALK_STEPS and GAMDP_OPS_WALK_RUNS mode, alternating")
     ap.add_argument("--ops-chunk-bytes", type=int, default=0, help="gamdp_ctx_set_ops_chunk_bytes (0: the default, 1 GiB)")
     args = ap.parse_args()
     if (args.device_fp and not args.ops) or (args.host_fp_too and not args.device_fp):
         ap.error("--device-fp goes with --ops, --host-fp-too with --device-fp")
+    if args.ops_walk_runs and not args.ops:
+        ap.error("--ops-walk-runs goes with --ops")
     if bool(args.pairs) == bool(args.mixed):
         ap.error("one of --pairs N or --mixed N")
     if args.walk_skip_pair and not args.carry:
@@ -126,7 +136,11 @@ def main():
     if args.device_fp:
         res_d, fp_d = (L.Result * n)(), (C.c_uint32 * n)()
         ctx.set_ops_chunk_bytes(args.ops_chunk_bytes)
-    dev_ms, dev_fp_ms, dev_wall_ms, host_wall_ms = [], [], [], []
+    # (--ops-walk-runs: the lists of the second mode, RUNS, are the ones with index 1)
+    walk_modes = (L.OPS_WALK_STEPS, L.OPS_WALK_RUNS) if args.ops_walk_runs else (None,)
+    per_mode = lambda: tuple([] for _ in walk_modes)  # noqa: E731
+    dev_ms_m, dev_fp_ms_m, dev_wall_ms_m, host_wall_ms_m, align_ops_ms_m = per_mode(), per_mode(), per_mode(), per_mode(), per_mode()
+    walk_stats = None
     dev_mismatches, dev_first_bad, fp_info = 0, None, None
     if host_fp_path:
         caps = [sset.lengths[t.a_id] + sset.lengths[t.b_id] + 2 * t.band + 64 for t in tasks]
@@ -137,7 +151,7 @@ def main():
         buf = C.create_string_buffer(max(1, ops_bytes))
         buf_addr = C.addressof(buf)
         ops_struct = L.Ops(C.cast(buf, C.c_void_p), (C.c_uint64 * n)(*offs), (C.c_uint64 * n)(*caps))
-    align_ops_ms, ops_ms = [], []
+    ops_ms = []
     ops_mismatches, ops_first_bad = 0, None
     mismatches, first_bad = 0, None
     carry_mismatches, carry_first_bad = 0, None
@@ -168,37 +182,47 @@ def main():
             f_ms = ctx.kernel_time(reset=True)[0]
             if rep:
                 ops_ms.append(f_ms)
-        if host_fp_path:
+        for m, mode in enumerate(walk_modes if host_fp_path else ()):
+            if mode is not None:
+                ctx.set_ops_walk(mode)
             t0 = time.perf_counter()
             rc = ctx.lib.gamdp_align_batch(ctx.handle, sset.handle, sset.handle, tasks, n, res_o, C.byref(ops_struct))
             assert rc == 0, ("gamdp_align_batch with edit strings", rc, ctx.last_error())
             host_fps = [ctx.lib.gamdp_ops_fingerprint(C.c_char_p(buf_addr + offs[i]), res_o[i].length) if res_o[i].status == 0 else 0 for i in range(n)]
             wall = (time.perf_counter() - t0) * 1e3
             ao_ms = ctx.kernel_time(reset=True)[0]
+            if mode == L.OPS_WALK_RUNS:
+                walk_stats = ctx.ops_walk_stats()
             if rep:
-                align_ops_ms.append(ao_ms)
-                host_wall_ms.append(wall)
+                align_ops_ms_m[m].append(ao_ms)
+                host_wall_ms_m[m].append(wall)
             for i in range(n):   # (a status other than OK has no edit string: fingerprint 0 on both sides)
                 if host_fps[i] != fp[i] or whole(res_o[i]) != whole(res_f[i]):
                     ops_mismatches += 1
                     if ops_first_bad is None:
                         ops_first_bad = dict(task=i, align_fp=host_fps[i], carry_fp=fp[i], align=whole(res_o[i]), carry=whole(res_f[i]))
-        if args.device_fp:
+        for m, mode in enumerate(walk_modes if args.device_fp else ()):
+            if mode is not None:
+                ctx.set_ops_walk(mode)
             t0 = time.perf_counter()
             rc = ctx.lib.gamdp_align_batch_fp(ctx.handle, sset.handle, sset.handle, tasks, n, res_d, fp_d)
             wall = (time.perf_counter() - t0) * 1e3
             assert rc == 0, ("gamdp_align_batch_fp", rc, ctx.last_error())
             d_ms = ctx.kernel_time(reset=True)[0]
             fp_info = ctx.ops_fp_info()
+            if mode == L.OPS_WALK_RUNS:
+                walk_stats = ctx.ops_walk_stats()
             if rep:
-                dev_ms.append(d_ms)
-                dev_fp_ms.append(fp_info["kernel_ms"])
-                dev_wall_ms.append(wall)
+                dev_ms_m[m].append(d_ms)
+                dev_fp_ms_m[m].append(fp_info["kernel_ms"])
+                dev_wall_ms_m[m].append(wall)
             for i in range(n):
                 if fp_d[i] != fp[i] or whole(res_d[i]) != whole(res_f[i]):
                     dev_mismatches += 1
                     if dev_first_bad is None:
                         dev_first_bad = dict(task=i, align_fp=fp_d[i], carry_fp=fp[i], align=whole(res_d[i]), carry=whole(res_f[i]))
+        if args.ops_walk_runs:
+            ctx.set_ops_walk(L.OPS_WALK_STEPS)
         if rep:
             align_ms.append(a_ms)
             score_ms.append(s_ms)
@@ -214,6 +238,7 @@ def main():
                 if carry_first_bad is None:
                     carry_first_bad = dict(task=i, align=whole(res[i]), carry=whole(ca[i]))
     cells = sum(r.cells for r in res)
+    dev_ms, dev_fp_ms, dev_wall_ms, host_wall_ms, align_ops_ms = dev_ms_m[0], dev_fp_ms_m[0], dev_wall_ms_m[0], host_wall_ms_m[0], align_ops_ms_m[0]
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
     rec = dict(workload, tasks=n, mismatches=mismatches, first_mismatch=first_bad, ok=sum(1 for r in res if r.status == 0), cells=cells,
                align_kernels=sorted({r["kernel"] for r in ctx.launch_info()}), score_kernels=[r["kernel"] for r in ctx.score_info()],
@@ -241,6 +266,17 @@ def main():
         rec.update(device_fp_mismatches=dev_mismatches, device_fp_first_mismatch=dev_first_bad, align_fp_kernel_ms=[round(v, 3) for v in dev_ms],
                    ops_fp_kernel_ms=[round(v, 4) for v in dev_fp_ms], ops_fp_info=fp_info, ops_fp_gb_per_s=round(gbs, 1) if gbs else None,
                    align_fp_wall_ms=[round(v, 2) for v in dev_wall_ms], align_fp_bytes_to_host=44 * n)
+    launch_ms = lambda call, fold: [round(a - b, 3) for a, b in zip(call, fold)]  # noqa: E731
+    if args.device_fp:
+        rec.update(align_fp_launch_ms=launch_ms(dev_ms, dev_fp_ms))
+    if args.ops_walk_runs:
+        runs = dict(stats=walk_stats)
+        if host_fp_path:
+            runs.update(align_ops_kernel_ms=[round(v, 3) for v in align_ops_ms_m[1]], align_ops_wall_ms=[round(v, 2) for v in host_wall_ms_m[1]])
+        if args.device_fp:
+            runs.update(align_fp_kernel_ms=[round(v, 3) for v in dev_ms_m[1]], ops_fp_kernel_ms=[round(v, 4) for v in dev_fp_ms_m[1]],
+                        align_fp_launch_ms=launch_ms(dev_ms_m[1], dev_fp_ms_m[1]), align_fp_wall_ms=[round(v, 2) for v in dev_wall_ms_m[1]])
+        rec.update(ops_walk_runs=runs)
     print(json.dumps(rec), flush=True)
     sset.close()
     sys.exit(0 if mismatches == 0 and carry_mismatches == 0 and ops_mismatches == 0 and dev_mismatches == 0 else 1)
